@@ -20,7 +20,7 @@ broadcast of the coefficient table from rank 0.
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  After the timed region rank 0
 copies four output frames back and compares them, whole, with the CPU restatement of the reference (oracle/,
 the checker — never on the measured path): the "parity" record; a violation of the stated tolerance makes the
-exit code 3.
+exit code 3.  --dump-outputs DIR also writes what the last timed step computed to DIR/*.npy (dump_outputs()).
 """
 import argparse
 import json
@@ -95,7 +95,14 @@ def parse(argv=None):
                    "barriers run on RCCL on a one-GPU box (tests/test_gpu_configs.py); the measurement is unchanged")
     p.add_argument("--alloc-frames", type=int, default=0, help="experiment: size the device buffers for this "
                    "many frames (>= --frames) but process only --frames of them")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step "
+                   "left in the output pool to DIR/*.npy (float32; the whole output when it fits, else a fixed seeded "
+                   "sample of whole rows of the parity frames; see dump_outputs()), so that two builds can be compared "
+                   "output for output")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 # ---- the multi-rank logic, kept in functions so tests/test_multi_rank.py runs THESE under gloo ---------------
@@ -192,6 +199,43 @@ def sample_frame_ids(nframes, seed=0x5EED):
             break
         ids.add(int(rng.integers(0, nframes)))
     return sorted(ids)
+
+
+DUMP_BYTES = 48 << 20  # float32 bytes of output one --dump-outputs run writes, over all ranks (cap: 64 MB)
+
+
+def dump_selection(nframes, h, w, out_bpp, budget=DUMP_BYTES, seed=0x5EED):
+    """(local frame ids, row ids) that --dump-outputs writes: every frame and row when they fit `budget` as float32;
+    otherwise the parity frames (sample_frame_ids) and, in each, the same whole rows: the three at either edge
+    (where the filters' borders are) and seeded-random ones up to the budget.  Depends on the shape alone."""
+    if nframes * h * w * out_bpp * 4 <= budget:
+        return list(range(nframes)), list(range(h))
+    frames = sample_frame_ids(nframes, seed)
+    nrows = max(1, min(h, budget // (len(frames) * w * out_bpp * 4)))
+    rows = sorted({r for r in (0, 1, 2, h - 3, h - 2, h - 1) if 0 <= r < h})[:nrows]
+    rest = np.setdiff1d(np.arange(h), rows)
+    pick = np.random.default_rng(seed).choice(rest, size=min(nrows - len(rows), rest.size), replace=False)
+    return frames, sorted(rows + [int(r) for r in pick])
+
+
+def dump_outputs(dirname, d_out, first_frame, rank, world, budget=DUMP_BYTES):
+    """Write the output pool d_out ((F, h, w, bpp) uint8 on the device), or the dump_selection() sample of it, as
+    DIR/output.npy (float32, (frames, rows, w, bpp), or (frames, rows, w) for one-byte outputs, as the host-buffer
+    calls return them), with DIR/output_frames.npy (global frame indices) and DIR/output_rows.npy (row indices) in
+    float64.  Ranks other than 0 add "_rank<r>" to the names."""
+    import torch
+    F, h, w, out_bpp = d_out.shape
+    frames, rows = dump_selection(F, h, w, out_bpp, budget // world)
+    dev = d_out.device
+    sel = d_out.index_select(0, torch.tensor(frames, device=dev)).index_select(1, torch.tensor(rows, device=dev))
+    out = sel.cpu().numpy().astype(np.float32)
+    if out_bpp == 1:
+        out = out[..., 0]
+    tag = "" if rank == 0 else "_rank%d" % rank
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "output%s.npy" % tag), out)
+    np.save(os.path.join(dirname, "output_frames%s.npy" % tag), np.asarray(frames, np.float64) + first_frame)
+    np.save(os.path.join(dirname, "output_rows%s.npy" % tag), np.asarray(rows, np.float64))
 
 
 def oracle_frame(oracle, name, frame, k, table, threads):
@@ -327,8 +371,9 @@ def main(argv=None):
             d_in[f, :, :, :3] = big[oy:oy + h, ox:ox + w]
         d_in[..., 3] = 255
         del big
-    if args.random_alpha:
-        d_in[..., 3] = torch.randint(0, 256, (F, h, w), dtype=torch.uint8, device=dev)
+    if args.random_alpha:  # seeded per rank: the same arguments give the same frames in every run
+        gen = torch.Generator(device=dev).manual_seed(0x5EED + first_frame)
+        d_in[..., 3] = torch.randint(0, 256, (F, h, w), dtype=torch.uint8, device=dev, generator=gen)
     if 0 <= args.const_alpha <= 255:
         d_in[..., 3] = args.const_alpha
 
@@ -422,6 +467,8 @@ def main(argv=None):
     kernel_ms = ctx.timer_end()  # hipEventRecord + hipEventSynchronize + hipEventElapsedTime
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # before the side figures below re-use the output pool
+        dump_outputs(args.dump_outputs, d_out, first_frame, rank, world)
 
     # one launch per step: average launch duration from the HIP events around the timed region
     avg_launch_ms = kernel_ms / args.steps

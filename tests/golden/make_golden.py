@@ -8,6 +8,8 @@ What is committed and where it comes from:
   gauss_weights_ref.json     OUTPUT OF THE REFERENCE ITSELF: Controller::_GenerateGausianKernel compiled
                              from /root/reference (oracle/Makefile target `ref`), float bit patterns.
                              These are the golden vectors that pin the weight generator.
+  gauss_weights_ref_grid.json the same generator (buffer layout) on the grid GRID_K x GRID_SIGMA, which
+                             tests/test_oracle.py compares the oracle with wherever oracle/_ref is absent.
   oracle_regression.json     sha256 of the oracle's outputs on the fixture image and on synthetic frames.
                              Produced by OUR restatement, so they pin nothing about the reference: they
                              only detect an accidental change of the oracle ("parity unpinned" paths).
@@ -31,6 +33,16 @@ WEIGHT_CASES = [(1, 1.0), (3, 0.5), (3, 0.8), (3, 1.0), (5, 1.0), (5, 1.5), (5, 
                 (9, 2.5), (11, 3.0), (13, 3.3), (15, 4.0), (17, 6.0), (21, 5.0), (31, 10.0), (63, 20.0)]
 
 
+GRID_K = (1, 3, 5, 7, 9, 17, 25)
+GRID_SIGMA = (0.4, 1.0, 1.5, 2.2, 6.0, 11.0)
+
+
+def grid_weights():
+    """{"k=..,sigma=..": float bit patterns} of the reference build over GRID_K x GRID_SIGMA."""
+    return {"k=%d,sigma=%r" % (k, s): [int(v) for v in O.ref_gauss_weights(k, s).reshape(-1).view(np.uint32)]
+            for k in GRID_K for s in GRID_SIGMA}
+
+
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
@@ -50,6 +62,7 @@ def main():
             key = "k=%d,sigma=%r,%s" % (k, s, "image2d" if image_support else "buffers")
             weights[key] = [int(v) for v in w.reshape(-1).view(np.uint32)]
     json.dump(weights, open(os.path.join(HERE, "gauss_weights_ref.json"), "w"), indent=0)
+    json.dump(grid_weights(), open(os.path.join(HERE, "gauss_weights_ref_grid.json"), "w"), indent=0)
 
     rgba = np.dstack([img, np.full(img.shape[:2], 255, np.uint8)])
     bgr = img[..., ::-1]

@@ -14,12 +14,13 @@ published about its own runs, the PNGs hold decoded PIXELS of its test images.
   ref_images/<name>_y.png     the same file decoded as cv::imread(IMREAD_GRAYSCALE) decodes a JPEG: the decoder's
                        own luma plane (libjpeg out_color_space = JCS_GRAYSCALE; PIL: Image.draft('L', size)).
                        This is the input of the reference's CPU Sobel (EdgeDetection.cpp:202).
-The two largest images (1023x819, 683x1023; 3.4 MB as PNG) are not committed: the test decodes them live where
-/root/reference exists (this container) and skips them elsewhere.
+  ref_jpeg/<name>.jpg   images/<name>.jpg itself, byte for byte (all eight).  The two largest images (1023x819,
+                       683x1023; 3.4 MB as PNG) are not stored decoded: the test decodes these JPEG files itself.
 """
 import csv
 import json
 import os
+import shutil
 
 import numpy as np
 from PIL import Image
@@ -68,6 +69,9 @@ def main():
             Image.fromarray(rgb).save(os.path.join(HERE, "ref_images", n + "_rgb.png"), optimize=True)
         Image.fromarray(y).save(os.path.join(HERE, "ref_images", n + "_y.png"), optimize=True)
         print(n, rgb.shape)
+    os.makedirs(os.path.join(HERE, "ref_jpeg"), exist_ok=True)
+    for n in NAMES:
+        shutil.copyfile(os.path.join(REF, "images", n + ".jpg"), os.path.join(HERE, "ref_jpeg", n + ".jpg"))
 
 
 if __name__ == "__main__":

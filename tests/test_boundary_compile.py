@@ -1,9 +1,11 @@
 """SURVEY.md §8(b), first sentence: the reference application must compile UNCHANGED against this build's
 Controller / ProgramHandler / Logger / FileHandler / Comparator headers and CL/cl.h.
 
-The file is compiled where it lies (/root/reference, never copied), syntax-only, against host/include plus a
-test-only declaration stub of the few cv:: names it uses (tests/stubs/opencv2: OpenCV is not installed here).
-This is an interface check, not a parity check; it is skipped where /root/reference does not exist (the GPU box)."""
+The application is compiled where it lies by oracle/Makefile (target `ref`, run by build() where the reference tree
+exists; its source is never copied), against host/include plus a test-only declaration stub of the few cv:: names it
+uses (tests/stubs/opencv2: OpenCV is not installed here), into oracle/_ref/RealtimeImageProcessing.o, which travels
+with oracle/_ref.  This is an interface check, not a parity check: the first test is skipped where oracle/_ref was not
+built; the second needs nothing but g++."""
 import os
 import shutil
 import subprocess
@@ -12,22 +14,44 @@ import pytest
 
 import __graft_entry__ as entry
 
-REF_APP = "/root/reference/src/RealtimeImageProcessing/RealtimeImageProcessing.cpp"
 HOST_INC = os.path.join(entry.PKG_DIR, "host", "include")
+HOST_LIB = os.path.join(entry.PKG_DIR, "lib", "libmi355_host.so")
 STUBS = os.path.join(entry.ROOT, "tests", "stubs")
+APP_OBJ = os.path.join(entry.ROOT, "oracle", "_ref", "RealtimeImageProcessing.o")
+APP_ERR = os.path.join(entry.ROOT, "oracle", "_ref", "RealtimeImageProcessing.err")
+HOST_CLASSES = ("Controller::", "ProgramHandler::", "Logger::", "FileHandler::", "Comparator::")
 
-needs_ref = pytest.mark.skipif(not os.path.exists(REF_APP) or shutil.which("g++") is None,
-                               reason="/root/reference (or g++) is not present on this machine")
+needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ is not present on this machine")
 
 
-@needs_ref
+def _nm(*args):
+    """Mangled symbol names nm lists (no spaces in them: the name is the line's last field)."""
+    run = subprocess.run(["nm"] + list(args), capture_output=True, text=True, check=True)
+    return [ln.split()[-1] for ln in run.stdout.splitlines() if ln.strip()]
+
+
+def _demangle(symbols):
+    run = subprocess.run(["c++filt"], input="\n".join(symbols) + "\n", capture_output=True, text=True, check=True)
+    return run.stdout.splitlines()
+
+
 def test_reference_application_compiles_unchanged_against_the_host_headers():
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-I", HOST_INC, "-I", STUBS, REF_APP]
-    run = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stderr[-4000:]
+    """The object oracle/Makefile compiled, and every host-API symbol it leaves undefined (the Controller /
+    ProgramHandler / Logger / FileHandler / Comparator members and the cl* calls; cv:: and the C++ runtime aside)
+    is exported by lib/libmi355_host.so."""
+    if not os.path.exists(APP_OBJ):
+        if os.path.exists(APP_ERR):
+            pytest.fail("the reference application does not compile against host/include:\n" + open(APP_ERR).read()[-4000:])
+        pytest.skip("oracle/_ref not built here")
+    undefined = _nm("-u", APP_OBJ)
+    names = dict(zip(undefined, _demangle(undefined)))
+    wanted = sorted(m for m, d in names.items() if d.startswith(HOST_CLASSES) or d.startswith("cl"))
+    assert wanted, names
+    exported = set(_nm("-D", "--defined-only", HOST_LIB))
+    assert [names[m] for m in wanted if m not in exported] == []
 
 
-@needs_ref
+@needs_gxx
 def test_every_member_the_application_calls_is_declared_with_the_reference_signature(tmp_path):
     """Belt and braces for the check above: take the address of every Controller / ProgramHandler / Logger member
     RealtimeImageProcessing.cpp:435-442,351-355,372-376,398-402,423-426 uses, with the exact pointer-to-member

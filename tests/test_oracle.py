@@ -1,11 +1,13 @@
 """CPU suite: the oracle against the reference-built golden vectors, hand-derivable known answers
  and an independent numpy restatement.  No GPU."""
 import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
 
-from conftest import rand_rgba
+from conftest import GOLDEN, rand_rgba
 
 
 def sha(a):
@@ -45,14 +47,16 @@ def test_float_exp_variant_is_rejected_by_the_pin(oracle, golden_weights):
 
 
 def test_weights_against_live_reference_build(oracle):
-    """Where oracle/_ref exists (built from /root/reference by oracle/Makefile), compare live."""
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built here")
-    for k in (1, 3, 5, 7, 9, 17, 25):
-        for sigma in (0.4, 1.0, 1.5, 2.2, 6.0, 11.0):
-            a = oracle.gauss_weights(k, sigma).view(np.uint32)
-            r = oracle.ref_gauss_weights(k, sigma).view(np.uint32)
-            assert np.array_equal(a, r), (k, sigma)
+    """The reference build's output on a grid of (k, sigma), stored in gauss_weights_ref_grid.json (written from
+    oracle/_ref by tests/golden/make_golden.py); where oracle/_ref exists, the stored vectors are checked live too."""
+    grid = json.load(open(os.path.join(GOLDEN, "gauss_weights_ref_grid.json")))
+    assert len(grid) == 42
+    for key, bits in grid.items():
+        k, sigma = int(key.split(",")[0][2:]), float(key.split(",")[1][6:])
+        a = oracle.gauss_weights(k, sigma).reshape(-1).view(np.uint32)
+        assert a.tolist() == bits, key
+        if oracle.have_ref():
+            assert oracle.ref_gauss_weights(k, sigma).reshape(-1).view(np.uint32).tolist() == bits, key
 
 
 def test_weights_known_values(oracle):
