@@ -1,12 +1,13 @@
 // gauss_mfma_reg.hip — separable Gaussian blur of RGBA8 frames on the matrix cores, every matrix operand born in the
 // register layout the instruction wants (no LDS staging of the input).  Any odd k <= 17 (the reference application's
-// own default is k = 17, sigma = 6: include/ProgramHandler.hpp:9), width % 4 == 0.  gfx950 only.  Same arithmetic and
-// contract as gauss_mfma.hip (within 1 LSB per channel of the CPU path, src/GaussianBlur/GaussianBlur.cpp:234-261;
-// fp16 hi + lo splits of weights and intermediate, everything scaled by 256, see there); a different skeleton.
+// own default is k = 17, sigma = 6: include/ProgramHandler.hpp:9), width % 4 == 0.  gfx950 only.  FAST contract: within
+// 1 LSB per channel of the CPU path (src/GaussianBlur/GaussianBlur.cpp:234-261).  Bytes are exact in fp16; every fp32
+// weight and the fp32 intermediate of pass 1 are split hi + lo (two fp16) and both parts accumulate in fp32; weights are
+// scaled by 256 so that every lo part stays a normal fp16 and the intermediate 256 * H <= 65280 still fits fp16.
 //
-// gauss_mfma.hip stages fp16 planes in LDS (vertical pass first, hardware-transposed reads) and is bound by its
+// An LDS-staged version (fp16 planes in LDS, vertical pass first, hardware-transposed reads) was bound by its
 // workgroup-synchronous chain — load, convert, LDS, barrier, transposed reads, matrix chain, output tile, barrier —
-// at 4.0-4.36 TB/s whatever is removed from it.  Here the HORIZONTAL pass comes first:
+// at 4.0-4.36 TB/s whatever was removed from it.  Here the HORIZONTAL pass comes first:
 //   pass 1  H[y][x'] = sum_x X[y][x] * Th[x][x']       A = X: lane (m, g) of v_mfma_f32_16x16x32_f16 supplies row m,
 //           k = 8g .. 8g+7 — EIGHT CONSECUTIVE PIXELS OF ONE ROW, which is what a 32-byte global load returns.  The
 //           lane splits its 8 RGBA pixels into four channel operands (pixel pairs deinterleaved once, then one
@@ -146,8 +147,8 @@ __global__ __launch_bounds__(kThreadsR) void gauss_mfma_reg_kernel(const uint8_t
     };
 
     // Per wave: every pixel of the 32-pixel window inside the image (INTERIOR) or not; two instantiations entered
-    // through one scalar branch (see gauss_mfma.hip: as sibling branches inside the loop the two load paths make hipcc
-    // drain the memory counter before every load).
+    // through one scalar branch (as sibling branches inside the loop the two load paths make hipcc drain the memory
+    // counter before every load).
     auto walk = [&](auto interior_tag) {
         constexpr bool INTERIOR = decltype(interior_tag)::value;
         // Loads are issued in the COALESCED arrangement — lane 4r + p reads piece p of row r, four adjacent lanes one

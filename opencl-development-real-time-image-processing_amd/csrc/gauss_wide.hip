@@ -66,7 +66,7 @@ __device__ __forceinline__ bool gauss_wide_band(const WideLane& L, const float (
     // at k = 17 that is 51 instead of 102: 139 VGPRs instead of 223, 3 waves per SIMD instead of 2.  The vertical sums of an
     // output row are formed when its window is complete, by v_fma_mix_f32 (fp32 multiply-add with an fp16 source,
     // converted exactly): the same canonical chain, the same bits.  v_fma_mix issues at ~3 cycles instead of 2
-    // (tools/probe_valu.hip), which the doubled occupancy more than pays for.
+    // (profiles/r02_probe_valu.txt), which the doubled occupancy more than pays for.
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     h2 ring[K][NCH];
     // horizontal pass: output pixel e of this lane reads strip pixels 2*lane + e - R + t = row entries

@@ -162,7 +162,7 @@ hipError_t launch_gray(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, 
     const bool aligned = ((reinterpret_cast<uintptr_t>(d_in) & 15u) == 0) &&
                          ((reinterpret_cast<uintptr_t>(d_out) & (one_channel ? 3u : 15u)) == 0);
     const size_t nquads = aligned ? npx / 4 : 0;
-    // grid-stride; measured on MI355X (tools/membench.hip): a flat 16 B/lane stream runs 5.3 TB/s with
+    // grid-stride; measured on MI355X (profiles/r01_membench.txt): a flat 16 B/lane stream runs 5.3 TB/s with
     // 2,048 blocks, 6.2-6.4 TB/s with >= 8k blocks and non-temporal loads + stores; this kernel: 4.8 / 5.6 / 5.9 / 6.3 TB/s at 2k / 8k / 64k / 256k+ blocks
     static const unsigned kCap = [] {
         const char* e = tune_env("MI355_TUNE_GRAY_BLOCKS");  // tuning sweeps only

@@ -2,8 +2,8 @@
 // k in {3, 5}, width % 8 == 0, aligned buffers.  gfx950 only.  Same definition (SURVEY.md §8a "a-pipe",
 // oracle_pipeline_rgba), same arithmetic ("exact by exception", exact_common.hpp), the same bits as pipe_slide.hip.
 //
-// Why: pipe_slide.hip is bound by the work of its waves (its rate is proportional to the lanes a strip uses:
-// tools/lanes_sweep_pipeline.sh), ~160 instructions per wave-row of 240 pixels.  With 8 pixels per lane a wave-row
+// Why: pipe_slide.hip is bound by the work of its waves (its rate is proportional to the lanes a strip uses,
+// measured by a lane sweep), ~160 instructions per wave-row of 240 pixels.  With 8 pixels per lane a wave-row
 // covers 480 pixels and everything that is per ROW rather than per pixel is paid half as often — row control and
 // address arithmetic, the flag test's tree / ballot / branch, the neighbour-lane taps of both stencils (4 + 4 DPP reads per
 // row either way), the two halo lanes — and the 1-byte output leaves as 8 bytes per lane (480-byte spans = whole
@@ -271,7 +271,7 @@ hipError_t launch_r8(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, in
     const int lanes_out = (octs + nstrips - 1) / nstrips;  // 4K: 480 octets = 8 strips x 60 lanes
     BandPlan plan;
     // Tall bands: this kernel's waves are few and long (4-5 per SIMD), and each band pays 2R + 2 warm-up rows.  Same
-    // box, 256 x 4K frames (tools/pipe8_sweep.sh): k = 5: 24 rows 4.44 TB/s, 48: 4.70, 72: 4.73, 96: 4.82, 144: 4.80,
+    // box, 256 x 4K frames: k = 5: 24 rows 4.44 TB/s, 48: 4.70, 72: 4.73, 96: 4.82, 144: 4.80,
     // 216: 4.70 (pipe_slide.hip: 4.67); k = 3: 16 rows 4.91, 32: 5.14, 48: 5.24, 72: 5.33 (pipe_slide.hip: 4.94).
     // Smaller launches get shorter bands (make_band_plan).
     constexpr int kRowsMin = (R == 1) ? 16 : 24, kRowsMax = (R == 1) ? 72 : 96;

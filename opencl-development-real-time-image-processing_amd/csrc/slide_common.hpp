@@ -68,7 +68,7 @@ inline bool make_band_plan(int h, int nstrips, int nframes, int waves_per_simd, 
     const double resident = 256.0 * 4.0 * waves_per_simd;
     double rows = (double)h * nstrips * nframes / (10.0 * resident);
     int rows_big = (int)(rows < rows_min ? rows_min : (rows > rows_max ? rows_max : rows));
-    // MI355_TUNE_* environment overrides exist for tuning sweeps only (tools/sweep*.sh); read once
+    // MI355_TUNE_* environment overrides exist for tuning sweeps only (tools/rows.py with the tuning build); read once
     static const struct Tune {
         int band_rows = 0, tail_rows = 0;
         double tail_frac = -1.0;

@@ -206,7 +206,7 @@ hipError_t launch_pipeline(hipStream_t stream, const uint8_t* d_in, uint8_t* d_o
     // both Gaussian modes; tables it cannot take (non-separable, asymmetric factor) arrive here with exact = true
     {
         // 8 pixels per lane (pipe_slide8.hip, the same bits) pays on big launches of wide rows at k = 5: same box,
-        // 4K frames, 4 / 8 pixels per lane (tools/pipe8_ab.sh): 256 frames 4.57 / 4.82 TB/s (another box 4.67 / 4.73),
+        // 4K frames, 4 / 8 pixels per lane: 256 frames 4.57 / 4.82 TB/s (another box 4.67 / 4.73),
         // 128 frames 4.53 / 4.71, 64 frames 4.31 / 4.30, 8 frames 4.02 / 3.87, 1 frame 2.26 / 1.77; 640 x 512 x 4096
         // 4.17 / 3.66 (80 octets = 2 strips of 40 lanes); k = 3: 4.84 / 4.91 on one box, 4.93 / 4.82 on another.
         const int octs = w / 8, strips8 = (octs + kSlideLanesOutMax - 1) / kSlideLanesOutMax;

@@ -164,8 +164,8 @@ __global__ __launch_bounds__(kThreads) void selftest_kernel(unsigned long long* 
 }
 
 // Streaming copy, 16 B per lane, non-temporal loads and stores, 4 accesses in flight per lane: the on-box
-// ceiling for "read N bytes + write N bytes" that bench.py reports beside the filter kernels (tools/membench.hip
-// measured this form at 6.2-6.4 TB/s with >= 8k blocks; hipMemcpy D2D reaches only 4.4-4.7).
+// ceiling for "read N bytes + write N bytes" that bench.py reports beside the filter kernels (profiles/r01_membench.txt:
+// this form runs 6.2-6.4 TB/s with >= 8k blocks; hipMemcpy D2D reaches only 4.4-4.7).
 __global__ __launch_bounds__(kThreads) void stream_copy_kernel(const u32x4* __restrict__ in, u32x4* __restrict__ out,
                                                                size_t n)
 {

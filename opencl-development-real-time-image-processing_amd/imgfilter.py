@@ -65,7 +65,7 @@ def load_library(path=None):
     if path is None and _lib is not None:
         return _lib
     other = path is not None
-    # MI355_IMGFILTER_LIB: another build of the same library (A/B timing of kernel changes, tools/ab.sh)
+    # MI355_IMGFILTER_LIB: another build of the same library (A/B timing of kernel changes, tools/abx.py)
     path = path or os.environ.get("MI355_IMGFILTER_LIB", _LIB)
     if not os.path.exists(path):
         raise Mi355Error("load_library", -1, "%s is missing: run __graft_entry__.build()" % path)

@@ -1,5 +1,5 @@
-"""GPU suite (-m gpu): the matrix-core Gaussian (csrc/gauss_mfma_reg.hip, MI355_IMPL_MFMA; its LDS-staged A/B
-partner csrc/gauss_mfma.hip through the tuning build) against the oracle.
+"""GPU suite (-m gpu): the matrix-core Gaussian (csrc/gauss_mfma_reg.hip, MI355_IMPL_MFMA; its band heights through
+the tuning build) against the oracle.
 
 Contract: FAST arithmetic, |d| <= 1 LSB per channel against the CPU path (src/GaussianBlur/GaussianBlur.cpp:234-261)
 on every shape; the fp16 hi + lo splits keep the error of the sums near 1e-4, so the share of bytes that differ at
@@ -148,11 +148,10 @@ print(worst)
 """
 
 
-def test_lds_staged_partner_and_band_heights():
-    """The tuning build keeps two knobs of the matrix-core path reachable: MI355_MFMA_LDS=1 runs the LDS-staged kernel
-    (gauss_mfma.hip, round 2's first version, the A/B partner of tools/mfma_reg_ab.sh), MI355_MFMA_BPB sets the band
-    height of gauss_mfma_reg.hip (1 block per band: every block pays a halo tile; 3: ragged last band).  Each within
-    1 LSB of the oracle on shapes with edges, several bands (2300 rows > 68 blocks), opaque frames with one hole."""
+def test_mfma_band_heights():
+    """The tuning build's MI355_MFMA_BPB sets the band height of gauss_mfma_reg.hip (1 block per band: every block pays
+    a halo tile; 2 and 3: ragged last bands).  Each within 1 LSB of the oracle on shapes with edges, several bands
+    (2300 rows > 68 blocks), opaque frames with one hole."""
     import os
     import subprocess
     import sys
@@ -160,9 +159,7 @@ def test_lds_staged_partner_and_band_heights():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     tune_lib = os.path.join(entry.ROOT, "tools", "lib", "libmi355_imgfilter_tune.so")
     assert os.path.exists(tune_lib), "run __graft_entry__.build()"
-    # MI355_MFMA_DMA=1: gauss_mfma_dma.hip, the register kernel with its input tiles staged by LDS-DMA (global_load_lds_dwordx4)
-    for knobs in ({"MI355_MFMA_LDS": "1"}, {"MI355_MFMA_BPB": "1"}, {"MI355_MFMA_BPB": "3"}, {"MI355_MFMA_DMA": "1"},
-                  {"MI355_MFMA_DMA": "1", "MI355_MFMA_BPB": "2"}):
+    for knobs in ({"MI355_MFMA_BPB": "1"}, {"MI355_MFMA_BPB": "2"}, {"MI355_MFMA_BPB": "3"}):
         env = dict(os.environ, MI355_IMGFILTER_LIB=tune_lib, **knobs)
         out = subprocess.run([sys.executable, "-c", _PARTNER_SCRIPT, root], env=env, capture_output=True, text=True,
                              timeout=300)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/build_variant.sh <name> <sed-expr> <file> [<sed-expr> <file> ...] — builds ab/lib_<name>.so from a patched
-# copy of csrc/ (experiments that should not touch the tree); compare with tools/ab.sh on one box.
+# copy of csrc/ (experiments that should not touch the tree); compare with tools/abx.py on one box.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 PKG=opencl-development-real-time-image-processing_amd

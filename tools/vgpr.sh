@@ -6,7 +6,7 @@ cd $ROOT/opencl-development-real-time-image-processing_amd/csrc
 B=$(basename $F .hip)
 EXTRA=""
 case " gauss_slide gauss_wide gauss_exact sobel_slide pipe_slide pipe_slide8 " in *" $B "*) EXTRA="$EXTRA -fno-slp-vectorize";; esac
-case " gauss_mfma gauss_mfma_reg gauss_mfma_dma gauss_mfma_i8 " in *" $B "*) EXTRA="$EXTRA -mllvm -amdgpu-mfma-vgpr-form";; esac
+case " gauss_mfma_reg " in *" $B "*) EXTRA="$EXTRA -mllvm -amdgpu-mfma-vgpr-form";; esac
 case " pipe_slide pipe_slide8 gauss_exact " in *" $B "*) EXTRA="$EXTRA -mllvm -pragma-unroll-threshold=131072";; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -fvisibility=hidden $EXTRA \
   -Rpass-analysis=kernel-resource-usage -c $B.hip -o /tmp/vgpr_$B.o 2>&1 |
