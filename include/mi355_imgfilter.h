@@ -72,7 +72,9 @@ int mi355_ctx_set_gauss_mode(mi355_ctx* ctx, int mode);
  *          EXACT mode: the exact-by-exception sliding kernel for k in {3,5,7} and width % 4 == 0, the tiled kernel
  *          otherwise.  Pipeline: k in {3,5,7}, w >= 4, h >= 2 sliding (8 pixels per lane for k = 5 launches of
  *          >= 10^9 pixels with width % 8 == 0), tiled otherwise.
- *   TILE — always the LDS-tiled kernels.
+ *          Single-channel filters (MI355_FILTER_*_GRAY8): k in {3,5,7} with a constant k, both Gaussian modes
+ *          exact by exception; the runtime-k kernel otherwise.
+ *   TILE — always the LDS-tiled kernels (for the single-channel filters: runtime k, EXACT pixels by the CPU chain).
  *   VALU — as AUTO but never the matrix cores.  TILE and VALU give identical bits. */
 #define MI355_IMPL_AUTO 0
 #define MI355_IMPL_TILE 1
@@ -175,10 +177,32 @@ int mi355_gauss_weights_image2d(int k, float sigma, float* out_k2);
 #define MI355_FILTER_GAUSS 2    /* RGBA -> RGBA              */
 #define MI355_FILTER_SOBEL 3    /* RGBA -> 1 byte            */
 #define MI355_FILTER_PIPELINE 4 /* RGBA -> 1 byte            */
+/* Single-channel filters: 1 byte per pixel in, 1 byte per pixel out, frames tightly packed (stride = width) — a mono
+ * camera frame, the luma plane of a decoded video frame, a cv::Mat read with cv::IMREAD_GRAYSCALE, a torch (N, H, W)
+ * uint8 tensor, or this library's own GRAY1 output.  Device buffers may have any byte alignment and any width >= 1
+ * (the dword alignment rule of the RGBA filters does not apply).  The host-buffer calls return MI355_ERR_UNSUPPORTED
+ * under MI355_INPUT_BGR: a gray plane is never converted.  mi355_image2d_rgba8 does not take these ids.
+ *   GAUSS_GRAY8     src/GaussianBlur/GaussianBlur.cpp:234-261 on one channel: clamp-to-edge taps, the same table,
+ *                   truncation — the R channel of mi355_gauss_rgba8 of (y, y, y, 255).  EXACT mode is bit-identical
+ *                   to it, FAST mode within 1 LSB (bit-identical too for k in {3, 5, 7} outside MI355_IMPL_TILE).  Any
+ *                   odd k <= MI355_MAX_GAUSS_K; an installed non-separable table is applied tap by tap.
+ *   SOBEL_GRAY8     src/EdgeDetection/EdgeDetection.cpp:219-240 on the given plane itself (the reference reads it with
+ *                   cv::IMREAD_GRAYSCALE, :202): filter2D CV_32F with BORDER_REFLECT_101, magnitude, convertTo CV_8U.
+ *                   No luminance step — unlike MI355_FILTER_SOBEL, whose luminance of (v, v, v) is v - 1 for 65 byte
+ *                   values.
+ *   PIPELINE_GRAY8  SOBEL_GRAY8 of the EXACT-mode GAUSS_GRAY8, bit-identical to that chain in both Gaussian modes.
+ *                   Deliberately NOT MI355_FILTER_PIPELINE on (y, y, y, 255): the input is already a gray plane, so no
+ *                   luminance is re-applied. */
+#define MI355_FILTER_GAUSS_GRAY8 5    /* 1 byte -> 1 byte */
+#define MI355_FILTER_SOBEL_GRAY8 6    /* 1 byte -> 1 byte */
+#define MI355_FILTER_PIPELINE_GRAY8 7 /* 1 byte -> 1 byte */
 int mi355_filter_batched(mi355_ctx* ctx, int filter, const uint8_t* rgba, uint8_t* out, int w, int h,
                          int nframes, int k, float sigma, uint64_t prof_ns[6]);
-/* bytes per output pixel of a filter (4 or 1), or MI355_ERR_BAD_ARG */
+/* bytes per output pixel of a filter (4 or 1), or MI355_ERR_BAD_ARG.  Pure host function. */
 int mi355_filter_out_bpp(int filter);
+/* bytes per input pixel of a filter: 4 for the RGBA filters (ids 0-4), 1 for the *_GRAY8 ids, or MI355_ERR_BAD_ARG.
+ * Pure host function.  Every buffer size of the batched, streamed, pool and group calls is counted in these bytes. */
+int mi355_filter_in_bpp(int filter);
 
 /* Streamed host-buffer form: nframes frames in `rgba` -> `out`, both on the host, moved
  * in chunks of chunk_frames (0 = choose) through three device slots with three stages in flight on three HIP
@@ -196,7 +220,7 @@ int mi355_host_free(mi355_ctx* ctx, void* h_ptr);
 /* ---- device-resident calls -----------------------------------------------------------------
  * d_in / d_out are device pointers on the context's GPU holding nframes tightly packed frames;
  * the call enqueues the kernel(s) on the context's stream and returns without synchronising.
- * [d_in, d_in + 4*w*h*nframes) and the output range must not overlap: the stencil filters (Gaussian, Sobel,
+ * [d_in, d_in + in_bpp*w*h*nframes) (mi355_filter_in_bpp) and the output range must not overlap: the stencil filters (Gaussian, Sobel,
  * pipeline) read neighbouring rows and halo pixels that another wave may already have overwritten, and the
  * grayscale kernels, although pointwise, are compiled with non-aliasing (__restrict__) pointers and non-temporal
  * accesses — so an in-place or overlapping call is rejected with MI355_ERR_BAD_ARG, for every filter, instead of
@@ -246,7 +270,7 @@ int mi355_dev_alloc(mi355_ctx* ctx, size_t nbytes, void** d_ptr);
 /* Frame pools with a placement search.  On MI355X the PHYSICAL placement of a streaming kernel's input and output
  * buffers decides up to 8 % of its rate (the same command reads 5.5 or 6.0 TB/s from one process to the next), and
  * an allocation cannot be steered, only re-drawn.  This call allocates the input pool
- * (nframes x w x h RGBA, filled with 0xFF) and up to `tries` (<= 16) candidate output pools side by side — all
+ * (nframes x w x h pixels of mi355_filter_in_bpp(filter) bytes, filled with 0xFF) and up to `tries` (<= 16) candidate output pools side by side — all
  * alive at once, hence all in different places; fewer if memory runs short — runs a few launches of `filter` on
  * each, keeps the fastest and frees the others.  tries <= 1: plain allocation, no probing.  probe_ms (optional,
  * `tries` floats): average launch time per candidate, -1 for candidates that were not allocated.  Synchronises

@@ -6,10 +6,15 @@ lib/libmi355_imgfilter.so (csrc/); this package is only the ctypes door to it.
 """
 from .imgfilter import (  # noqa: F401
     FILTER_GAUSS,
+    FILTER_GAUSS_GRAY8,
     FILTER_GRAY,
     FILTER_GRAY1,
     FILTER_PIPELINE,
+    FILTER_PIPELINE_GRAY8,
     FILTER_SOBEL,
+    FILTER_SOBEL_GRAY8,
+    IN_BPP,
+    OUT_BPP,
     GAUSS_EXACT,
     GAUSS_FAST,
     IMPL_AUTO,

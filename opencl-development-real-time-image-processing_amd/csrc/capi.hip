@@ -290,7 +290,14 @@ int ensure(mi355_ctx* ctx, void** p, size_t* cap, size_t need)
     return MI355_OK;
 }
 
-bool filter_needs_gauss(int f) { return f == MI355_FILTER_GAUSS || f == MI355_FILTER_PIPELINE; }
+bool filter_needs_gauss(int f)
+{
+    return f == MI355_FILTER_GAUSS || f == MI355_FILTER_PIPELINE || f == MI355_FILTER_GAUSS_GRAY8 ||
+           f == MI355_FILTER_PIPELINE_GRAY8;
+}
+
+// the single-channel filters take 1-byte pixels: any byte alignment, and no BGR ingest
+bool filter_is_gray8(int f) { return mi355_filter_in_bpp(f) == 1; }
 
 int check_frames(const void* in, const void* out, int w, int h, int nframes)
 {
@@ -311,7 +318,10 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
     int rc = check_frames(d_in, d_out, w, h, nframes);
     if (rc != MI355_OK)
         return rc;
-    if (reinterpret_cast<uintptr_t>(d_in) & 3u)
+    const int in_bpp = mi355_filter_in_bpp(filter);
+    if (in_bpp < 0)
+        return MI355_ERR_BAD_ARG;
+    if (in_bpp == 4 && (reinterpret_cast<uintptr_t>(d_in) & 3u))
         return MI355_ERR_BAD_ARG;  // RGBA pixels are accessed as dwords
     const bool rgba_out = (filter == MI355_FILTER_GRAY || filter == MI355_FILTER_GAUSS);
     if (rgba_out && (reinterpret_cast<uintptr_t>(d_out) & 3u))
@@ -325,7 +335,7 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
         if (bpp < 0)
             return MI355_ERR_BAD_ARG;
         const size_t npx = (size_t)w * h * nframes;
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_in), a1 = a0 + npx * 4;
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_in), a1 = a0 + npx * (size_t)in_bpp;
         const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + npx * (size_t)bpp;
         if (a0 < b1 && b0 < a1)
             return MI355_ERR_BAD_ARG;
@@ -368,6 +378,15 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
     case MI355_FILTER_PIPELINE:
         e = launch_pipeline(ctx->stream, in, out, w, h, nframes, *coef, exact, ctx->impl);
         break;
+    case MI355_FILTER_GAUSS_GRAY8:
+        e = launch_gauss_gray8(ctx->stream, in, out, w, h, nframes, *coef, exact, ctx->impl);
+        break;
+    case MI355_FILTER_SOBEL_GRAY8:
+        e = launch_sobel_gray8(ctx->stream, in, out, w, h, nframes);
+        break;
+    case MI355_FILTER_PIPELINE_GRAY8:
+        e = launch_pipeline_gray8(ctx->stream, in, out, w, h, nframes, *coef, ctx->impl);
+        break;
     default:
         return MI355_ERR_BAD_ARG;
     }
@@ -407,10 +426,12 @@ int run_host(mi355_ctx* ctx, int filter, const uint8_t* in, uint8_t* out, int w,
         return rc;
     if (filter_needs_gauss(filter) && (!valid_k(k) || !valid_sigma(sigma)))
         return MI355_ERR_BAD_ARG;
+    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
+    if (bgr && filter_is_gray8(filter))
+        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t npx = (size_t)w * h * nframes;
-    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    const size_t in_bytes = npx * 4, out_bytes = npx * (size_t)bpp;
+    const size_t in_bytes = npx * (size_t)mi355_filter_in_bpp(filter), out_bytes = npx * (size_t)bpp;
     rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, in_bytes);
     if (rc != MI355_OK)
         return rc;
@@ -731,7 +752,25 @@ MI355_API int mi355_filter_out_bpp(int filter)
     case MI355_FILTER_GAUSS: return 4;
     case MI355_FILTER_GRAY1:
     case MI355_FILTER_SOBEL:
-    case MI355_FILTER_PIPELINE: return 1;
+    case MI355_FILTER_PIPELINE:
+    case MI355_FILTER_GAUSS_GRAY8:
+    case MI355_FILTER_SOBEL_GRAY8:
+    case MI355_FILTER_PIPELINE_GRAY8: return 1;
+    default: return MI355_ERR_BAD_ARG;
+    }
+}
+
+MI355_API int mi355_filter_in_bpp(int filter)
+{
+    switch (filter) {
+    case MI355_FILTER_GRAY:
+    case MI355_FILTER_GRAY1:
+    case MI355_FILTER_GAUSS:
+    case MI355_FILTER_SOBEL:
+    case MI355_FILTER_PIPELINE: return 4;
+    case MI355_FILTER_GAUSS_GRAY8:
+    case MI355_FILTER_SOBEL_GRAY8:
+    case MI355_FILTER_PIPELINE_GRAY8: return 1;
     default: return MI355_ERR_BAD_ARG;
     }
 }
@@ -815,11 +854,15 @@ MI355_API int mi355_filter_stream(mi355_ctx* ctx, int filter, const uint8_t* rgb
         return rc;
     if (filter_needs_gauss(filter) && (!valid_k(k) || !valid_sigma(sigma)))
         return MI355_ERR_BAD_ARG;
+    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
+    if (bgr && filter_is_gray8(filter))
+        return MI355_ERR_UNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t fpx = (size_t)w * h;
+    const size_t dev_in_bpp = (size_t)mi355_filter_in_bpp(filter);  // what the kernel reads: 4 (RGBA) or 1 (gray8)
     if (chunk_frames == 0) {
         // ~64 MB of input per chunk: long enough DMA transfers to run at link rate, short enough to overlap
-        chunk_frames = (int)((64u << 20) / (fpx * 4));
+        chunk_frames = (int)((64u << 20) / (fpx * dev_in_bpp));
         if (chunk_frames < 1)
             chunk_frames = 1;
     }
@@ -835,9 +878,8 @@ MI355_API int mi355_filter_stream(mi355_ctx* ctx, int filter, const uint8_t* rgb
             HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_d2h[i], hipEventDisableTiming));
         }
     }
-    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    const size_t in_bpp = bgr ? 3 : 4;
-    const size_t in_chunk = fpx * 4 * chunk_frames, out_chunk = fpx * (size_t)bpp * chunk_frames;
+    const size_t in_bpp = bgr ? 3 : dev_in_bpp;  // what crosses PCIe
+    const size_t in_chunk = fpx * dev_in_bpp * chunk_frames, out_chunk = fpx * (size_t)bpp * chunk_frames;
     if (bgr && ctx->slot_raw_cap < fpx * 3 * chunk_frames) {
         HIP_TRY(ctx, hipDeviceSynchronize());
         for (int i = 0; i < NS; i++) {
@@ -1041,7 +1083,8 @@ MI355_API int mi355_pool_alloc(mi355_ctx* ctx, int filter, int w, int h, int nfr
     for (int i = 0; probe_ms && i < tries; i++)
         probe_ms[i] = -1.0f;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)w * h * nframes, in_bytes = npx * 4, out_bytes = npx * (size_t)bpp;
+    const size_t npx = (size_t)w * h * nframes, in_bytes = npx * (size_t)mi355_filter_in_bpp(filter),
+                 out_bytes = npx * (size_t)bpp;
     void* in = nullptr;
     if (hipMalloc(&in, in_bytes) != hipSuccess)
         return MI355_ERR_NOMEM;

@@ -128,11 +128,10 @@ inline double half_ulp(double x)
 
 // |S - S_cpu| <= delta for every window of bytes, where S is the kernel's separable pair-form evaluation with w1 and
 // S_cpu the CPU path's k*k-term float sum with w2.  Everything is non-negative (checked by the caller), so partial
-// sums never exceed the final ones.
-template <int K>
-double delta_bound(const float* w1, const float* w2)
+// sums never exceed the final ones.  Runtime-k form (gray8.hip); delta_bound<K> below is the same function.
+inline double delta_bound_k(int K, const float* w1, const float* w2)
 {
-    constexpr int R = K / 2;
+    const int R = K / 2;
     double sum2 = 0.0, max2 = 0.0, sum1 = 0.0, mismatch = 0.0;
     for (int i = 0; i < K * K; i++) {
         sum2 += (double)w2[i];
@@ -179,6 +178,12 @@ double delta_bound(const float* w1, const float* w2)
     (void)sum2;
     // every term above is a worst case already; the margin only covers the double arithmetic of this function
     return 1.02 * (e_cpu + e_h + 255.0 * mismatch) + 1e-7;
+}
+
+template <int K>
+double delta_bound(const float* w1, const float* w2)
+{
+    return delta_bound_k(K, w1, w2);
 }
 
 

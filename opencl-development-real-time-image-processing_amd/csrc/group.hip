@@ -62,7 +62,11 @@ struct Member {
     }
 };
 
-bool filter_needs_gauss(int f) { return f == MI355_FILTER_GAUSS || f == MI355_FILTER_PIPELINE; }
+bool filter_needs_gauss(int f)
+{
+    return f == MI355_FILTER_GAUSS || f == MI355_FILTER_PIPELINE || f == MI355_FILTER_GAUSS_GRAY8 ||
+           f == MI355_FILTER_PIPELINE_GRAY8;
+}
 
 uint32_t fbits(float f)
 {
@@ -265,13 +269,15 @@ MI355_API int mi355_group_filter_batched(mi355_group* g, int filter, const uint8
     const int bpp = mi355_filter_out_bpp(filter);
     if (bpp < 0)
         return MI355_ERR_BAD_ARG;
+    if (g->input_format == MI355_INPUT_BGR && mi355_filter_in_bpp(filter) == 1)
+        return MI355_ERR_UNSUPPORTED;  // gray planes have no BGR form
     std::lock_guard<std::mutex> lk(g->call);
     if (filter_needs_gauss(filter)) {
         const int rc = g->ensure_table(k, sigma);
         if (rc != MI355_OK)
             return rc;
     }
-    const size_t fpx = (size_t)w * h, in_bpp = g->input_format == MI355_INPUT_BGR ? 3 : 4;
+    const size_t fpx = (size_t)w * h, in_bpp = g->input_format == MI355_INPUT_BGR ? 3 : (size_t)mi355_filter_in_bpp(filter);
     const int n = (int)g->members.size();
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = g->all([&](Member& mb, int i) {

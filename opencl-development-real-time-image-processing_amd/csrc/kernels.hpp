@@ -92,6 +92,15 @@ hipError_t launch_pipe_slide8(hipStream_t stream, const uint8_t* d_in, uint8_t* 
 hipError_t launch_pipe_slide(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                              const GaussCoef& coef);
 
+// single-channel (1 byte per pixel) filters (gray8.hip): any width, any byte alignment.  impl 1 (TILE) forces the
+// runtime-k kernels and the CPU chain for every EXACT pixel; otherwise k in {3, 5, 7} runs with a constant k and both
+// Gaussian modes exact by exception.  The pipeline's Gaussian is the EXACT one in both modes.
+hipError_t launch_gauss_gray8(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
+                              const GaussCoef& coef, bool exact, int impl);
+hipError_t launch_sobel_gray8(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes);
+hipError_t launch_pipeline_gray8(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
+                                 const GaussCoef& coef, int impl);
+
 // image2d_t-mode semantics of the reference (image2d.hip): filter 0 gray / 2 gauss / 3 sobel
 hipError_t launch_image2d(hipStream_t stream, int filter, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                           int k, const float* d_table);

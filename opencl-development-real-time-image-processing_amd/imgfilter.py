@@ -20,10 +20,15 @@ _LIB = os.path.join(_HERE, "lib", "libmi355_imgfilter.so")
 _HEADER = os.path.join(_ROOT, "include", "mi355_imgfilter.h")
 
 FILTER_GRAY, FILTER_GRAY1, FILTER_GAUSS, FILTER_SOBEL, FILTER_PIPELINE = 0, 1, 2, 3, 4
+# single-channel filters: 1 byte per pixel in and out (include/mi355_imgfilter.h, MI355_FILTER_*_GRAY8)
+FILTER_GAUSS_GRAY8, FILTER_SOBEL_GRAY8, FILTER_PIPELINE_GRAY8 = 5, 6, 7
 GAUSS_FAST, GAUSS_EXACT = 0, 1
 INPUT_RGBA, INPUT_BGR = 0, 1
 IMPL_AUTO, IMPL_TILE, IMPL_MFMA, IMPL_VALU = 0, 1, 2, 3
-OUT_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 1, FILTER_GAUSS: 4, FILTER_SOBEL: 1, FILTER_PIPELINE: 1}
+OUT_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 1, FILTER_GAUSS: 4, FILTER_SOBEL: 1, FILTER_PIPELINE: 1,
+           FILTER_GAUSS_GRAY8: 1, FILTER_SOBEL_GRAY8: 1, FILTER_PIPELINE_GRAY8: 1}
+IN_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 4, FILTER_GAUSS: 4, FILTER_SOBEL: 4, FILTER_PIPELINE: 4,
+          FILTER_GAUSS_GRAY8: 1, FILTER_SOBEL_GRAY8: 1, FILTER_PIPELINE_GRAY8: 1}
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _f32p = ctypes.POINTER(ctypes.c_float)
@@ -93,6 +98,7 @@ def load_library(path=None):
         "mi355_pipeline_rgba8": [_vp, _u8p, _u8p, _ci, _ci, _ci, ctypes.c_float, _u64p],
         "mi355_filter_batched": [_vp, _ci, _u8p, _u8p, _ci, _ci, _ci, _ci, ctypes.c_float, _u64p],
         "mi355_filter_out_bpp": [_ci],
+        "mi355_filter_in_bpp": [_ci],
         "mi355_filter_stream": [_vp, _ci, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, ctypes.c_float,
                                 ctypes.POINTER(ctypes.c_double)],
         "mi355_host_alloc": [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)],
@@ -172,6 +178,18 @@ def gauss_weights_image2d(k, sigma):
     rc = load_library().mi355_gauss_weights_image2d(int(k), float(sigma), out.ctypes.data_as(_f32p))
     _check("mi355_gauss_weights_image2d", rc)
     return out
+
+
+def _batch_shape(filt, frames, in_ch):
+    """(n, h, w) of a host batch: (n, h, w, in_ch) frames, or (n, h, w) planes for the single-channel filters (under
+    a BGR input format those reach the library, which refuses them with MI355_ERR_UNSUPPORTED)."""
+    if IN_BPP.get(filt) == 1:
+        assert frames.ndim == 3, "single-channel filters take (n, h, w) uint8 planes"
+        return frames.shape
+    assert frames.ndim == 4
+    n, h, w, c = frames.shape
+    assert c == in_ch
+    return n, h, w
 
 
 def device_count():
@@ -279,6 +297,31 @@ class Context:
     def pipeline(self, rgba, k, sigma, profile=False):
         return self._host(FILTER_PIPELINE, rgba, k, sigma, profile=profile)
 
+    # -- single-channel frames: (h, w) or (n, h, w) uint8 in, the same shape out --------------------
+    def _host_gray8(self, filt, y, k=0, sigma=0.0):
+        y = np.ascontiguousarray(y, np.uint8)
+        if y.ndim not in (2, 3):
+            raise Mi355Error("filter", -1, "expected (h, w) or (n, h, w) uint8")
+        frames = y[None] if y.ndim == 2 else y
+        n, h, w = frames.shape
+        out = np.empty((n, h, w), np.uint8)
+        rc = self._lib.mi355_filter_batched(self._h, filt, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p),
+                                            w, h, n, int(k), float(sigma), None)
+        _check("mi355_filter_batched", rc, self._h)
+        return out[0] if y.ndim == 2 else out
+
+    def gauss_gray8(self, y, k, sigma):
+        """GaussianBlur.cpp:234-261 on one channel (MI355_FILTER_GAUSS_GRAY8)."""
+        return self._host_gray8(FILTER_GAUSS_GRAY8, y, k, sigma)
+
+    def sobel_gray8(self, y):
+        """EdgeDetection.cpp:219-240 on the given plane, no luminance step (MI355_FILTER_SOBEL_GRAY8)."""
+        return self._host_gray8(FILTER_SOBEL_GRAY8, y)
+
+    def pipeline_gray8(self, y, k, sigma):
+        """sobel_gray8(EXACT gauss_gray8(y)) in either Gaussian mode (MI355_FILTER_PIPELINE_GRAY8)."""
+        return self._host_gray8(FILTER_PIPELINE_GRAY8, y, k, sigma)
+
     def image2d(self, filt, rgba, k=0, sigma=0.0):
         """mi355_image2d_rgba8: the reference's image2d_t-mode semantics.  Returns (out, six timestamps)."""
         rgba = np.ascontiguousarray(rgba, np.uint8)
@@ -307,10 +350,10 @@ class Context:
             _check("mi355_host_free", self._lib.mi355_host_free(self._h, _vp(p)), self._h)
 
     def stream(self, filt, frames, out=None, k=0, sigma=0.0, chunk_frames=0):
-        """mi355_filter_stream: overlapped H2D / kernel / D2H over a host batch.  Returns (out, elapsed_ms)."""
-        assert frames.flags["C_CONTIGUOUS"] and frames.dtype == np.uint8 and frames.ndim == 4
-        n, h, w, c = frames.shape
-        assert c == getattr(self, "_in_ch", 4)
+        """mi355_filter_stream: overlapped H2D / kernel / D2H over a host batch.  Returns (out, elapsed_ms).
+        frames: (n, h, w, c), or (n, h, w) for the single-channel filters."""
+        assert frames.flags["C_CONTIGUOUS"] and frames.dtype == np.uint8
+        n, h, w = _batch_shape(filt, frames, getattr(self, "_in_ch", 4))
         bpp = OUT_BPP[filt]
         if out is None:
             out = np.empty((n, h, w, 4) if bpp == 4 else (n, h, w), np.uint8)
@@ -466,10 +509,10 @@ class Group:
         _check("mi355_group_set_gauss_weights", rc)
 
     def filter_batched(self, filt, frames, k=0, sigma=0.0, out=None):
-        """Host frames (n, h, w, c) -> (out, elapsed_ms): every member streams its contiguous range."""
+        """Host frames (n, h, w, c), or (n, h, w) for the single-channel filters -> (out, elapsed_ms): every member
+        streams its contiguous range."""
         frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, c = frames.shape
-        assert c == getattr(self, "_in_ch", 4)
+        n, h, w = _batch_shape(filt, frames, getattr(self, "_in_ch", 4))
         bpp = OUT_BPP[filt]
         if out is None:
             out = np.empty((n, h, w, 4) if bpp == 4 else (n, h, w), np.uint8)
