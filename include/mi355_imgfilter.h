@@ -196,11 +196,26 @@ int mi355_gauss_weights_image2d(int k, float sigma, float* out_k2);
 #define MI355_FILTER_GAUSS_GRAY8 5    /* 1 byte -> 1 byte */
 #define MI355_FILTER_SOBEL_GRAY8 6    /* 1 byte -> 1 byte */
 #define MI355_FILTER_PIPELINE_GRAY8 7 /* 1 byte -> 1 byte */
+/* Median filter, cv::medianBlur(src, dst, k): every channel on its own (alpha included), a k x k window with clamp-to-edge
+ * (BORDER_REPLICATE) borders — the clamp of the CPU Gaussian — and the middle one of the k*k values.  The output is an
+ * input byte, so every implementation is bit-identical; there is no rounding contract.  Frames are independent (a
+ * window never reads a neighbouring frame).  k must be 3, 5 or 7 (MI355_MAX_MEDIAN_K), anything else is
+ * MI355_ERR_BAD_ARG; sigma is ignored and no weight table is made; the Gaussian mode does not apply.  Kernels: AUTO,
+ * VALU and MFMA all choose the packed 16-bit compare networks for k in {3, 5} and the LDS counting kernel for k = 7;
+ * MI355_IMPL_TILE forces the counting kernel for every k.
+ *   MEDIAN        RGBA -> RGBA, dword-aligned device buffers; takes BGR host frames (expanded to RGBA, A = 255) under
+ *                 MI355_INPUT_BGR.
+ *   MEDIAN_GRAY8  1 byte -> 1 byte with the single-channel rules above (any byte alignment, UNSUPPORTED under BGR).
+ * The ids start at 16, leaving 8-15 unassigned: id 8 has always been rejected, and callers (this library's own tests
+ * among them) rely on the first ids after the gray8 block staying invalid. */
+#define MI355_MAX_MEDIAN_K 7
+#define MI355_FILTER_MEDIAN 16       /* RGBA -> RGBA     */
+#define MI355_FILTER_MEDIAN_GRAY8 17 /* 1 byte -> 1 byte */
 int mi355_filter_batched(mi355_ctx* ctx, int filter, const uint8_t* rgba, uint8_t* out, int w, int h,
                          int nframes, int k, float sigma, uint64_t prof_ns[6]);
 /* bytes per output pixel of a filter (4 or 1), or MI355_ERR_BAD_ARG.  Pure host function. */
 int mi355_filter_out_bpp(int filter);
-/* bytes per input pixel of a filter: 4 for the RGBA filters (ids 0-4), 1 for the *_GRAY8 ids, or MI355_ERR_BAD_ARG.
+/* bytes per input pixel of a filter: 4 for the RGBA filters (ids 0-4, 16), 1 for the *_GRAY8 ids, or MI355_ERR_BAD_ARG.
  * Pure host function.  Every buffer size of the batched, streamed, pool and group calls is counted in these bytes. */
 int mi355_filter_in_bpp(int filter);
 

@@ -9,6 +9,8 @@ from .imgfilter import (  # noqa: F401
     FILTER_GAUSS_GRAY8,
     FILTER_GRAY,
     FILTER_GRAY1,
+    FILTER_MEDIAN,
+    FILTER_MEDIAN_GRAY8,
     FILTER_PIPELINE,
     FILTER_PIPELINE_GRAY8,
     FILTER_SOBEL,
@@ -23,6 +25,7 @@ from .imgfilter import (  # noqa: F401
     INPUT_RGBA,
     IMPL_TILE,
     IMPL_VALU,
+    MAX_MEDIAN_K,
     Context,
     Group,
     Mi355Error,

@@ -296,6 +296,21 @@ bool filter_needs_gauss(int f)
            f == MI355_FILTER_PIPELINE_GRAY8;
 }
 
+bool filter_is_median(int f) { return f == MI355_FILTER_MEDIAN || f == MI355_FILTER_MEDIAN_GRAY8; }
+
+bool valid_median_k(int k) { return k >= 3 && k <= MI355_MAX_MEDIAN_K && (k & 1) == 1; }
+
+// the (k, sigma) of a call are acceptable for this filter: Gaussian filters take an odd k <= MI355_MAX_GAUSS_K and a
+// valid sigma, the median an odd 3 <= k <= MI355_MAX_MEDIAN_K (sigma ignored), the others ignore both
+bool valid_filter_k(int f, int k, float sigma)
+{
+    if (filter_needs_gauss(f))
+        return valid_k(k) && valid_sigma(sigma);
+    if (filter_is_median(f))
+        return valid_median_k(k);
+    return true;
+}
+
 // the single-channel filters take 1-byte pixels: any byte alignment, and no BGR ingest
 bool filter_is_gray8(int f) { return mi355_filter_in_bpp(f) == 1; }
 
@@ -323,7 +338,7 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
         return MI355_ERR_BAD_ARG;
     if (in_bpp == 4 && (reinterpret_cast<uintptr_t>(d_in) & 3u))
         return MI355_ERR_BAD_ARG;  // RGBA pixels are accessed as dwords
-    const bool rgba_out = (filter == MI355_FILTER_GRAY || filter == MI355_FILTER_GAUSS);
+    const bool rgba_out = (filter == MI355_FILTER_GRAY || filter == MI355_FILTER_GAUSS || filter == MI355_FILTER_MEDIAN);
     if (rgba_out && (reinterpret_cast<uintptr_t>(d_out) & 3u))
         return MI355_ERR_BAD_ARG;
     {
@@ -340,6 +355,8 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
         if (a0 < b1 && b0 < a1)
             return MI355_ERR_BAD_ARG;
     }
+    if (filter_is_median(filter) && !valid_median_k(k))
+        return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const GaussCoef* coef = nullptr;
     if (filter_needs_gauss(filter)) {
@@ -387,6 +404,10 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
     case MI355_FILTER_PIPELINE_GRAY8:
         e = launch_pipeline_gray8(ctx->stream, in, out, w, h, nframes, *coef, ctx->impl);
         break;
+    case MI355_FILTER_MEDIAN:
+    case MI355_FILTER_MEDIAN_GRAY8:
+        e = launch_median(ctx->stream, in, out, w, h, nframes, k, filter == MI355_FILTER_MEDIAN_GRAY8, ctx->impl);
+        break;
     default:
         return MI355_ERR_BAD_ARG;
     }
@@ -424,7 +445,7 @@ int run_host(mi355_ctx* ctx, int filter, const uint8_t* in, uint8_t* out, int w,
     int rc = check_frames(in, out, w, h, nframes);
     if (rc != MI355_OK)
         return rc;
-    if (filter_needs_gauss(filter) && (!valid_k(k) || !valid_sigma(sigma)))
+    if (!valid_filter_k(filter, k, sigma))
         return MI355_ERR_BAD_ARG;
     const bool bgr = ctx->input_format == MI355_INPUT_BGR;
     if (bgr && filter_is_gray8(filter))
@@ -749,13 +770,15 @@ MI355_API int mi355_filter_out_bpp(int filter)
 {
     switch (filter) {
     case MI355_FILTER_GRAY:
-    case MI355_FILTER_GAUSS: return 4;
+    case MI355_FILTER_GAUSS:
+    case MI355_FILTER_MEDIAN: return 4;
     case MI355_FILTER_GRAY1:
     case MI355_FILTER_SOBEL:
     case MI355_FILTER_PIPELINE:
     case MI355_FILTER_GAUSS_GRAY8:
     case MI355_FILTER_SOBEL_GRAY8:
-    case MI355_FILTER_PIPELINE_GRAY8: return 1;
+    case MI355_FILTER_PIPELINE_GRAY8:
+    case MI355_FILTER_MEDIAN_GRAY8: return 1;
     default: return MI355_ERR_BAD_ARG;
     }
 }
@@ -767,10 +790,12 @@ MI355_API int mi355_filter_in_bpp(int filter)
     case MI355_FILTER_GRAY1:
     case MI355_FILTER_GAUSS:
     case MI355_FILTER_SOBEL:
-    case MI355_FILTER_PIPELINE: return 4;
+    case MI355_FILTER_PIPELINE:
+    case MI355_FILTER_MEDIAN: return 4;
     case MI355_FILTER_GAUSS_GRAY8:
     case MI355_FILTER_SOBEL_GRAY8:
-    case MI355_FILTER_PIPELINE_GRAY8: return 1;
+    case MI355_FILTER_PIPELINE_GRAY8:
+    case MI355_FILTER_MEDIAN_GRAY8: return 1;
     default: return MI355_ERR_BAD_ARG;
     }
 }
@@ -852,7 +877,7 @@ MI355_API int mi355_filter_stream(mi355_ctx* ctx, int filter, const uint8_t* rgb
     int rc = check_frames(rgba, out, w, h, nframes);
     if (rc != MI355_OK)
         return rc;
-    if (filter_needs_gauss(filter) && (!valid_k(k) || !valid_sigma(sigma)))
+    if (!valid_filter_k(filter, k, sigma))
         return MI355_ERR_BAD_ARG;
     const bool bgr = ctx->input_format == MI355_INPUT_BGR;
     if (bgr && filter_is_gray8(filter))
@@ -1077,7 +1102,7 @@ MI355_API int mi355_pool_alloc(mi355_ctx* ctx, int filter, int w, int h, int nfr
     const int bpp = mi355_filter_out_bpp(filter);
     if (bpp < 0 || w <= 0 || h <= 0 || nframes <= 0 || (double)w * h * nframes > 6.0e10)
         return MI355_ERR_BAD_ARG;
-    if (filter_needs_gauss(filter) && (!valid_k(k) || !valid_sigma(sigma)))
+    if (!valid_filter_k(filter, k, sigma))
         return MI355_ERR_BAD_ARG;
     constexpr int kMaxCand = 16;
     for (int i = 0; probe_ms && i < tries; i++)

@@ -101,6 +101,12 @@ hipError_t launch_sobel_gray8(hipStream_t stream, const uint8_t* d_in, uint8_t* 
 hipError_t launch_pipeline_gray8(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                                  const GaussCoef& coef, int impl);
 
+// median filter (median.hip), cv::medianBlur semantics, odd k in 3..MI355_MAX_MEDIAN_K; gray8 = 1 byte per pixel (any
+// byte alignment), else RGBA (dword-aligned).  impl 1 (TILE) forces the LDS counting kernel, which AUTO also takes for
+// k = 7; k = 3 and 5 otherwise run the packed-u16 compare networks.
+hipError_t launch_median(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k,
+                         bool gray8, int impl);
+
 // image2d_t-mode semantics of the reference (image2d.hip): filter 0 gray / 2 gauss / 3 sobel
 hipError_t launch_image2d(hipStream_t stream, int filter, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                           int k, const float* d_table);

@@ -22,6 +22,9 @@ _HEADER = os.path.join(_ROOT, "include", "mi355_imgfilter.h")
 FILTER_GRAY, FILTER_GRAY1, FILTER_GAUSS, FILTER_SOBEL, FILTER_PIPELINE = 0, 1, 2, 3, 4
 # single-channel filters: 1 byte per pixel in and out (include/mi355_imgfilter.h, MI355_FILTER_*_GRAY8)
 FILTER_GAUSS_GRAY8, FILTER_SOBEL_GRAY8, FILTER_PIPELINE_GRAY8 = 5, 6, 7
+# median filter (MI355_FILTER_MEDIAN*): ids 16 and 17, k in {3, 5, 7}, sigma ignored
+FILTER_MEDIAN, FILTER_MEDIAN_GRAY8 = 16, 17
+MAX_MEDIAN_K = 7
 GAUSS_FAST, GAUSS_EXACT = 0, 1
 INPUT_RGBA, INPUT_BGR = 0, 1
 IMPL_AUTO, IMPL_TILE, IMPL_MFMA, IMPL_VALU = 0, 1, 2, 3
@@ -29,6 +32,18 @@ OUT_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 1, FILTER_GAUSS: 4, FILTER_SOBEL: 1, FI
            FILTER_GAUSS_GRAY8: 1, FILTER_SOBEL_GRAY8: 1, FILTER_PIPELINE_GRAY8: 1}
 IN_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 4, FILTER_GAUSS: 4, FILTER_SOBEL: 4, FILTER_PIPELINE: 4,
           FILTER_GAUSS_GRAY8: 1, FILTER_SOBEL_GRAY8: 1, FILTER_PIPELINE_GRAY8: 1}
+# ids outside IN_BPP / OUT_BPP (which list the filters 0-7); every lookup goes through _in_bpp / _out_bpp
+_MORE_BPP = {FILTER_MEDIAN: (4, 4), FILTER_MEDIAN_GRAY8: (1, 1)}
+
+
+def _in_bpp(filt):
+    """Bytes per input pixel of any filter id (None for an unknown id, which the library then rejects)."""
+    return IN_BPP[filt] if filt in IN_BPP else _MORE_BPP.get(filt, (None, None))[0]
+
+
+def _out_bpp(filt):
+    return OUT_BPP[filt] if filt in OUT_BPP else _MORE_BPP[filt][1]
+
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _f32p = ctypes.POINTER(ctypes.c_float)
@@ -183,7 +198,7 @@ def gauss_weights_image2d(k, sigma):
 def _batch_shape(filt, frames, in_ch):
     """(n, h, w) of a host batch: (n, h, w, in_ch) frames, or (n, h, w) planes for the single-channel filters (under
     a BGR input format those reach the library, which refuses them with MI355_ERR_UNSUPPORTED)."""
-    if IN_BPP.get(filt) == 1:
+    if _in_bpp(filt) == 1:
         assert frames.ndim == 3, "single-channel filters take (n, h, w) uint8 planes"
         return frames.shape
     assert frames.ndim == 4
@@ -269,7 +284,7 @@ class Context:
         n, h, w, c = frames.shape
         if c != getattr(self, "_in_ch", 4):
             raise Mi355Error("filter", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
-        bpp = OUT_BPP[filt]
+        bpp = _out_bpp(filt)
         out = np.empty((n, h, w, 4) if bpp == 4 else (n, h, w), np.uint8)
         prof = (ctypes.c_uint64 * 6)()
         rc = self._lib.mi355_filter_batched(self._h, filt, frames.ctypes.data_as(_u8p),
@@ -322,6 +337,14 @@ class Context:
         """sobel_gray8(EXACT gauss_gray8(y)) in either Gaussian mode (MI355_FILTER_PIPELINE_GRAY8)."""
         return self._host_gray8(FILTER_PIPELINE_GRAY8, y, k, sigma)
 
+    def median(self, rgba, k, profile=False):
+        """cv::medianBlur on every channel of (h, w, 4) / (n, h, w, 4) frames (MI355_FILTER_MEDIAN); k in {3, 5, 7}."""
+        return self._host(FILTER_MEDIAN, rgba, k, 0.0, profile=profile)
+
+    def median_gray8(self, y, k):
+        """cv::medianBlur of (h, w) / (n, h, w) single-channel frames (MI355_FILTER_MEDIAN_GRAY8)."""
+        return self._host_gray8(FILTER_MEDIAN_GRAY8, y, k)
+
     def image2d(self, filt, rgba, k=0, sigma=0.0):
         """mi355_image2d_rgba8: the reference's image2d_t-mode semantics.  Returns (out, six timestamps)."""
         rgba = np.ascontiguousarray(rgba, np.uint8)
@@ -354,7 +377,7 @@ class Context:
         frames: (n, h, w, c), or (n, h, w) for the single-channel filters."""
         assert frames.flags["C_CONTIGUOUS"] and frames.dtype == np.uint8
         n, h, w = _batch_shape(filt, frames, getattr(self, "_in_ch", 4))
-        bpp = OUT_BPP[filt]
+        bpp = _out_bpp(filt)
         if out is None:
             out = np.empty((n, h, w, 4) if bpp == 4 else (n, h, w), np.uint8)
         ms = ctypes.c_double(0)
@@ -513,7 +536,7 @@ class Group:
         streams its contiguous range."""
         frames = np.ascontiguousarray(frames, np.uint8)
         n, h, w = _batch_shape(filt, frames, getattr(self, "_in_ch", 4))
-        bpp = OUT_BPP[filt]
+        bpp = _out_bpp(filt)
         if out is None:
             out = np.empty((n, h, w, 4) if bpp == 4 else (n, h, w), np.uint8)
         ms = ctypes.c_double(0)
