@@ -211,11 +211,40 @@ int mi355_gauss_weights_image2d(int k, float sigma, float* out_k2);
 #define MI355_MAX_MEDIAN_K 7
 #define MI355_FILTER_MEDIAN 16       /* RGBA -> RGBA     */
 #define MI355_FILTER_MEDIAN_GRAY8 17 /* 1 byte -> 1 byte */
+/* Rectangular grey-level morphology with a k x k MORPH_RECT element anchored at the centre:
+ *   ERODE  = cv::erode(src, dst, rect)             min over the window
+ *   DILATE = cv::dilate(src, dst, rect)            max over the window
+ *   OPEN   = cv::morphologyEx(MORPH_OPEN, rect)   = DILATE(ERODE(x)), the same k
+ *   CLOSE  = cv::morphologyEx(MORPH_CLOSE, rect)  = ERODE(DILATE(x)), the same k
+ * Every channel is filtered on its own (alpha included).  Borders clamp to the edge (BORDER_REPLICATE); for a
+ * rectangle and a min or a max this is the same as OpenCV's default border for erode and dilate, which leaves the
+ * outside out of the window (the clipped window), because a clamped window holds only values of the clipped one.
+ * OPEN / CLOSE treat the intermediate frame as a full frame with its own clamp-to-edge border: outside the frame it is
+ * the intermediate at the clamped position, not the first stage extended past the edge.  Frames are independent.  The
+ * output is an input byte, so there is no rounding contract.  k must be odd with 3 <= k <= MI355_MAX_MORPH_K, anything
+ * else is MI355_ERR_BAD_ARG; sigma is ignored and no table is made; the Gaussian mode does not apply.  OPEN / CLOSE run
+ * as one launch with no intermediate frame in device memory.  One kernel serves every id and k: the impl knob
+ * (MI355_IMPL_*) does not affect these ids.
+ *   ERODE, DILATE, OPEN, CLOSE  RGBA -> RGBA, dword-aligned device buffers; take BGR host frames (expanded to RGBA,
+ *                               A = 255) under MI355_INPUT_BGR.
+ *   *_GRAY8                     1 byte -> 1 byte with the single-channel rules above (any byte alignment, UNSUPPORTED
+ *                               under BGR).
+ * The ids are 24-31, leaving 18-23 unassigned: as with 8-15 after the gray8 block, callers (this library's own tests
+ * among them) rely on id 18, the first after the median block, staying invalid. */
+#define MI355_MAX_MORPH_K 17
+#define MI355_FILTER_ERODE 24        /* RGBA -> RGBA     */
+#define MI355_FILTER_DILATE 25       /* RGBA -> RGBA     */
+#define MI355_FILTER_OPEN 26         /* RGBA -> RGBA     */
+#define MI355_FILTER_CLOSE 27        /* RGBA -> RGBA     */
+#define MI355_FILTER_ERODE_GRAY8 28  /* 1 byte -> 1 byte */
+#define MI355_FILTER_DILATE_GRAY8 29 /* 1 byte -> 1 byte */
+#define MI355_FILTER_OPEN_GRAY8 30   /* 1 byte -> 1 byte */
+#define MI355_FILTER_CLOSE_GRAY8 31  /* 1 byte -> 1 byte */
 int mi355_filter_batched(mi355_ctx* ctx, int filter, const uint8_t* rgba, uint8_t* out, int w, int h,
                          int nframes, int k, float sigma, uint64_t prof_ns[6]);
 /* bytes per output pixel of a filter (4 or 1), or MI355_ERR_BAD_ARG.  Pure host function. */
 int mi355_filter_out_bpp(int filter);
-/* bytes per input pixel of a filter: 4 for the RGBA filters (ids 0-4, 16), 1 for the *_GRAY8 ids, or MI355_ERR_BAD_ARG.
+/* bytes per input pixel of a filter: 4 for the RGBA filters (ids 0-4, 16, 24-27), 1 for the *_GRAY8 ids, or MI355_ERR_BAD_ARG.
  * Pure host function.  Every buffer size of the batched, streamed, pool and group calls is counted in these bytes. */
 int mi355_filter_in_bpp(int filter);
 

@@ -300,14 +300,21 @@ bool filter_is_median(int f) { return f == MI355_FILTER_MEDIAN || f == MI355_FIL
 
 bool valid_median_k(int k) { return k >= 3 && k <= MI355_MAX_MEDIAN_K && (k & 1) == 1; }
 
+bool filter_is_morph(int f) { return f >= MI355_FILTER_ERODE && f <= MI355_FILTER_CLOSE_GRAY8; }
+
+bool valid_morph_k(int k) { return k >= 3 && k <= MI355_MAX_MORPH_K && (k & 1) == 1; }
+
 // the (k, sigma) of a call are acceptable for this filter: Gaussian filters take an odd k <= MI355_MAX_GAUSS_K and a
-// valid sigma, the median an odd 3 <= k <= MI355_MAX_MEDIAN_K (sigma ignored), the others ignore both
+// valid sigma, the median an odd 3 <= k <= MI355_MAX_MEDIAN_K, the morphology ids an odd 3 <= k <= MI355_MAX_MORPH_K
+// (sigma ignored), the others ignore both
 bool valid_filter_k(int f, int k, float sigma)
 {
     if (filter_needs_gauss(f))
         return valid_k(k) && valid_sigma(sigma);
     if (filter_is_median(f))
         return valid_median_k(k);
+    if (filter_is_morph(f))
+        return valid_morph_k(k);
     return true;
 }
 
@@ -338,7 +345,7 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
         return MI355_ERR_BAD_ARG;
     if (in_bpp == 4 && (reinterpret_cast<uintptr_t>(d_in) & 3u))
         return MI355_ERR_BAD_ARG;  // RGBA pixels are accessed as dwords
-    const bool rgba_out = (filter == MI355_FILTER_GRAY || filter == MI355_FILTER_GAUSS || filter == MI355_FILTER_MEDIAN);
+    const bool rgba_out = mi355_filter_out_bpp(filter) == 4;
     if (rgba_out && (reinterpret_cast<uintptr_t>(d_out) & 3u))
         return MI355_ERR_BAD_ARG;
     {
@@ -355,7 +362,7 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
         if (a0 < b1 && b0 < a1)
             return MI355_ERR_BAD_ARG;
     }
-    if (filter_is_median(filter) && !valid_median_k(k))
+    if ((filter_is_median(filter) && !valid_median_k(k)) || (filter_is_morph(filter) && !valid_morph_k(k)))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const GaussCoef* coef = nullptr;
@@ -407,6 +414,18 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
     case MI355_FILTER_MEDIAN:
     case MI355_FILTER_MEDIAN_GRAY8:
         e = launch_median(ctx->stream, in, out, w, h, nframes, k, filter == MI355_FILTER_MEDIAN_GRAY8, ctx->impl);
+        break;
+    case MI355_FILTER_ERODE:
+    case MI355_FILTER_DILATE:
+    case MI355_FILTER_OPEN:
+    case MI355_FILTER_CLOSE:
+        e = launch_morph(ctx->stream, in, out, w, h, nframes, k, filter - MI355_FILTER_ERODE, false);
+        break;
+    case MI355_FILTER_ERODE_GRAY8:
+    case MI355_FILTER_DILATE_GRAY8:
+    case MI355_FILTER_OPEN_GRAY8:
+    case MI355_FILTER_CLOSE_GRAY8:
+        e = launch_morph(ctx->stream, in, out, w, h, nframes, k, filter - MI355_FILTER_ERODE_GRAY8, true);
         break;
     default:
         return MI355_ERR_BAD_ARG;
@@ -771,14 +790,22 @@ MI355_API int mi355_filter_out_bpp(int filter)
     switch (filter) {
     case MI355_FILTER_GRAY:
     case MI355_FILTER_GAUSS:
-    case MI355_FILTER_MEDIAN: return 4;
+    case MI355_FILTER_MEDIAN:
+    case MI355_FILTER_ERODE:
+    case MI355_FILTER_DILATE:
+    case MI355_FILTER_OPEN:
+    case MI355_FILTER_CLOSE: return 4;
     case MI355_FILTER_GRAY1:
     case MI355_FILTER_SOBEL:
     case MI355_FILTER_PIPELINE:
     case MI355_FILTER_GAUSS_GRAY8:
     case MI355_FILTER_SOBEL_GRAY8:
     case MI355_FILTER_PIPELINE_GRAY8:
-    case MI355_FILTER_MEDIAN_GRAY8: return 1;
+    case MI355_FILTER_MEDIAN_GRAY8:
+    case MI355_FILTER_ERODE_GRAY8:
+    case MI355_FILTER_DILATE_GRAY8:
+    case MI355_FILTER_OPEN_GRAY8:
+    case MI355_FILTER_CLOSE_GRAY8: return 1;
     default: return MI355_ERR_BAD_ARG;
     }
 }
@@ -791,11 +818,19 @@ MI355_API int mi355_filter_in_bpp(int filter)
     case MI355_FILTER_GAUSS:
     case MI355_FILTER_SOBEL:
     case MI355_FILTER_PIPELINE:
-    case MI355_FILTER_MEDIAN: return 4;
+    case MI355_FILTER_MEDIAN:
+    case MI355_FILTER_ERODE:
+    case MI355_FILTER_DILATE:
+    case MI355_FILTER_OPEN:
+    case MI355_FILTER_CLOSE: return 4;
     case MI355_FILTER_GAUSS_GRAY8:
     case MI355_FILTER_SOBEL_GRAY8:
     case MI355_FILTER_PIPELINE_GRAY8:
-    case MI355_FILTER_MEDIAN_GRAY8: return 1;
+    case MI355_FILTER_MEDIAN_GRAY8:
+    case MI355_FILTER_ERODE_GRAY8:
+    case MI355_FILTER_DILATE_GRAY8:
+    case MI355_FILTER_OPEN_GRAY8:
+    case MI355_FILTER_CLOSE_GRAY8: return 1;
     default: return MI355_ERR_BAD_ARG;
     }
 }

@@ -68,10 +68,17 @@ bool filter_needs_gauss(int f)
            f == MI355_FILTER_PIPELINE_GRAY8;
 }
 
-bool filter_is_median(int f) { return f == MI355_FILTER_MEDIAN || f == MI355_FILTER_MEDIAN_GRAY8; }
-
-// the median takes an odd 3 <= k <= MI355_MAX_MEDIAN_K and no table; checked before the group allocates anything
-bool median_k_ok(int f, int k) { return !filter_is_median(f) || (k >= 3 && k <= MI355_MAX_MEDIAN_K && (k & 1) == 1); }
+// the median and the morphology ids take an odd 3 <= k <= their maximum and no table; checked before the group
+// allocates anything
+bool table_free_k_ok(int f, int k)
+{
+    int kmax = 0;
+    if (f == MI355_FILTER_MEDIAN || f == MI355_FILTER_MEDIAN_GRAY8)
+        kmax = MI355_MAX_MEDIAN_K;
+    else if (f >= MI355_FILTER_ERODE && f <= MI355_FILTER_CLOSE_GRAY8)
+        kmax = MI355_MAX_MORPH_K;
+    return kmax == 0 || (k >= 3 && k <= kmax && (k & 1) == 1);
+}
 
 uint32_t fbits(float f)
 {
@@ -274,7 +281,7 @@ MI355_API int mi355_group_filter_batched(mi355_group* g, int filter, const uint8
     if (!g || !rgba || !out || w <= 0 || h <= 0 || nframes <= 0)
         return MI355_ERR_BAD_ARG;
     const int bpp = mi355_filter_out_bpp(filter);
-    if (bpp < 0 || !median_k_ok(filter, k))
+    if (bpp < 0 || !table_free_k_ok(filter, k))
         return MI355_ERR_BAD_ARG;
     if (g->input_format == MI355_INPUT_BGR && mi355_filter_in_bpp(filter) == 1)
         return MI355_ERR_UNSUPPORTED;  // gray planes have no BGR form
@@ -303,7 +310,7 @@ MI355_API int mi355_group_filter_batched(mi355_group* g, int filter, const uint8
 MI355_API int mi355_group_filter_dev(mi355_group* g, int filter, const void* const* d_in, void* const* d_out, int w, int h,
                                      const int* nframes, int k, float sigma)
 {
-    if (!g || !d_in || !d_out || !nframes || mi355_filter_out_bpp(filter) < 0 || !median_k_ok(filter, k))
+    if (!g || !d_in || !d_out || !nframes || mi355_filter_out_bpp(filter) < 0 || !table_free_k_ok(filter, k))
         return MI355_ERR_BAD_ARG;
     for (size_t i = 0; i < g->members.size(); i++)
         if (nframes[i] < 0)

@@ -107,6 +107,12 @@ hipError_t launch_pipeline_gray8(hipStream_t stream, const uint8_t* d_in, uint8_
 hipError_t launch_median(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k,
                          bool gray8, int impl);
 
+// rectangular morphology (morph.hip): op 0 erode, 1 dilate, 2 open, 3 close, k x k MORPH_RECT, odd k in
+// 3..MI355_MAX_MORPH_K, clamp-to-edge borders; gray8 = 1 byte per pixel (any byte alignment), else RGBA (dword-aligned).
+// One LDS-tiled kernel for every op and k, one launch per call (OPEN / CLOSE included); there is no impl choice.
+hipError_t launch_morph(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k,
+                        int op, bool gray8);
+
 // image2d_t-mode semantics of the reference (image2d.hip): filter 0 gray / 2 gauss / 3 sobel
 hipError_t launch_image2d(hipStream_t stream, int filter, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                           int k, const float* d_table);

@@ -25,6 +25,10 @@ FILTER_GAUSS_GRAY8, FILTER_SOBEL_GRAY8, FILTER_PIPELINE_GRAY8 = 5, 6, 7
 # median filter (MI355_FILTER_MEDIAN*): ids 16 and 17, k in {3, 5, 7}, sigma ignored
 FILTER_MEDIAN, FILTER_MEDIAN_GRAY8 = 16, 17
 MAX_MEDIAN_K = 7
+# rectangular morphology (MI355_FILTER_ERODE ... CLOSE_GRAY8): ids 24-31 (18-23 unassigned), odd 3 <= k <= MAX_MORPH_K, sigma ignored
+FILTER_ERODE, FILTER_DILATE, FILTER_OPEN, FILTER_CLOSE = 24, 25, 26, 27
+FILTER_ERODE_GRAY8, FILTER_DILATE_GRAY8, FILTER_OPEN_GRAY8, FILTER_CLOSE_GRAY8 = 28, 29, 30, 31
+MAX_MORPH_K = 17
 GAUSS_FAST, GAUSS_EXACT = 0, 1
 INPUT_RGBA, INPUT_BGR = 0, 1
 IMPL_AUTO, IMPL_TILE, IMPL_MFMA, IMPL_VALU = 0, 1, 2, 3
@@ -33,7 +37,10 @@ OUT_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 1, FILTER_GAUSS: 4, FILTER_SOBEL: 1, FI
 IN_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 4, FILTER_GAUSS: 4, FILTER_SOBEL: 4, FILTER_PIPELINE: 4,
           FILTER_GAUSS_GRAY8: 1, FILTER_SOBEL_GRAY8: 1, FILTER_PIPELINE_GRAY8: 1}
 # ids outside IN_BPP / OUT_BPP (which list the filters 0-7); every lookup goes through _in_bpp / _out_bpp
-_MORE_BPP = {FILTER_MEDIAN: (4, 4), FILTER_MEDIAN_GRAY8: (1, 1)}
+_MORE_BPP = {FILTER_MEDIAN: (4, 4), FILTER_MEDIAN_GRAY8: (1, 1),
+             FILTER_ERODE: (4, 4), FILTER_DILATE: (4, 4), FILTER_OPEN: (4, 4), FILTER_CLOSE: (4, 4),
+             FILTER_ERODE_GRAY8: (1, 1), FILTER_DILATE_GRAY8: (1, 1), FILTER_OPEN_GRAY8: (1, 1),
+             FILTER_CLOSE_GRAY8: (1, 1)}
 
 
 def _in_bpp(filt):
@@ -344,6 +351,40 @@ class Context:
     def median_gray8(self, y, k):
         """cv::medianBlur of (h, w) / (n, h, w) single-channel frames (MI355_FILTER_MEDIAN_GRAY8)."""
         return self._host_gray8(FILTER_MEDIAN_GRAY8, y, k)
+
+    def erode(self, rgba, k, profile=False):
+        """cv::erode with a k x k rectangle on every channel of (h, w, 4) / (n, h, w, 4) frames (MI355_FILTER_ERODE);
+        odd 3 <= k <= MAX_MORPH_K, clamp-to-edge borders."""
+        return self._host(FILTER_ERODE, rgba, k, 0.0, profile=profile)
+
+    def dilate(self, rgba, k, profile=False):
+        """cv::dilate with a k x k rectangle on every channel (MI355_FILTER_DILATE)."""
+        return self._host(FILTER_DILATE, rgba, k, 0.0, profile=profile)
+
+    def morph_open(self, rgba, k, profile=False):
+        """cv::morphologyEx(MORPH_OPEN) with a k x k rectangle, dilate(erode(x)) in one launch (MI355_FILTER_OPEN)."""
+        return self._host(FILTER_OPEN, rgba, k, 0.0, profile=profile)
+
+    def morph_close(self, rgba, k, profile=False):
+        """cv::morphologyEx(MORPH_CLOSE) with a k x k rectangle, erode(dilate(x)) in one launch (MI355_FILTER_CLOSE).
+        (Named morph_*: Context.close() releases the context.)"""
+        return self._host(FILTER_CLOSE, rgba, k, 0.0, profile=profile)
+
+    def erode_gray8(self, y, k):
+        """cv::erode of (h, w) / (n, h, w) single-channel frames (MI355_FILTER_ERODE_GRAY8)."""
+        return self._host_gray8(FILTER_ERODE_GRAY8, y, k)
+
+    def dilate_gray8(self, y, k):
+        """cv::dilate of single-channel frames (MI355_FILTER_DILATE_GRAY8)."""
+        return self._host_gray8(FILTER_DILATE_GRAY8, y, k)
+
+    def morph_open_gray8(self, y, k):
+        """MORPH_OPEN of single-channel frames (MI355_FILTER_OPEN_GRAY8)."""
+        return self._host_gray8(FILTER_OPEN_GRAY8, y, k)
+
+    def morph_close_gray8(self, y, k):
+        """MORPH_CLOSE of single-channel frames (MI355_FILTER_CLOSE_GRAY8)."""
+        return self._host_gray8(FILTER_CLOSE_GRAY8, y, k)
 
     def image2d(self, filt, rgba, k=0, sigma=0.0):
         """mi355_image2d_rgba8: the reference's image2d_t-mode semantics.  Returns (out, six timestamps)."""
