@@ -240,6 +240,36 @@ int mi355_gauss_weights_image2d(int k, float sigma, float* out_k2);
 #define MI355_FILTER_DILATE_GRAY8 29 /* 1 byte -> 1 byte */
 #define MI355_FILTER_OPEN_GRAY8 30   /* 1 byte -> 1 byte */
 #define MI355_FILTER_CLOSE_GRAY8 31  /* 1 byte -> 1 byte */
+/* Whole-frame statistics of single-channel frames, OpenCV's plain C++ path (not its IPP or OpenCL paths).  Both ids
+ * follow the single-channel rules above (tightly packed, any byte alignment, any width >= 1, UNSUPPORTED under BGR);
+ * k and sigma are ignored and no table is made.  Each frame is its own image: its histogram never includes a
+ * neighbouring frame.  A call whose w * h is 2^31 or more is MI355_ERR_BAD_ARG (OpenCV counts pixels in an int).
+ * hist = the frame's 256 bin counts, total = w * h.
+ *   EQUALIZE_GRAY8  cv::equalizeHist.  i0 = the first bin with a nonzero count.  If hist[i0] == total every output
+ *                   byte is i0.  Otherwise, in fp32 with no fused multiply-add: scale = 255.f / (float)(total -
+ *                   hist[i0]); lut[i0] = 0; for i > i0: sum += hist[i] (int), lut[i] = saturate_u8(rint_half_even(
+ *                   (float)sum * scale)).  Output byte = lut[input byte].
+ *   OTSU_GRAY8      cv::threshold(src, dst, 0, 255, THRESH_BINARY | THRESH_OTSU).  The threshold t is OpenCV's fp64
+ *                   loop, operation by operation, no fused multiply-add, left to right:
+ *                     scale = 1.0 / (double)(w*h);  mu = sum_i i*(double)hist[i];  mu *= scale
+ *                     mu1 = q1 = max_sigma = 0;  t = 0
+ *                     for i in 0..255:
+ *                         p = hist[i]*scale;  mu1 *= q1;  q1 += p;  q2 = 1.0 - q1
+ *                         if min(q1,q2) < FLT_EPSILON or max(q1,q2) > 1.0 - FLT_EPSILON: continue
+ *                         mu1 = (mu1 + i*p) / q1;  mu2 = (mu - q1*mu1) / q2
+ *                         sigma = q1*q2*(mu1-mu2)*(mu1-mu2)
+ *                         if sigma > max_sigma: max_sigma = sigma; t = i
+ *                   Output byte = src > t ? 255 : 0.  Two quirks of that loop are kept: on a `continue` mu1 has been
+ *                   multiplied by q1 and not divided again (visible only when a bin holds less than FLT_EPSILON of
+ *                   the frame, i.e. frames of more than 2^23 pixels), and empty bins between occupied ones can move
+ *                   sigma in its last bits, where the strict > decides the winner.  A constant frame has t = 0.
+ * Three launches per call (histogram, table, apply) on the context's stream.  The scratch (1 KiB of histogram and
+ * 256 B of table per frame) is pooled in the context: after the first call for a given frame count a call allocates
+ * nothing and waits for nothing.  The impl knob (MI355_IMPL_*) does not affect these ids.
+ * The ids are 40 and 41, leaving 32-39 unassigned: id 42, the first after this block, stays invalid as callers expect.
+ * mi355_hist_gray8_dev and mi355_otsu_thresholds_gray8_dev (device-resident calls, below) expose the two steps. */
+#define MI355_FILTER_EQUALIZE_GRAY8 40 /* 1 byte -> 1 byte */
+#define MI355_FILTER_OTSU_GRAY8 41     /* 1 byte -> 1 byte */
 int mi355_filter_batched(mi355_ctx* ctx, int filter, const uint8_t* rgba, uint8_t* out, int w, int h,
                          int nframes, int k, float sigma, uint64_t prof_ns[6]);
 /* bytes per output pixel of a filter (4 or 1), or MI355_ERR_BAD_ARG.  Pure host function. */
@@ -284,6 +314,16 @@ int mi355_pipeline_rgba8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int 
                              int k, float sigma);
 int mi355_filter_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int w, int h,
                      int nframes, int k, float sigma);
+/* The statistics behind MI355_FILTER_EQUALIZE_GRAY8 / OTSU_GRAY8, with the rules of mi355_filter_dev (no
+ * synchronisation, overlapping buffers rejected, the same stream-capture promise) and the single-channel input rules.
+ *   mi355_hist_gray8_dev             writes nframes x 256 exact counts (cv::calcHist of each frame) to d_hist, which
+ *                                    it overwrites (it is zeroed in-stream first, not added to); d_hist needs 4-byte
+ *                                    alignment.
+ *   mi355_otsu_thresholds_gray8_dev  writes one t per frame (the value cv::threshold returns with THRESH_OTSU) to
+ *                                    d_thresh (4-byte aligned).
+ * w * h of 2^31 or more is MI355_ERR_BAD_ARG. */
+int mi355_hist_gray8_dev(mi355_ctx* ctx, const void* d_in, uint32_t* d_hist, int w, int h, int nframes);
+int mi355_otsu_thresholds_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_thresh, int w, int h, int nframes);
 
 /* Synthetic frames: px = hash(seed, first_frame + f, y, x), A = 255; mode 1 = smooth
  * gradient + 4-bit noise, mode 2 = flat 64 x 64 patches (constant windows: the content that sends the

@@ -51,6 +51,10 @@ struct mi355_ctx {
     float* d_img_table = nullptr;  // image2d-mode Gaussian table (k*k floats, MI355_MAX_GAUSS_K^2 capacity)
     void* d_flags = nullptr;  // per-work-item flags of the two-kernel Gaussian (gauss_wide.hip), pooled
     size_t d_flags_cap = 0;
+    void* d_hist = nullptr;  // per-frame 256-bin histograms of EQUALIZE_GRAY8 / OTSU_GRAY8 (hist.hip), pooled
+    size_t d_hist_cap = 0;
+    void* d_lut = nullptr;  // their per-frame 256-byte tables, pooled
+    size_t d_lut_cap = 0;
     // streamed path: copy streams, per-slot events and device slots (created on first use)
     static constexpr int kSlots = 3;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
@@ -318,6 +322,11 @@ bool valid_filter_k(int f, int k, float sigma)
     return true;
 }
 
+bool filter_is_hist(int f) { return f == MI355_FILTER_EQUALIZE_GRAY8 || f == MI355_FILTER_OTSU_GRAY8; }
+
+// the histogram ids take frames below 2^31 pixels (OpenCV counts a frame's pixels in an int)
+bool valid_frame_size(int f, int w, int h) { return !filter_is_hist(f) || (int64_t)w * (int64_t)h < (1ll << 31); }
+
 // the single-channel filters take 1-byte pixels: any byte alignment, and no BGR ingest
 bool filter_is_gray8(int f) { return mi355_filter_in_bpp(f) == 1; }
 
@@ -329,6 +338,23 @@ int check_frames(const void* in, const void* out, int w, int h, int nframes)
     const double px = (double)w * (double)h * (double)nframes;
     if (px > 6.0e10)
         return MI355_ERR_BAD_ARG;
+    return MI355_OK;
+}
+
+// EQUALIZE_GRAY8 / OTSU_GRAY8 up to the table: the pooled histograms, zeroed in-stream, the histogram launch and the
+// table launch (into the pooled tables; Otsu's thresholds also to d_thresh when it is not null).  Only the first call
+// for a larger frame count allocates (and synchronises, in ensure()).
+int hist_tables(mi355_ctx* ctx, const uint8_t* in, int32_t* d_thresh, int w, int h, int nframes, bool otsu)
+{
+    int rc = ensure(ctx, &ctx->d_hist, &ctx->d_hist_cap, (size_t)nframes * 256 * sizeof(uint32_t));
+    if (rc == MI355_OK)
+        rc = ensure(ctx, &ctx->d_lut, &ctx->d_lut_cap, (size_t)nframes * 256);
+    if (rc != MI355_OK)
+        return rc;
+    uint32_t* hist = static_cast<uint32_t*>(ctx->d_hist);
+    HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)nframes * 256 * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, launch_hist(ctx->stream, in, hist, w, h, nframes));
+    HIP_TRY(ctx, launch_hist_table(ctx->stream, hist, static_cast<uint8_t*>(ctx->d_lut), d_thresh, w, h, nframes, otsu));
     return MI355_OK;
 }
 
@@ -362,7 +388,8 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
         if (a0 < b1 && b0 < a1)
             return MI355_ERR_BAD_ARG;
     }
-    if ((filter_is_median(filter) && !valid_median_k(k)) || (filter_is_morph(filter) && !valid_morph_k(k)))
+    if ((filter_is_median(filter) && !valid_median_k(k)) || (filter_is_morph(filter) && !valid_morph_k(k)) ||
+        !valid_frame_size(filter, w, h))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const GaussCoef* coef = nullptr;
@@ -427,6 +454,13 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
     case MI355_FILTER_CLOSE_GRAY8:
         e = launch_morph(ctx->stream, in, out, w, h, nframes, k, filter - MI355_FILTER_ERODE_GRAY8, true);
         break;
+    case MI355_FILTER_EQUALIZE_GRAY8:
+    case MI355_FILTER_OTSU_GRAY8:
+        rc = hist_tables(ctx, in, nullptr, w, h, nframes, filter == MI355_FILTER_OTSU_GRAY8);
+        if (rc != MI355_OK)
+            return rc;
+        e = launch_lut_apply(ctx->stream, in, out, static_cast<const uint8_t*>(ctx->d_lut), w, h, nframes);
+        break;
     default:
         return MI355_ERR_BAD_ARG;
     }
@@ -464,7 +498,7 @@ int run_host(mi355_ctx* ctx, int filter, const uint8_t* in, uint8_t* out, int w,
     int rc = check_frames(in, out, w, h, nframes);
     if (rc != MI355_OK)
         return rc;
-    if (!valid_filter_k(filter, k, sigma))
+    if (!valid_filter_k(filter, k, sigma) || !valid_frame_size(filter, w, h))
         return MI355_ERR_BAD_ARG;
     const bool bgr = ctx->input_format == MI355_INPUT_BGR;
     if (bgr && filter_is_gray8(filter))
@@ -607,6 +641,10 @@ MI355_API int mi355_ctx_destroy(mi355_ctx* ctx)
         (void)hipFree(ctx->d_acc);
     if (ctx->d_flags)
         (void)hipFree(ctx->d_flags);
+    if (ctx->d_hist)
+        (void)hipFree(ctx->d_hist);
+    if (ctx->d_lut)
+        (void)hipFree(ctx->d_lut);
     if (ctx->d_img_table)
         (void)hipFree(ctx->d_img_table);
     for (int i = 0; i < mi355_ctx::kSlots; i++) {
@@ -805,7 +843,9 @@ MI355_API int mi355_filter_out_bpp(int filter)
     case MI355_FILTER_ERODE_GRAY8:
     case MI355_FILTER_DILATE_GRAY8:
     case MI355_FILTER_OPEN_GRAY8:
-    case MI355_FILTER_CLOSE_GRAY8: return 1;
+    case MI355_FILTER_CLOSE_GRAY8:
+    case MI355_FILTER_EQUALIZE_GRAY8:
+    case MI355_FILTER_OTSU_GRAY8: return 1;
     default: return MI355_ERR_BAD_ARG;
     }
 }
@@ -830,7 +870,9 @@ MI355_API int mi355_filter_in_bpp(int filter)
     case MI355_FILTER_ERODE_GRAY8:
     case MI355_FILTER_DILATE_GRAY8:
     case MI355_FILTER_OPEN_GRAY8:
-    case MI355_FILTER_CLOSE_GRAY8: return 1;
+    case MI355_FILTER_CLOSE_GRAY8:
+    case MI355_FILTER_EQUALIZE_GRAY8:
+    case MI355_FILTER_OTSU_GRAY8: return 1;
     default: return MI355_ERR_BAD_ARG;
     }
 }
@@ -912,7 +954,7 @@ MI355_API int mi355_filter_stream(mi355_ctx* ctx, int filter, const uint8_t* rgb
     int rc = check_frames(rgba, out, w, h, nframes);
     if (rc != MI355_OK)
         return rc;
-    if (!valid_filter_k(filter, k, sigma))
+    if (!valid_filter_k(filter, k, sigma) || !valid_frame_size(filter, w, h))
         return MI355_ERR_BAD_ARG;
     const bool bgr = ctx->input_format == MI355_INPUT_BGR;
     if (bgr && filter_is_gray8(filter))
@@ -1022,6 +1064,45 @@ MI355_API int mi355_filter_dev(mi355_ctx* ctx, int filter, const void* d_in, voi
     if (mi355_filter_out_bpp(filter) < 0)
         return MI355_ERR_BAD_ARG;
     return dispatch_dev(ctx, filter, d_in, d_out, w, h, nframes, k, sigma);
+}
+
+// the argument checks of the two statistics calls: mi355_filter_dev's, with `nout` bytes of 4-byte aligned output
+static int check_stats_call(mi355_ctx* ctx, const void* d_in, const void* d_out, int w, int h, int nframes, size_t nout)
+{
+    if (!ctx)
+        return MI355_ERR_BAD_ARG;
+    int rc = check_frames(d_in, d_out, w, h, nframes);
+    if (rc != MI355_OK)
+        return rc;
+    if (!valid_frame_size(MI355_FILTER_EQUALIZE_GRAY8, w, h) || (reinterpret_cast<uintptr_t>(d_out) & 3u))
+        return MI355_ERR_BAD_ARG;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_in), a1 = a0 + (size_t)w * h * nframes;
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + nout;
+    if (a0 < b1 && b0 < a1)
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return MI355_OK;
+}
+
+MI355_API int mi355_hist_gray8_dev(mi355_ctx* ctx, const void* d_in, uint32_t* d_hist, int w, int h, int nframes)
+{
+    const size_t nbytes = (size_t)(nframes > 0 ? nframes : 0) * 256 * sizeof(uint32_t);
+    const int rc = check_stats_call(ctx, d_in, d_hist, w, h, nframes, nbytes);
+    if (rc != MI355_OK)
+        return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, nbytes, ctx->stream));
+    HIP_TRY(ctx, launch_hist(ctx->stream, static_cast<const uint8_t*>(d_in), d_hist, w, h, nframes));
+    return MI355_OK;
+}
+
+MI355_API int mi355_otsu_thresholds_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_thresh, int w, int h,
+                                              int nframes)
+{
+    const size_t nbytes = (size_t)(nframes > 0 ? nframes : 0) * sizeof(int32_t);
+    const int rc = check_stats_call(ctx, d_in, d_thresh, w, h, nframes, nbytes);
+    if (rc != MI355_OK)
+        return rc;
+    return hist_tables(ctx, static_cast<const uint8_t*>(d_in), d_thresh, w, h, nframes, true);
 }
 
 MI355_API int mi355_gray_rgba8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h,
@@ -1137,7 +1218,7 @@ MI355_API int mi355_pool_alloc(mi355_ctx* ctx, int filter, int w, int h, int nfr
     const int bpp = mi355_filter_out_bpp(filter);
     if (bpp < 0 || w <= 0 || h <= 0 || nframes <= 0 || (double)w * h * nframes > 6.0e10)
         return MI355_ERR_BAD_ARG;
-    if (!valid_filter_k(filter, k, sigma))
+    if (!valid_filter_k(filter, k, sigma) || !valid_frame_size(filter, w, h))
         return MI355_ERR_BAD_ARG;
     constexpr int kMaxCand = 16;
     for (int i = 0; probe_ms && i < tries; i++)

@@ -1,0 +1,321 @@
+// hist.hip — whole-frame statistics of single-channel frames: the 256-bin histogram (cv::calcHist), histogram
+// equalization (MI355_FILTER_EQUALIZE_GRAY8, cv::equalizeHist) and Otsu thresholding (MI355_FILTER_OTSU_GRAY8,
+// cv::threshold(THRESH_BINARY | THRESH_OTSU)).  Semantics: include/mi355_imgfilter.h.
+//
+// Every frame is the flat byte range [f * npx, (f + 1) * npx), npx = w * h < 2^31 (OpenCV counts pixels in an int).
+// Three launches on one stream, the kernel boundaries being the only cross-workgroup synchronisation:
+//   hist_kernel   a block of 256 threads takes 256 x kHistVec 16-byte vectors of one frame (the frame's body from its
+//                 first 16-byte-aligned input byte; the unaligned head and tail, < 16 bytes each, go byte by byte in
+//                 the frame's first block).  Each wave counts into a private 256-bin LDS histogram with ds_add_u32;
+//                 the block sums its four and adds every nonzero bin once into the frame's row of a zeroed global
+//                 histogram (agent-scope integer atomics: exact, so the result does not depend on arrival order).
+//                 Flat content would put up to 64 lanes of one ds_add on one address (64-way serialised): equal bytes
+//                 are merged first.  Lanes whose 16 bytes all equal the wave's first such value add one count for all
+//                 of them, other lanes with 16 equal bytes add 16 once, dwords of 4 equal bytes add 4 once, and only
+//                 the rest add byte by byte;
+//   table_kernel  one wave per frame reads the histogram and writes a 256-byte table (LUT) per frame.  Equalize: an
+//                 integer prefix sum across lanes (exact in any order), then one fp32 multiply and rint per bin.
+//                 Otsu: OpenCV's serial fp64 loop in one lane, operation by operation (-ffp-contract=off: no fused
+//                 multiply-add; the fp64 divisions are the IEEE correctly rounded sequence), then lut[v] = v > t;
+//   apply_kernel  the frame's LUT in LDS, one ds_read_u8 per pixel; 16-byte non-temporal stores aligned on the output,
+//                 16-byte loads at whatever alignment the input then has, head and tail bytes as in hist_kernel.
+#include "common.hpp"
+#include "kernels.hpp"
+
+#include <cfloat>
+
+namespace mi355 {
+
+namespace {
+
+constexpr int kHThreads = 256;
+constexpr int kHWaves = kHThreads / kWave;
+constexpr int kHistVec = 16;  // 16-byte vectors per thread of hist_kernel: 64 KiB per block, 256 atomics per flush
+constexpr int kApplyVec = 8;  // per thread of apply_kernel: 32 KiB per block
+
+typedef u32x4 __attribute__((aligned(1))) u32x4_a1;
+
+// where the 16-byte body of a frame starts, relative to the frame, for a frame at address a of npx bytes
+__device__ __forceinline__ uint32_t head_bytes(uintptr_t a, uint32_t npx)
+{
+    const uint32_t hb = (uint32_t)((16u - (a & 15u)) & 15u);
+    return hb < npx ? hb : npx;
+}
+
+__device__ __forceinline__ void lds_add(uint32_t* hw, uint32_t bin, uint32_t n)
+{
+    __hip_atomic_fetch_add(hw + bin, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ void count_dword(uint32_t* hw, uint32_t d)
+{
+    const uint32_t b = d & 0xFFu;
+    if (d == b * 0x01010101u) {
+        lds_add(hw, b, 4);
+    } else {
+        lds_add(hw, b, 1);
+        lds_add(hw, (d >> 8) & 0xFFu, 1);
+        lds_add(hw, (d >> 16) & 0xFFu, 1);
+        lds_add(hw, d >> 24, 1);
+    }
+}
+
+// count the 16 bytes of v (valid lanes only) into the wave's LDS histogram hw
+__device__ __forceinline__ void count_vec(uint32_t* hw, const u32x4& v, bool valid)
+{
+    const uint32_t b = v.x & 0xFFu, rep = b * 0x01010101u;
+    const bool uni = valid && v.x == rep && v.y == rep && v.z == rep && v.w == rep;
+    const uint64_t um = __ballot(uni);
+    if (um) {
+        // the lanes whose 16 bytes all hold the first uniform lane's value: one add for all of them
+        const int leader = __ffsll((unsigned long long)um) - 1;
+        const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane((int)b, leader);
+        const uint64_t m = __ballot(uni && b == lb);
+        if ((int)__lane_id() == leader)
+            lds_add(hw, lb, 16u * (uint32_t)__popcll(m));
+        if ((m >> __lane_id()) & 1u)
+            return;
+    }
+    if (!valid)
+        return;
+    if (uni) {
+        lds_add(hw, b, 16);
+        return;
+    }
+    count_dword(hw, v.x);
+    count_dword(hw, v.y);
+    count_dword(hw, v.z);
+    count_dword(hw, v.w);
+}
+
+__global__ __launch_bounds__(kHThreads) void hist_kernel(const uint8_t* __restrict__ in, uint32_t* __restrict__ hist,
+                                                         uint32_t npx, uint32_t tiles)
+{
+    __shared__ uint32_t sh[kHWaves * 256];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < kHWaves * 256; i += kHThreads)
+        sh[i] = 0;
+    __syncthreads();
+    const uint32_t f = blockIdx.x / tiles, tile = blockIdx.x - f * tiles;
+    const uint8_t* p = in + (size_t)f * npx;
+    const uint32_t head = head_bytes(reinterpret_cast<uintptr_t>(p), npx);
+    const uint32_t nvec = (npx - head) / 16, body_end = head + 16 * nvec;
+    const u32x4* vp = reinterpret_cast<const u32x4*>(p + head);
+    uint32_t* hw = sh + (tid / kWave) * 256;
+    const uint32_t j0 = tile * (kHThreads * kHistVec) + tid;
+#pragma unroll
+    for (int u0 = 0; u0 < kHistVec; u0 += 4) {
+        u32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t j = j0 + (u0 + u) * kHThreads;
+            v[u] = j < nvec ? __builtin_nontemporal_load(vp + j) : u32x4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            count_vec(hw, v[u], j0 + (u0 + u) * kHThreads < nvec);
+    }
+    if (tile == 0) {
+        if ((uint32_t)tid < head)
+            lds_add(hw, p[tid], 1);
+        else if (tid >= 16 && tid < 32 && body_end + (uint32_t)(tid - 16) < npx)
+            lds_add(hw, p[body_end + (tid - 16)], 1);
+    }
+    __syncthreads();
+    uint32_t s = 0;
+#pragma unroll
+    for (int wv = 0; wv < kHWaves; wv++)
+        s += sh[wv * 256 + tid];
+    if (s)
+        __hip_atomic_fetch_add(hist + (size_t)f * 256 + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// OpenCV's getThreshVal_Otsu_8u loop (include/mi355_imgfilter.h), one lane; h = the frame's 256 counts in LDS
+__device__ int otsu_threshold(const uint32_t* h, uint32_t total, double mu)
+{
+    const double scale = 1.0 / (double)total;
+    mu *= scale;
+    double mu1 = 0.0, q1 = 0.0, max_sigma = 0.0;
+    int t = 0;
+    const double eps = (double)FLT_EPSILON;
+    for (int i = 0; i < 256; i++) {
+        const double p = (double)h[i] * scale;
+        mu1 *= q1;
+        q1 += p;
+        const double q2 = 1.0 - q1;
+        const double lo = q2 < q1 ? q2 : q1, hi = q1 < q2 ? q2 : q1;  // std::min / std::max
+        if (lo < eps || hi > 1.0 - eps)
+            continue;
+        mu1 = (mu1 + (double)i * p) / q1;
+        const double mu2 = (mu - q1 * mu1) / q2;
+        const double d = mu1 - mu2;
+        const double sigma = q1 * q2 * d * d;
+        if (sigma > max_sigma) {
+            max_sigma = sigma;
+            t = i;
+        }
+    }
+    return t;
+}
+
+// one wave per frame; lut may be null (thresholds only), thresh may be null (Otsu without reporting t)
+__global__ __launch_bounds__(kWave) void table_kernel(const uint32_t* __restrict__ hist, uint8_t* __restrict__ lut,
+                                                      int32_t* __restrict__ thresh, uint32_t total, int otsu)
+{
+    __shared__ uint32_t sh[256];
+    __shared__ int s_t;
+    const uint32_t f = blockIdx.x;
+    const int lane = threadIdx.x;
+    const u32x4 hv = reinterpret_cast<const u32x4*>(hist + (size_t)f * 256)[lane];  // bins 4 lane .. 4 lane + 3
+    uint32_t out = 0;
+    if (!otsu) {
+        // i0 = the first occupied bin (there is one: total >= 1)
+        const uint64_t nz = __ballot((hv.x | hv.y | hv.z | hv.w) != 0);
+        const int l0 = __ffsll((unsigned long long)nz) - 1;
+        const int j_own = hv.x ? 0 : (hv.y ? 1 : (hv.z ? 2 : 3));
+        const uint32_t c_own = hv.x ? hv.x : (hv.y ? hv.y : (hv.z ? hv.z : hv.w));
+        const int i0 = 4 * l0 + __builtin_amdgcn_readlane(j_own, l0);
+        const uint32_t h0 = (uint32_t)__builtin_amdgcn_readlane((int)c_own, l0);
+        if (h0 == total) {
+            out = (uint32_t)i0 * 0x01010101u;
+        } else {
+            const float scale = 255.0f / (float)(int)(total - h0);
+            // inclusive prefix sum of the per-lane sums (integers: exact in any order)
+            const uint32_t lsum = hv.x + hv.y + hv.z + hv.w;
+            uint32_t inc = lsum;
+#pragma unroll
+            for (int d = 1; d < kWave; d *= 2) {
+                const uint32_t o = __shfl_up(inc, d);
+                if (lane >= d)
+                    inc += o;
+            }
+            uint32_t c = inc - lsum;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                c += hv[j];
+                const int i = 4 * lane + j;
+                uint32_t byte = 0;
+                if (i > i0) {
+                    // sum of the bins i0 + 1 .. i (the bins below i0 are empty); (float)sum * scale, cvRound
+                    const float v = __builtin_rintf((float)(int)(c - h0) * scale);
+                    byte = v >= 255.0f ? 255u : (uint32_t)v;
+                }
+                out |= byte << (8 * j);
+            }
+        }
+    } else {
+        // mu = sum i * hist[i]: every partial sum is an integer below 2^53, so the serial double sum is this exact
+        // integer whatever the order of the additions
+        uint64_t m = (uint64_t)(4 * lane) * hv.x + (uint64_t)(4 * lane + 1) * hv.y + (uint64_t)(4 * lane + 2) * hv.z +
+                     (uint64_t)(4 * lane + 3) * hv.w;
+#pragma unroll
+        for (int d = kWave / 2; d >= 1; d /= 2)
+            m += __shfl_xor(m, d);
+        reinterpret_cast<u32x4*>(sh)[lane] = hv;
+        __syncthreads();
+        if (lane == 0) {
+            const int t = otsu_threshold(sh, total, (double)m);
+            s_t = t;
+            if (thresh)
+                thresh[f] = t;
+        }
+        __syncthreads();
+        const int t = s_t;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            out |= (4 * lane + j > t ? 0xFFu : 0u) << (8 * j);
+    }
+    if (lut)
+        reinterpret_cast<uint32_t*>(lut + (size_t)f * 256)[lane] = out;
+}
+
+__device__ __forceinline__ uint32_t lut_dword(const uint8_t* sl, uint32_t d)
+{
+    return (uint32_t)sl[d & 0xFFu] | ((uint32_t)sl[(d >> 8) & 0xFFu] << 8) | ((uint32_t)sl[(d >> 16) & 0xFFu] << 16) |
+           ((uint32_t)sl[d >> 24] << 24);
+}
+
+__global__ __launch_bounds__(kHThreads) void apply_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                                          const uint8_t* __restrict__ lut, uint32_t npx, uint32_t tiles)
+{
+    __shared__ uint8_t sl[256];
+    const int tid = threadIdx.x;
+    const uint32_t f = blockIdx.x / tiles, tile = blockIdx.x - f * tiles;
+    sl[tid] = lut[(size_t)f * 256 + tid];
+    __syncthreads();
+    const uint8_t* p = in + (size_t)f * npx;
+    uint8_t* q = out + (size_t)f * npx;
+    const uint32_t head = head_bytes(reinterpret_cast<uintptr_t>(q), npx);
+    const uint32_t nvec = (npx - head) / 16, body_end = head + 16 * nvec;
+    const uint32_t j0 = tile * (kHThreads * kApplyVec) + tid;
+    u32x4 v[kApplyVec];
+#pragma unroll
+    for (int u = 0; u < kApplyVec; u++) {
+        const uint32_t j = j0 + u * kHThreads;
+        if (j < nvec)
+            v[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_a1*>(p + head + 16 * (size_t)j));
+    }
+#pragma unroll
+    for (int u = 0; u < kApplyVec; u++) {
+        const uint32_t j = j0 + u * kHThreads;
+        if (j < nvec) {
+            const u32x4 o = {lut_dword(sl, v[u].x), lut_dword(sl, v[u].y), lut_dword(sl, v[u].z), lut_dword(sl, v[u].w)};
+            __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(q + head) + j);
+        }
+    }
+    if (tile == 0) {
+        if ((uint32_t)tid < head)
+            q[tid] = sl[p[tid]];
+        else if (tid >= 16 && tid < 32 && body_end + (uint32_t)(tid - 16) < npx)
+            q[body_end + (tid - 16)] = sl[p[body_end + (tid - 16)]];
+    }
+}
+
+// blocks of one frame for `per_block` 16-byte vectors per block, and the whole grid; false if it is too large
+bool grid_of(int w, int h, int nframes, int per_block, uint32_t* tiles, uint32_t* blocks)
+{
+    const uint64_t npx = (uint64_t)w * (uint64_t)h;
+    if (w <= 0 || h <= 0 || nframes <= 0 || npx >= (1ull << 31))
+        return false;
+    const uint64_t t = (npx / 16 + (uint64_t)per_block - 1) / (uint64_t)per_block;
+    const uint64_t tt = t ? t : 1;  // a frame shorter than one vector still has its head / tail block
+    if (tt * (uint64_t)nframes > 0x7FFFFFFFull)
+        return false;
+    *tiles = (uint32_t)tt;
+    *blocks = (uint32_t)(tt * (uint64_t)nframes);
+    return true;
+}
+
+}  // namespace
+
+hipError_t launch_hist(hipStream_t stream, const uint8_t* d_in, uint32_t* d_hist, int w, int h, int nframes)
+{
+    uint32_t tiles = 0, blocks = 0;
+    if (!grid_of(w, h, nframes, kHThreads * kHistVec, &tiles, &blocks))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hist_kernel, dim3(blocks), dim3(kHThreads), 0, stream, d_in, d_hist, (uint32_t)(w * h), tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_hist_table(hipStream_t stream, const uint32_t* d_hist, uint8_t* d_lut, int32_t* d_thresh, int w,
+                             int h, int nframes, bool otsu)
+{
+    if (w <= 0 || h <= 0 || nframes <= 0 || (uint64_t)w * (uint64_t)h >= (1ull << 31))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(table_kernel, dim3((unsigned)nframes), dim3(kWave), 0, stream, d_hist, d_lut, d_thresh,
+                       (uint32_t)(w * h), otsu ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_lut_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, const uint8_t* d_lut, int w, int h,
+                            int nframes)
+{
+    uint32_t tiles = 0, blocks = 0;
+    if (!grid_of(w, h, nframes, kHThreads * kApplyVec, &tiles, &blocks))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(kHThreads), 0, stream, d_in, d_out, d_lut, (uint32_t)(w * h),
+                       tiles);
+    return hipGetLastError();
+}
+
+}  // namespace mi355

@@ -113,6 +113,19 @@ hipError_t launch_median(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out
 hipError_t launch_morph(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k,
                         int op, bool gray8);
 
+// whole-frame statistics of single-channel frames (hist.hip): frame f is the flat byte range [f w h, (f + 1) w h),
+// w * h < 2^31, any byte alignment.  launch_hist ADDS each frame's 256 bin counts into d_hist[f * 256 ..] (the caller
+// zeroes it first; 4-byte aligned).
+hipError_t launch_hist(hipStream_t stream, const uint8_t* d_in, uint32_t* d_hist, int w, int h, int nframes);
+// one wave per frame: the 256-byte table of cv::equalizeHist (otsu false) or of the Otsu threshold (lut[v] = v > t ?
+// 255 : 0) from 16-byte aligned histograms; d_lut (256 B per frame, 4-byte aligned) and d_thresh (Otsu's t per frame)
+// may each be null
+hipError_t launch_hist_table(hipStream_t stream, const uint32_t* d_hist, uint8_t* d_lut, int32_t* d_thresh, int w,
+                             int h, int nframes, bool otsu);
+// out byte = d_lut[f * 256 + in byte] for every pixel of frame f
+hipError_t launch_lut_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, const uint8_t* d_lut, int w, int h,
+                            int nframes);
+
 // image2d_t-mode semantics of the reference (image2d.hip): filter 0 gray / 2 gauss / 3 sobel
 hipError_t launch_image2d(hipStream_t stream, int filter, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                           int k, const float* d_table);

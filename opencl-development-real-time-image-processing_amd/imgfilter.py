@@ -29,6 +29,8 @@ MAX_MEDIAN_K = 7
 FILTER_ERODE, FILTER_DILATE, FILTER_OPEN, FILTER_CLOSE = 24, 25, 26, 27
 FILTER_ERODE_GRAY8, FILTER_DILATE_GRAY8, FILTER_OPEN_GRAY8, FILTER_CLOSE_GRAY8 = 28, 29, 30, 31
 MAX_MORPH_K = 17
+# whole-frame statistics (MI355_FILTER_EQUALIZE_GRAY8 / OTSU_GRAY8): ids 40 and 41 (32-39 unassigned), k and sigma ignored
+FILTER_EQUALIZE_GRAY8, FILTER_OTSU_GRAY8 = 40, 41
 GAUSS_FAST, GAUSS_EXACT = 0, 1
 INPUT_RGBA, INPUT_BGR = 0, 1
 IMPL_AUTO, IMPL_TILE, IMPL_MFMA, IMPL_VALU = 0, 1, 2, 3
@@ -40,7 +42,7 @@ IN_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 4, FILTER_GAUSS: 4, FILTER_SOBEL: 4, FIL
 _MORE_BPP = {FILTER_MEDIAN: (4, 4), FILTER_MEDIAN_GRAY8: (1, 1),
              FILTER_ERODE: (4, 4), FILTER_DILATE: (4, 4), FILTER_OPEN: (4, 4), FILTER_CLOSE: (4, 4),
              FILTER_ERODE_GRAY8: (1, 1), FILTER_DILATE_GRAY8: (1, 1), FILTER_OPEN_GRAY8: (1, 1),
-             FILTER_CLOSE_GRAY8: (1, 1)}
+             FILTER_CLOSE_GRAY8: (1, 1), FILTER_EQUALIZE_GRAY8: (1, 1), FILTER_OTSU_GRAY8: (1, 1)}
 
 
 def _in_bpp(filt):
@@ -131,6 +133,8 @@ def load_library(path=None):
         "mi355_sobel_rgba8_dev": [_vp, _vp, _vp, _ci, _ci, _ci],
         "mi355_pipeline_rgba8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, ctypes.c_float],
         "mi355_filter_dev": [_vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, ctypes.c_float],
+        "mi355_hist_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci],
+        "mi355_otsu_thresholds_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci],
         "mi355_synth_rgba8_dev": [_vp, _vp, _ci, _ci, _ci, _ci, ctypes.c_uint32, _ci],
         "mi355_checksum_dev": [_vp, _vp, ctypes.c_size_t, ctypes.c_uint64, _u64p],
         "mi355_stream_copy_dev": [_vp, _vp, _vp, ctypes.c_size_t],
@@ -386,6 +390,49 @@ class Context:
         """MORPH_CLOSE of single-channel frames (MI355_FILTER_CLOSE_GRAY8)."""
         return self._host_gray8(FILTER_CLOSE_GRAY8, y, k)
 
+    def equalize_hist_gray8(self, y):
+        """cv::equalizeHist of (h, w) / (n, h, w) single-channel frames, each frame on its own
+        (MI355_FILTER_EQUALIZE_GRAY8)."""
+        return self._host_gray8(FILTER_EQUALIZE_GRAY8, y)
+
+    def otsu_gray8(self, y):
+        """cv::threshold(THRESH_BINARY | THRESH_OTSU) to 0 / 255 of single-channel frames (MI355_FILTER_OTSU_GRAY8)."""
+        return self._host_gray8(FILTER_OTSU_GRAY8, y)
+
+    def _stats_gray8(self, fn, y, per_frame, dtype):
+        y = np.ascontiguousarray(y, np.uint8)
+        if y.ndim not in (2, 3):
+            raise Mi355Error(fn, -1, "expected (h, w) or (n, h, w) uint8")
+        frames = y[None] if y.ndim == 2 else y
+        n, h, w = frames.shape
+        out = np.empty((n, per_frame), dtype)
+        d_in = self.alloc(frames.nbytes)
+        try:
+            d_out = self.alloc(out.nbytes)
+            try:
+                self.h2d(d_in, frames)
+                rc = getattr(self._lib, fn)(self._h, _vp(d_in), _vp(d_out), w, h, n)
+                _check(fn, rc, self._h)
+                self.sync()
+                self.d2h(out, d_out)
+            finally:
+                self.sync()
+                self.free(d_out)
+        finally:
+            self.free(d_in)
+        return out[0] if y.ndim == 2 else out
+
+    def hist_gray8(self, y):
+        """The 256 bin counts of each single-channel frame (cv::calcHist), through mi355_hist_gray8_dev: (n, 256)
+        uint32 for (n, h, w) frames, (256,) for one (h, w) frame."""
+        return self._stats_gray8("mi355_hist_gray8_dev", y, 256, np.uint32)
+
+    def otsu_thresholds_gray8(self, y):
+        """The Otsu threshold t of each single-channel frame (what cv::threshold returns), through
+        mi355_otsu_thresholds_gray8_dev: (n,) int32 for (n, h, w) frames, a 0-d array for one (h, w) frame."""
+        out = self._stats_gray8("mi355_otsu_thresholds_gray8_dev", y, 1, np.int32)
+        return out[..., 0]
+
     def image2d(self, filt, rgba, k=0, sigma=0.0):
         """mi355_image2d_rgba8: the reference's image2d_t-mode semantics.  Returns (out, six timestamps)."""
         rgba = np.ascontiguousarray(rgba, np.uint8)
@@ -445,6 +492,17 @@ class Context:
         rc = self._lib.mi355_filter_dev(self._h, int(filt), _vp(int(d_in)), _vp(int(d_out)), int(w), int(h),
                                         int(nframes), int(k), float(sigma))
         _check("mi355_filter_dev", rc, self._h)
+
+    def hist_gray8_dev(self, d_in, d_hist, w, h, nframes):
+        """mi355_hist_gray8_dev: nframes x 256 uint32 counts to d_hist (overwritten), no synchronisation."""
+        rc = self._lib.mi355_hist_gray8_dev(self._h, _vp(int(d_in)), _vp(int(d_hist)), int(w), int(h), int(nframes))
+        _check("mi355_hist_gray8_dev", rc, self._h)
+
+    def otsu_thresholds_gray8_dev(self, d_in, d_thresh, w, h, nframes):
+        """mi355_otsu_thresholds_gray8_dev: one int32 Otsu threshold per frame to d_thresh, no synchronisation."""
+        rc = self._lib.mi355_otsu_thresholds_gray8_dev(self._h, _vp(int(d_in)), _vp(int(d_thresh)), int(w), int(h),
+                                                       int(nframes))
+        _check("mi355_otsu_thresholds_gray8_dev", rc, self._h)
 
     def synth_dev(self, d_out, w, h, nframes, first_frame=0, seed=0x5EED, mode=0):
         rc = self._lib.mi355_synth_rgba8_dev(self._h, _vp(int(d_out)), int(w), int(h), int(nframes),
