@@ -35,6 +35,12 @@ struct CoefEntry {
 constexpr size_t kMaxCoefEntries = 16;
 constexpr size_t kMaxInstalledCoefs = 64;
 
+// a pooled device buffer of the context: freed by mi355_ctx_destroy, grown by ensure() / ensure_slots()
+struct DevBuf {
+    void* p;
+    size_t cap;
+};
+
 }  // namespace
 
 struct mi355_ctx {
@@ -43,30 +49,19 @@ struct mi355_ctx {
     bool own_stream = false;
     hipEvent_t ev[6] = {};
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    void* d_in = nullptr;
-    size_t d_in_cap = 0;
-    void* d_out = nullptr;
-    size_t d_out_cap = 0;
+    DevBuf d_in = {}, d_out = {};
+    DevBuf d_raw = {};    // BGR staging of the host-buffer calls
+    DevBuf d_flags = {};  // per-work-item flags of the two-kernel Gaussian (gauss_wide.hip)
+    DevBuf d_hist = {};   // per-frame 256-bin histograms of EQUALIZE_GRAY8 / OTSU_GRAY8 (hist.hip)
+    DevBuf d_lut = {};    // their per-frame 256-byte tables
     unsigned long long* d_acc = nullptr;
     float* d_img_table = nullptr;  // image2d-mode Gaussian table (k*k floats, MI355_MAX_GAUSS_K^2 capacity)
-    void* d_flags = nullptr;  // per-work-item flags of the two-kernel Gaussian (gauss_wide.hip), pooled
-    size_t d_flags_cap = 0;
-    void* d_hist = nullptr;  // per-frame 256-bin histograms of EQUALIZE_GRAY8 / OTSU_GRAY8 (hist.hip), pooled
-    size_t d_hist_cap = 0;
-    void* d_lut = nullptr;  // their per-frame 256-byte tables, pooled
-    size_t d_lut_cap = 0;
     // streamed path: copy streams, per-slot events and device slots (created on first use)
     static constexpr int kSlots = 3;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     hipEvent_t ev_h2d[kSlots] = {}, ev_k[kSlots] = {}, ev_d2h[kSlots] = {};
-    void* slot_in[kSlots] = {};
-    void* slot_out[kSlots] = {};
-    size_t slot_in_cap = 0, slot_out_cap = 0;
+    DevBuf slot_in[kSlots] = {}, slot_out[kSlots] = {}, slot_raw[kSlots] = {};
     int input_format = MI355_INPUT_RGBA;
-    void* d_raw = nullptr;  // BGR staging of the host-buffer calls
-    size_t d_raw_cap = 0;
-    void* slot_raw[3] = {};
-    size_t slot_raw_cap = 0;
     int gauss_mode = MI355_GAUSS_FAST;
     int impl = MI355_IMPL_AUTO;
     int last_hip = 0;
@@ -268,77 +263,126 @@ int get_coef(mi355_ctx* ctx, int k, float sigma, const GaussCoef** out)
     return install_coef(ctx, k, sigma, w.data(), false, out);
 }
 
-int ensure(mi355_ctx* ctx, void** p, size_t* cap, size_t need)
+int ensure(mi355_ctx* ctx, DevBuf& b, size_t need)
 {
-    if (*cap >= need)
+    if (b.cap >= need)
         return MI355_OK;
-    if (*p) {
+    if (b.p) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
+        HIP_TRY(ctx, hipFree(b.p));
+        b = {};
     }
     // grow geometrically so a stream of slightly different frame sizes does not reallocate each time
     size_t want = need + need / 4;
-    hipError_t e = hipMalloc(p, want);
+    hipError_t e = hipMalloc(&b.p, want);
     if (e != hipSuccess) {
-        e = hipMalloc(p, need);
+        e = hipMalloc(&b.p, need);
         want = need;
     }
     if (e != hipSuccess) {
         ctx->last_hip = (int)e;
-        *p = nullptr;
+        b.p = nullptr;
         return MI355_ERR_NOMEM;
     }
-    *cap = want;
+    b.cap = want;
     return MI355_OK;
 }
 
-bool filter_needs_gauss(int f)
+// the streamed path's slots: exactly `need` bytes each.  A slot may still be in use on any of the path's three
+// streams, so growing them waits for the whole device first.
+int ensure_slots(mi355_ctx* ctx, DevBuf (&slots)[mi355_ctx::kSlots], size_t need)
 {
-    return f == MI355_FILTER_GAUSS || f == MI355_FILTER_PIPELINE || f == MI355_FILTER_GAUSS_GRAY8 ||
-           f == MI355_FILTER_PIPELINE_GRAY8;
+    if (slots[0].cap >= need)
+        return MI355_OK;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    for (DevBuf& b : slots) {
+        if (b.p)
+            (void)hipFree(b.p);
+        b = {};
+    }
+    for (DevBuf& b : slots)
+        if (hipMalloc(&b.p, need) != hipSuccess)
+            return MI355_ERR_NOMEM;  // the caps stay 0: the next call starts over
+    for (DevBuf& b : slots)
+        b.cap = need;
+    return MI355_OK;
 }
 
-bool filter_is_median(int f) { return f == MI355_FILTER_MEDIAN || f == MI355_FILTER_MEDIAN_GRAY8; }
+// What a filter call's k and sigma must be: ignored; the Gaussian's odd 1 <= k <= MI355_MAX_GAUSS_K with a finite
+// sigma > 0; the median's odd 3 <= k <= MI355_MAX_MEDIAN_K; the morphology's odd 3 <= k <= MI355_MAX_MORPH_K.
+enum class KRule { none, gauss, median, morph };
 
-bool valid_median_k(int k) { return k >= 3 && k <= MI355_MAX_MEDIAN_K && (k & 1) == 1; }
+struct FilterInfo {
+    int id;
+    int in_bpp, out_bpp;  // bytes per pixel the kernel reads / writes
+    KRule k;
+    bool table;     // needs the (k, sigma) coefficient table
+    bool below_2g;  // frames of 2^31 pixels or more are rejected (OpenCV counts a frame's pixels in an int)
+};
 
-bool filter_is_morph(int f) { return f >= MI355_FILTER_ERODE && f <= MI355_FILTER_CLOSE_GRAY8; }
+// every filter id of include/mi355_imgfilter.h; dispatch_dev's switch maps each one to its launcher
+constexpr FilterInfo kFilters[] = {
+    {MI355_FILTER_GRAY, 4, 4, KRule::none, false, false},
+    {MI355_FILTER_GRAY1, 4, 1, KRule::none, false, false},
+    {MI355_FILTER_GAUSS, 4, 4, KRule::gauss, true, false},
+    {MI355_FILTER_SOBEL, 4, 1, KRule::none, false, false},
+    {MI355_FILTER_PIPELINE, 4, 1, KRule::gauss, true, false},
+    {MI355_FILTER_GAUSS_GRAY8, 1, 1, KRule::gauss, true, false},
+    {MI355_FILTER_SOBEL_GRAY8, 1, 1, KRule::none, false, false},
+    {MI355_FILTER_PIPELINE_GRAY8, 1, 1, KRule::gauss, true, false},
+    {MI355_FILTER_MEDIAN, 4, 4, KRule::median, false, false},
+    {MI355_FILTER_MEDIAN_GRAY8, 1, 1, KRule::median, false, false},
+    {MI355_FILTER_ERODE, 4, 4, KRule::morph, false, false},
+    {MI355_FILTER_DILATE, 4, 4, KRule::morph, false, false},
+    {MI355_FILTER_OPEN, 4, 4, KRule::morph, false, false},
+    {MI355_FILTER_CLOSE, 4, 4, KRule::morph, false, false},
+    {MI355_FILTER_ERODE_GRAY8, 1, 1, KRule::morph, false, false},
+    {MI355_FILTER_DILATE_GRAY8, 1, 1, KRule::morph, false, false},
+    {MI355_FILTER_OPEN_GRAY8, 1, 1, KRule::morph, false, false},
+    {MI355_FILTER_CLOSE_GRAY8, 1, 1, KRule::morph, false, false},
+    {MI355_FILTER_EQUALIZE_GRAY8, 1, 1, KRule::none, false, true},
+    {MI355_FILTER_OTSU_GRAY8, 1, 1, KRule::none, false, true},
+};
 
-bool valid_morph_k(int k) { return k >= 3 && k <= MI355_MAX_MORPH_K && (k & 1) == 1; }
-
-// the (k, sigma) of a call are acceptable for this filter: Gaussian filters take an odd k <= MI355_MAX_GAUSS_K and a
-// valid sigma, the median an odd 3 <= k <= MI355_MAX_MEDIAN_K, the morphology ids an odd 3 <= k <= MI355_MAX_MORPH_K
-// (sigma ignored), the others ignore both
-bool valid_filter_k(int f, int k, float sigma)
+const FilterInfo* filter_info(int filter)
 {
-    if (filter_needs_gauss(f))
-        return valid_k(k) && valid_sigma(sigma);
-    if (filter_is_median(f))
-        return valid_median_k(k);
-    if (filter_is_morph(f))
-        return valid_morph_k(k);
-    return true;
+    for (const FilterInfo& f : kFilters)
+        if (f.id == filter)
+            return &f;
+    return nullptr;
 }
 
-bool filter_is_hist(int f) { return f == MI355_FILTER_EQUALIZE_GRAY8 || f == MI355_FILTER_OTSU_GRAY8; }
+bool odd_in(int k, int lo, int hi) { return k >= lo && k <= hi && (k & 1) == 1; }
 
-// the histogram ids take frames below 2^31 pixels (OpenCV counts a frame's pixels in an int)
-bool valid_frame_size(int f, int w, int h) { return !filter_is_hist(f) || (int64_t)w * (int64_t)h < (1ll << 31); }
-
-// the single-channel filters take 1-byte pixels: any byte alignment, and no BGR ingest
-bool filter_is_gray8(int f) { return mi355_filter_in_bpp(f) == 1; }
-
-int check_frames(const void* in, const void* out, int w, int h, int nframes)
+bool valid_sizes(int w, int h, int nframes)
 {
-    if (!in || !out || w <= 0 || h <= 0 || nframes <= 0)
-        return MI355_ERR_BAD_ARG;
     // 2^31 tiles / 2^40 bytes is far beyond 288 GB of HBM; reject before any size_t arithmetic wraps
-    const double px = (double)w * (double)h * (double)nframes;
-    if (px > 6.0e10)
+    return w > 0 && h > 0 && nframes > 0 && (double)w * (double)h * (double)nframes <= 6.0e10;
+}
+
+// The value checks of every filter call (the callers check their own context and pointers first): a known id and
+// sizes, then the id's k / sigma / frame-size rule.  All of them come before any HIP call.
+int check_filter(int filter, int w, int h, int nframes, int k, float sigma, const FilterInfo** row)
+{
+    const FilterInfo* f = filter_info(filter);
+    if (!f || !valid_sizes(w, h, nframes))
         return MI355_ERR_BAD_ARG;
+    const bool k_ok = f->k == KRule::gauss    ? valid_k(k) && valid_sigma(sigma)
+                      : f->k == KRule::median ? odd_in(k, 3, MI355_MAX_MEDIAN_K)
+                      : f->k == KRule::morph  ? odd_in(k, 3, MI355_MAX_MORPH_K)
+                                              : true;
+    if (!k_ok || (f->below_2g && (int64_t)w * (int64_t)h >= (1ll << 31)))
+        return MI355_ERR_BAD_ARG;
+    if (row)
+        *row = f;
     return MI355_OK;
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+bool overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
 }
 
 // EQUALIZE_GRAY8 / OTSU_GRAY8 up to the table: the pooled histograms, zeroed in-stream, the histogram launch and the
@@ -346,56 +390,40 @@ int check_frames(const void* in, const void* out, int w, int h, int nframes)
 // for a larger frame count allocates (and synchronises, in ensure()).
 int hist_tables(mi355_ctx* ctx, const uint8_t* in, int32_t* d_thresh, int w, int h, int nframes, bool otsu)
 {
-    int rc = ensure(ctx, &ctx->d_hist, &ctx->d_hist_cap, (size_t)nframes * 256 * sizeof(uint32_t));
+    int rc = ensure(ctx, ctx->d_hist, (size_t)nframes * 256 * sizeof(uint32_t));
     if (rc == MI355_OK)
-        rc = ensure(ctx, &ctx->d_lut, &ctx->d_lut_cap, (size_t)nframes * 256);
+        rc = ensure(ctx, ctx->d_lut, (size_t)nframes * 256);
     if (rc != MI355_OK)
         return rc;
-    uint32_t* hist = static_cast<uint32_t*>(ctx->d_hist);
+    uint32_t* hist = static_cast<uint32_t*>(ctx->d_hist.p);
     HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)nframes * 256 * sizeof(uint32_t), ctx->stream));
     HIP_TRY(ctx, launch_hist(ctx->stream, in, hist, w, h, nframes));
-    HIP_TRY(ctx, launch_hist_table(ctx->stream, hist, static_cast<uint8_t*>(ctx->d_lut), d_thresh, w, h, nframes, otsu));
+    HIP_TRY(ctx, launch_hist_table(ctx->stream, hist, static_cast<uint8_t*>(ctx->d_lut.p), d_thresh, w, h, nframes,
+                                   otsu));
     return MI355_OK;
 }
 
 int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int w, int h, int nframes,
                  int k, float sigma)
 {
-    if (!ctx)
+    if (!ctx || !d_in || !d_out)
         return MI355_ERR_BAD_ARG;
-    int rc = check_frames(d_in, d_out, w, h, nframes);
+    const FilterInfo* f = nullptr;
+    int rc = check_filter(filter, w, h, nframes, k, sigma, &f);
     if (rc != MI355_OK)
         return rc;
-    const int in_bpp = mi355_filter_in_bpp(filter);
-    if (in_bpp < 0)
-        return MI355_ERR_BAD_ARG;
-    if (in_bpp == 4 && (reinterpret_cast<uintptr_t>(d_in) & 3u))
-        return MI355_ERR_BAD_ARG;  // RGBA pixels are accessed as dwords
-    const bool rgba_out = mi355_filter_out_bpp(filter) == 4;
-    if (rgba_out && (reinterpret_cast<uintptr_t>(d_out) & 3u))
-        return MI355_ERR_BAD_ARG;
-    {
-        // the stencil kernels read neighbouring rows / halo pixels of what another wave may already have overwritten,
-        // and the (pointwise) grayscale kernels are compiled for non-aliasing pointers (__restrict__, non-temporal
-        // accesses): in-place and overlapping calls are rejected, not run, for every filter (the reference never
-        // aliases them either: two clCreateBuffer objects per call, RT/src/Controller.cpp:234-244)
-        const int bpp = mi355_filter_out_bpp(filter);
-        if (bpp < 0)
-            return MI355_ERR_BAD_ARG;
-        const size_t npx = (size_t)w * h * nframes;
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_in), a1 = a0 + npx * (size_t)in_bpp;
-        const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + npx * (size_t)bpp;
-        if (a0 < b1 && b0 < a1)
-            return MI355_ERR_BAD_ARG;
-    }
-    if ((filter_is_median(filter) && !valid_median_k(k)) || (filter_is_morph(filter) && !valid_morph_k(k)) ||
-        !valid_frame_size(filter, w, h))
+    // RGBA pixels are accessed as dwords.  The stencil kernels read neighbouring rows / halo pixels of what another
+    // wave may already have overwritten, and the (pointwise) grayscale kernels are compiled for non-aliasing pointers
+    // (__restrict__, non-temporal accesses): in-place and overlapping calls are rejected, not run, for every filter
+    // (the reference never aliases them either: two clCreateBuffer objects per call, RT/src/Controller.cpp:234-244)
+    const size_t npx = (size_t)w * h * nframes;
+    if ((f->in_bpp == 4 && (reinterpret_cast<uintptr_t>(d_in) & 3u)) ||
+        (f->out_bpp == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u)) ||
+        overlap(d_in, npx * (size_t)f->in_bpp, d_out, npx * (size_t)f->out_bpp))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const GaussCoef* coef = nullptr;
-    if (filter_needs_gauss(filter)) {
-        if (!valid_k(k) || !valid_sigma(sigma))
-            return MI355_ERR_BAD_ARG;
+    if (f->table) {
         rc = get_coef(ctx, k, sigma, &coef);
         if (rc != MI355_OK)
             return rc;
@@ -415,12 +443,12 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
     case MI355_FILTER_GAUSS: {
         const size_t nflags = gauss_flag_items(in, out, w, h, nframes, *coef, exact, ctx->impl);
         if (nflags) {
-            rc = ensure(ctx, &ctx->d_flags, &ctx->d_flags_cap, nflags * sizeof(uint32_t));
+            rc = ensure(ctx, ctx->d_flags, nflags * sizeof(uint32_t));
             if (rc != MI355_OK)
                 return rc;
         }
         e = launch_gauss(ctx->stream, in, out, w, h, nframes, *coef, exact, ctx->impl,
-                         static_cast<uint32_t*>(ctx->d_flags));
+                         static_cast<uint32_t*>(ctx->d_flags.p));
         break;
     }
     case MI355_FILTER_SOBEL:
@@ -459,7 +487,7 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
         rc = hist_tables(ctx, in, nullptr, w, h, nframes, filter == MI355_FILTER_OTSU_GRAY8);
         if (rc != MI355_OK)
             return rc;
-        e = launch_lut_apply(ctx->stream, in, out, static_cast<const uint8_t*>(ctx->d_lut), w, h, nframes);
+        e = launch_lut_apply(ctx->stream, in, out, static_cast<const uint8_t*>(ctx->d_lut.p), w, h, nframes);
         break;
     default:
         return MI355_ERR_BAD_ARG;
@@ -486,72 +514,70 @@ int fill_prof(mi355_ctx* ctx, uint64_t host0, uint64_t prof_ns[6])
     return MI355_OK;
 }
 
-// H2D, kernel, D2H with the reference's six profiling timestamps (RT/src/Controller.cpp:66-74)
-int run_host(mi355_ctx* ctx, int filter, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
-             int k, float sigma, uint64_t prof_ns[6])
+// The timed part of a host-buffer call: H2D of `in_bytes` from `in` to `d_dst`, launch(), D2H of `out_bytes` from
+// ctx->d_out to `out`, synchronised, with the reference's six profiling timestamps (RT/src/Controller.cpp:66-74).
+// Four events on the in-order stream give the six timestamps: write-end IS kernel-start and kernel-end IS read-start
+// (round 2 recorded six events and made five elapsed-time queries per call; at 75 x 75 the API calls around the three
+// operations were a third of the call).  No events at all when the caller wants no timestamps.
+template <class Launch>
+int timed_roundtrip(mi355_ctx* ctx, void* d_dst, const void* in, size_t in_bytes, uint8_t* out, size_t out_bytes,
+                    uint64_t prof_ns[6], Launch launch)
 {
-    if (!ctx)
-        return MI355_ERR_BAD_ARG;
-    const int bpp = mi355_filter_out_bpp(filter);
-    if (bpp < 0)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_frames(in, out, w, h, nframes);
-    if (rc != MI355_OK)
-        return rc;
-    if (!valid_filter_k(filter, k, sigma) || !valid_frame_size(filter, w, h))
-        return MI355_ERR_BAD_ARG;
-    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    if (bgr && filter_is_gray8(filter))
-        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)w * h * nframes;
-    const size_t in_bytes = npx * (size_t)mi355_filter_in_bpp(filter), out_bytes = npx * (size_t)bpp;
-    rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, in_bytes);
-    if (rc != MI355_OK)
-        return rc;
-    if (bgr) {
-        rc = ensure(ctx, &ctx->d_raw, &ctx->d_raw_cap, npx * 3);
-        if (rc != MI355_OK)
-            return rc;
-    }
-    rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, out_bytes);
-    if (rc != MI355_OK)
-        return rc;
-    if (filter_needs_gauss(filter)) {
-        // build/upload the coefficient table outside the timed write/kernel/read window
-        const GaussCoef* coef = nullptr;
-        rc = get_coef(ctx, k, sigma, &coef);
-        if (rc != MI355_OK)
-            return rc;
-    }
-    // Four events on the in-order stream give the six timestamps: write-end IS kernel-start and kernel-end IS
-    // read-start (round 2 recorded six events and made five elapsed-time queries per call; at 75 x 75 the API calls
-    // around the three operations were a third of the call).  No events at all when the caller wants no timestamps.
     hipStream_t s = ctx->stream;
     const uint64_t host0 = now_ns();
     if (prof_ns)
         HIP_TRY(ctx, hipEventRecord(ctx->ev[0], s));
-    if (bgr) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_raw, in, npx * 3, hipMemcpyHostToDevice, s));
-    } else {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_in, in, in_bytes, hipMemcpyHostToDevice, s));
-    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_dst, in, in_bytes, hipMemcpyHostToDevice, s));
     if (prof_ns)
         HIP_TRY(ctx, hipEventRecord(ctx->ev[1], s));
-    if (bgr)  // the BGR2RGBA expansion counts as kernel time
-        HIP_TRY(ctx, launch_bgr_to_rgba(s, static_cast<const uint8_t*>(ctx->d_raw), static_cast<uint8_t*>(ctx->d_in), npx));
-    rc = dispatch_dev(ctx, filter, ctx->d_in, ctx->d_out, w, h, nframes, k, sigma);
+    const int rc = launch();
     if (rc != MI355_OK)
         return rc;
     if (prof_ns)
         HIP_TRY(ctx, hipEventRecord(ctx->ev[3], s));
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
     if (prof_ns)
         HIP_TRY(ctx, hipEventRecord(ctx->ev[5], s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     if (prof_ns)
         return fill_prof(ctx, host0, prof_ns);
     return MI355_OK;
+}
+
+// H2D, kernel, D2H through the context's pooled buffers
+int run_host(mi355_ctx* ctx, int filter, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
+             int k, float sigma, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    const FilterInfo* f = nullptr;
+    int rc = check_filter(filter, w, h, nframes, k, sigma, &f);
+    if (rc != MI355_OK)
+        return rc;
+    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
+    if (bgr && f->in_bpp == 1)
+        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t npx = (size_t)w * h * nframes;
+    const size_t in_bytes = npx * (size_t)f->in_bpp, out_bytes = npx * (size_t)f->out_bpp;
+    rc = ensure(ctx, ctx->d_in, in_bytes);
+    if (rc == MI355_OK && bgr)
+        rc = ensure(ctx, ctx->d_raw, npx * 3);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, out_bytes);
+    const GaussCoef* coef = nullptr;
+    if (rc == MI355_OK && f->table)
+        rc = get_coef(ctx, k, sigma, &coef);  // built / uploaded outside the timed write/kernel/read window
+    if (rc != MI355_OK)
+        return rc;
+    auto launch = [&] {
+        if (bgr)  // the BGR2RGBA expansion counts as kernel time
+            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
+                                            static_cast<uint8_t*>(ctx->d_in.p), npx));
+        return dispatch_dev(ctx, filter, ctx->d_in.p, ctx->d_out.p, w, h, nframes, k, sigma);
+    };
+    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? npx * 3 : in_bytes, out, out_bytes, prof_ns,
+                           launch);
 }
 
 int create_common(int device, hipStream_t stream, bool own, mi355_ctx** out)
@@ -628,48 +654,24 @@ MI355_API int mi355_ctx_destroy(mi355_ctx* ctx)
         (void)hipFree(e.d_buf);
     for (void* p : ctx->pinned)
         (void)hipHostFree(p);
-    if (ctx->d_in)
-        (void)hipFree(ctx->d_in);
-    if (ctx->d_raw)
-        (void)hipFree(ctx->d_raw);
-    for (void* p : ctx->slot_raw)
+    for (void* p : {(void*)ctx->d_acc, (void*)ctx->d_img_table, ctx->d_in.p, ctx->d_out.p, ctx->d_raw.p, ctx->d_flags.p,
+                    ctx->d_hist.p, ctx->d_lut.p})
         if (p)
             (void)hipFree(p);
-    if (ctx->d_out)
-        (void)hipFree(ctx->d_out);
-    if (ctx->d_acc)
-        (void)hipFree(ctx->d_acc);
-    if (ctx->d_flags)
-        (void)hipFree(ctx->d_flags);
-    if (ctx->d_hist)
-        (void)hipFree(ctx->d_hist);
-    if (ctx->d_lut)
-        (void)hipFree(ctx->d_lut);
-    if (ctx->d_img_table)
-        (void)hipFree(ctx->d_img_table);
     for (int i = 0; i < mi355_ctx::kSlots; i++) {
-        if (ctx->slot_in[i])
-            (void)hipFree(ctx->slot_in[i]);
-        if (ctx->slot_out[i])
-            (void)hipFree(ctx->slot_out[i]);
-        if (ctx->ev_h2d[i])
-            (void)hipEventDestroy(ctx->ev_h2d[i]);
-        if (ctx->ev_k[i])
-            (void)hipEventDestroy(ctx->ev_k[i]);
-        if (ctx->ev_d2h[i])
-            (void)hipEventDestroy(ctx->ev_d2h[i]);
+        for (void* p : {ctx->slot_in[i].p, ctx->slot_out[i].p, ctx->slot_raw[i].p})
+            if (p)
+                (void)hipFree(p);
+        for (hipEvent_t ev : {ctx->ev_h2d[i], ctx->ev_k[i], ctx->ev_d2h[i]})
+            if (ev)
+                (void)hipEventDestroy(ev);
     }
-    if (ctx->s_h2d)
-        (void)hipStreamDestroy(ctx->s_h2d);
-    if (ctx->s_d2h)
-        (void)hipStreamDestroy(ctx->s_d2h);
-    for (auto& ev : ctx->ev)
+    for (hipStream_t s : {ctx->s_h2d, ctx->s_d2h})
+        if (s)
+            (void)hipStreamDestroy(s);
+    for (hipEvent_t ev : {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->ev[4], ctx->ev[5], ctx->t0, ctx->t1})
         if (ev)
             (void)hipEventDestroy(ev);
-    if (ctx->t0)
-        (void)hipEventDestroy(ctx->t0);
-    if (ctx->t1)
-        (void)hipEventDestroy(ctx->t1);
     if (ctx->own_stream && ctx->stream)
         (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -734,12 +736,7 @@ MI355_API int mi355_ctx_set_input_format(mi355_ctx* ctx, int format)
 
 MI355_API int mi355_bgr_to_rgba8_dev(mi355_ctx* ctx, const void* d_bgr, void* d_rgba, int w, int h, int nframes)
 {
-    if (!ctx)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_frames(d_bgr, d_rgba, w, h, nframes);
-    if (rc != MI355_OK)
-        return rc;
-    if (reinterpret_cast<uintptr_t>(d_rgba) & 3u)
+    if (!ctx || !d_bgr || !d_rgba || !valid_sizes(w, h, nframes) || (reinterpret_cast<uintptr_t>(d_rgba) & 3u))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(d_bgr), static_cast<uint8_t*>(d_rgba),
@@ -766,20 +763,17 @@ MI355_API int mi355_gauss_weights_image2d(int k, float sigma, float* out_k2)
 MI355_API int mi355_image2d_rgba8(mi355_ctx* ctx, int filter, const uint8_t* rgba, uint8_t* out, int w, int h, int k,
                                   float sigma, uint64_t prof_ns[6])
 {
-    if (!ctx || (filter != MI355_FILTER_GRAY && filter != MI355_FILTER_GAUSS && filter != MI355_FILTER_SOBEL))
+    if (!ctx || !rgba || !out || !valid_sizes(w, h, 1) ||
+        (filter != MI355_FILTER_GRAY && filter != MI355_FILTER_GAUSS && filter != MI355_FILTER_SOBEL))
         return MI355_ERR_BAD_ARG;
-    int rc = check_frames(rgba, out, w, h, 1);
-    if (rc != MI355_OK)
-        return rc;
     const bool gauss = filter == MI355_FILTER_GAUSS;
     if (gauss && (!valid_k(k) || !valid_sigma(sigma)))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t npx = (size_t)w * h, in_bytes = npx * 4, out_bytes = npx * (gauss ? 4 : 1);
-    rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, in_bytes);
-    if (rc != MI355_OK)
-        return rc;
-    rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, out_bytes);
+    int rc = ensure(ctx, ctx->d_in, in_bytes);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, out_bytes);
     if (rc != MI355_OK)
         return rc;
     if (gauss) {
@@ -790,24 +784,11 @@ MI355_API int mi355_image2d_rgba8(mi355_ctx* ctx, int filter, const uint8_t* rgb
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a kernel in flight may still read the previous table
         HIP_TRY(ctx, hipMemcpy(ctx->d_img_table, table.data(), sizeof(float) * table.size(), hipMemcpyHostToDevice));
     }
-    hipStream_t s = ctx->stream;
-    const uint64_t host0 = now_ns();
-    if (prof_ns)
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[0], s));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_in, rgba, in_bytes, hipMemcpyHostToDevice, s));
-    if (prof_ns)
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[1], s));
-    HIP_TRY(ctx, launch_image2d(s, filter, static_cast<const uint8_t*>(ctx->d_in), static_cast<uint8_t*>(ctx->d_out), w, h, 1,
-                                k, ctx->d_img_table));
-    if (prof_ns)
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[3], s));
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    if (prof_ns)
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[5], s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    if (prof_ns)
-        return fill_prof(ctx, host0, prof_ns);
-    return MI355_OK;
+    return timed_roundtrip(ctx, ctx->d_in.p, rgba, in_bytes, out, out_bytes, prof_ns, [&] {
+        HIP_TRY(ctx, launch_image2d(ctx->stream, filter, static_cast<const uint8_t*>(ctx->d_in.p),
+                                    static_cast<uint8_t*>(ctx->d_out.p), w, h, 1, k, ctx->d_img_table));
+        return MI355_OK;
+    });
 }
 
 MI355_API int mi355_ctx_set_gauss_weights(mi355_ctx* ctx, int k, float sigma, const float* w_k2)
@@ -825,56 +806,14 @@ MI355_API int mi355_ctx_set_gauss_weights(mi355_ctx* ctx, int k, float sigma, co
 
 MI355_API int mi355_filter_out_bpp(int filter)
 {
-    switch (filter) {
-    case MI355_FILTER_GRAY:
-    case MI355_FILTER_GAUSS:
-    case MI355_FILTER_MEDIAN:
-    case MI355_FILTER_ERODE:
-    case MI355_FILTER_DILATE:
-    case MI355_FILTER_OPEN:
-    case MI355_FILTER_CLOSE: return 4;
-    case MI355_FILTER_GRAY1:
-    case MI355_FILTER_SOBEL:
-    case MI355_FILTER_PIPELINE:
-    case MI355_FILTER_GAUSS_GRAY8:
-    case MI355_FILTER_SOBEL_GRAY8:
-    case MI355_FILTER_PIPELINE_GRAY8:
-    case MI355_FILTER_MEDIAN_GRAY8:
-    case MI355_FILTER_ERODE_GRAY8:
-    case MI355_FILTER_DILATE_GRAY8:
-    case MI355_FILTER_OPEN_GRAY8:
-    case MI355_FILTER_CLOSE_GRAY8:
-    case MI355_FILTER_EQUALIZE_GRAY8:
-    case MI355_FILTER_OTSU_GRAY8: return 1;
-    default: return MI355_ERR_BAD_ARG;
-    }
+    const FilterInfo* f = filter_info(filter);
+    return f ? f->out_bpp : MI355_ERR_BAD_ARG;
 }
 
 MI355_API int mi355_filter_in_bpp(int filter)
 {
-    switch (filter) {
-    case MI355_FILTER_GRAY:
-    case MI355_FILTER_GRAY1:
-    case MI355_FILTER_GAUSS:
-    case MI355_FILTER_SOBEL:
-    case MI355_FILTER_PIPELINE:
-    case MI355_FILTER_MEDIAN:
-    case MI355_FILTER_ERODE:
-    case MI355_FILTER_DILATE:
-    case MI355_FILTER_OPEN:
-    case MI355_FILTER_CLOSE: return 4;
-    case MI355_FILTER_GAUSS_GRAY8:
-    case MI355_FILTER_SOBEL_GRAY8:
-    case MI355_FILTER_PIPELINE_GRAY8:
-    case MI355_FILTER_MEDIAN_GRAY8:
-    case MI355_FILTER_ERODE_GRAY8:
-    case MI355_FILTER_DILATE_GRAY8:
-    case MI355_FILTER_OPEN_GRAY8:
-    case MI355_FILTER_CLOSE_GRAY8:
-    case MI355_FILTER_EQUALIZE_GRAY8:
-    case MI355_FILTER_OTSU_GRAY8: return 1;
-    default: return MI355_ERR_BAD_ARG;
-    }
+    const FilterInfo* f = filter_info(filter);
+    return f ? f->in_bpp : MI355_ERR_BAD_ARG;
 }
 
 MI355_API int mi355_gray_rgba8(mi355_ctx* ctx, const uint8_t* rgba, uint8_t* out, int w, int h,
@@ -946,22 +885,18 @@ MI355_API int mi355_host_free(mi355_ctx* ctx, void* h_ptr)
 MI355_API int mi355_filter_stream(mi355_ctx* ctx, int filter, const uint8_t* rgba, uint8_t* out, int w, int h,
                                   int nframes, int chunk_frames, int k, float sigma, double* elapsed_ms)
 {
-    if (!ctx)
+    if (!ctx || !rgba || !out || chunk_frames < 0)
         return MI355_ERR_BAD_ARG;
-    const int bpp = mi355_filter_out_bpp(filter);
-    if (bpp < 0 || chunk_frames < 0)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_frames(rgba, out, w, h, nframes);
+    const FilterInfo* f = nullptr;
+    int rc = check_filter(filter, w, h, nframes, k, sigma, &f);
     if (rc != MI355_OK)
         return rc;
-    if (!valid_filter_k(filter, k, sigma) || !valid_frame_size(filter, w, h))
-        return MI355_ERR_BAD_ARG;
     const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    if (bgr && filter_is_gray8(filter))
+    if (bgr && f->in_bpp == 1)
         return MI355_ERR_UNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t fpx = (size_t)w * h;
-    const size_t dev_in_bpp = (size_t)mi355_filter_in_bpp(filter);  // what the kernel reads: 4 (RGBA) or 1 (gray8)
+    const size_t fpx = (size_t)w * h, bpp = (size_t)f->out_bpp;
+    const size_t dev_in_bpp = (size_t)f->in_bpp;  // what the kernel reads: 4 (RGBA) or 1 (gray8)
     if (chunk_frames == 0) {
         // ~64 MB of input per chunk: long enough DMA transfers to run at link rate, short enough to overlap
         chunk_frames = (int)((64u << 20) / (fpx * dev_in_bpp));
@@ -981,44 +916,16 @@ MI355_API int mi355_filter_stream(mi355_ctx* ctx, int filter, const uint8_t* rgb
         }
     }
     const size_t in_bpp = bgr ? 3 : dev_in_bpp;  // what crosses PCIe
-    const size_t in_chunk = fpx * dev_in_bpp * chunk_frames, out_chunk = fpx * (size_t)bpp * chunk_frames;
-    if (bgr && ctx->slot_raw_cap < fpx * 3 * chunk_frames) {
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        for (int i = 0; i < NS; i++) {
-            if (ctx->slot_raw[i])
-                (void)hipFree(ctx->slot_raw[i]);
-            ctx->slot_raw[i] = nullptr;
-        }
-        ctx->slot_raw_cap = 0;
-        for (int i = 0; i < NS; i++)
-            if (hipMalloc(&ctx->slot_raw[i], fpx * 3 * chunk_frames) != hipSuccess)
-                return MI355_ERR_NOMEM;
-        ctx->slot_raw_cap = fpx * 3 * chunk_frames;
-    }
-    if (ctx->slot_in_cap < in_chunk || ctx->slot_out_cap < out_chunk) {
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        for (int i = 0; i < NS; i++) {
-            if (ctx->slot_in[i])
-                (void)hipFree(ctx->slot_in[i]);
-            if (ctx->slot_out[i])
-                (void)hipFree(ctx->slot_out[i]);
-            ctx->slot_in[i] = ctx->slot_out[i] = nullptr;
-        }
-        ctx->slot_in_cap = ctx->slot_out_cap = 0;
-        for (int i = 0; i < NS; i++) {
-            if (hipMalloc(&ctx->slot_in[i], in_chunk) != hipSuccess ||
-                hipMalloc(&ctx->slot_out[i], out_chunk) != hipSuccess)
-                return MI355_ERR_NOMEM;
-        }
-        ctx->slot_in_cap = in_chunk;
-        ctx->slot_out_cap = out_chunk;
-    }
-    if (filter_needs_gauss(filter)) {
-        const GaussCoef* coef = nullptr;
+    rc = bgr ? ensure_slots(ctx, ctx->slot_raw, fpx * 3 * chunk_frames) : MI355_OK;
+    if (rc == MI355_OK)
+        rc = ensure_slots(ctx, ctx->slot_in, fpx * dev_in_bpp * chunk_frames);
+    if (rc == MI355_OK)
+        rc = ensure_slots(ctx, ctx->slot_out, fpx * bpp * chunk_frames);
+    const GaussCoef* coef = nullptr;
+    if (rc == MI355_OK && f->table)
         rc = get_coef(ctx, k, sigma, &coef);
-        if (rc != MI355_OK)
-            return rc;
-    }
+    if (rc != MI355_OK)
+        return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const uint64_t t0 = now_ns();
     const int nchunks = (nframes + chunk_frames - 1) / chunk_frames;
@@ -1029,24 +936,25 @@ MI355_API int mi355_filter_stream(mi355_ctx* ctx, int filter, const uint8_t* rgb
         // input slot is free once the kernel of chunk c-NS has read it
         if (c >= NS)
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_h2d, ctx->ev_k[slot], 0));
-        HIP_TRY(ctx, hipMemcpyAsync(bgr ? ctx->slot_raw[slot] : ctx->slot_in[slot], rgba + (size_t)f0 * fpx * in_bpp,
-                                    fpx * in_bpp * nf, hipMemcpyHostToDevice, ctx->s_h2d));
+        HIP_TRY(ctx, hipMemcpyAsync(bgr ? ctx->slot_raw[slot].p : ctx->slot_in[slot].p,
+                                    rgba + (size_t)f0 * fpx * in_bpp, fpx * in_bpp * nf, hipMemcpyHostToDevice,
+                                    ctx->s_h2d));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_h2d[slot], ctx->s_h2d));
         // kernel: needs its input, and its output slot drained by the D2H of chunk c-NS
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_h2d[slot], 0));
         if (c >= NS)
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_d2h[slot], 0));
         if (bgr)
-            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->slot_raw[slot]),
-                                            static_cast<uint8_t*>(ctx->slot_in[slot]), fpx * nf));
-        rc = dispatch_dev(ctx, filter, ctx->slot_in[slot], ctx->slot_out[slot], w, h, nf, k, sigma);
+            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->slot_raw[slot].p),
+                                            static_cast<uint8_t*>(ctx->slot_in[slot].p), fpx * nf));
+        rc = dispatch_dev(ctx, filter, ctx->slot_in[slot].p, ctx->slot_out[slot].p, w, h, nf, k, sigma);
         if (rc != MI355_OK) {
             (void)hipDeviceSynchronize();
             return rc;
         }
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k[slot], ctx->stream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, ctx->ev_k[slot], 0));
-        HIP_TRY(ctx, hipMemcpyAsync(out + (size_t)f0 * fpx * bpp, ctx->slot_out[slot], fpx * (size_t)bpp * nf,
+        HIP_TRY(ctx, hipMemcpyAsync(out + (size_t)f0 * fpx * bpp, ctx->slot_out[slot].p, fpx * bpp * nf,
                                     hipMemcpyDeviceToHost, ctx->s_d2h));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_d2h[slot], ctx->s_d2h));
     }
@@ -1061,24 +969,18 @@ MI355_API int mi355_filter_stream(mi355_ctx* ctx, int filter, const uint8_t* rgb
 MI355_API int mi355_filter_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int w, int h,
                                int nframes, int k, float sigma)
 {
-    if (mi355_filter_out_bpp(filter) < 0)
-        return MI355_ERR_BAD_ARG;
     return dispatch_dev(ctx, filter, d_in, d_out, w, h, nframes, k, sigma);
 }
 
 // the argument checks of the two statistics calls: mi355_filter_dev's, with `nout` bytes of 4-byte aligned output
 static int check_stats_call(mi355_ctx* ctx, const void* d_in, const void* d_out, int w, int h, int nframes, size_t nout)
 {
-    if (!ctx)
+    if (!ctx || !d_in || !d_out)
         return MI355_ERR_BAD_ARG;
-    int rc = check_frames(d_in, d_out, w, h, nframes);
+    const int rc = check_filter(MI355_FILTER_EQUALIZE_GRAY8, w, h, nframes, 0, 0.0f, nullptr);
     if (rc != MI355_OK)
         return rc;
-    if (!valid_frame_size(MI355_FILTER_EQUALIZE_GRAY8, w, h) || (reinterpret_cast<uintptr_t>(d_out) & 3u))
-        return MI355_ERR_BAD_ARG;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_in), a1 = a0 + (size_t)w * h * nframes;
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + nout;
-    if (a0 < b1 && b0 < a1)
+    if ((reinterpret_cast<uintptr_t>(d_out) & 3u) || overlap(d_in, (size_t)w * h * nframes, d_out, nout))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return MI355_OK;
@@ -1138,12 +1040,8 @@ MI355_API int mi355_pipeline_rgba8_dev(mi355_ctx* ctx, const void* d_in, void* d
 MI355_API int mi355_synth_rgba8_dev(mi355_ctx* ctx, void* d_out, int w, int h, int nframes,
                                     int first_frame, uint32_t seed, int mode)
 {
-    if (!ctx || mode < 0 || mode > 3)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_frames(d_out, d_out, w, h, nframes);
-    if (rc != MI355_OK)
-        return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & 3u)
+    if (!ctx || !d_out || mode < 0 || mode > 3 || !valid_sizes(w, h, nframes) ||
+        (reinterpret_cast<uintptr_t>(d_out) & 3u))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_synth(ctx->stream, static_cast<uint8_t*>(d_out), w, h, nframes, first_frame, seed,
@@ -1169,10 +1067,7 @@ MI355_API int mi355_checksum_dev(mi355_ctx* ctx, const void* d_buf, size_t nbyte
 
 MI355_API int mi355_stream_copy_dev(mi355_ctx* ctx, void* d_dst, const void* d_src, size_t nbytes)
 {
-    if (!ctx || !d_dst || !d_src)
-        return MI355_ERR_BAD_ARG;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_src), b0 = reinterpret_cast<uintptr_t>(d_dst);
-    if (a0 < b0 + nbytes && b0 < a0 + nbytes)
+    if (!ctx || !d_dst || !d_src || overlap(d_src, nbytes, d_dst, nbytes))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_stream_copy(ctx->stream, static_cast<const uint8_t*>(d_src), static_cast<uint8_t*>(d_dst),
@@ -1215,23 +1110,22 @@ MI355_API int mi355_pool_alloc(mi355_ctx* ctx, int filter, int w, int h, int nfr
     if (!ctx || !d_in || !d_out)
         return MI355_ERR_BAD_ARG;
     *d_in = *d_out = nullptr;
-    const int bpp = mi355_filter_out_bpp(filter);
-    if (bpp < 0 || w <= 0 || h <= 0 || nframes <= 0 || (double)w * h * nframes > 6.0e10)
-        return MI355_ERR_BAD_ARG;
-    if (!valid_filter_k(filter, k, sigma) || !valid_frame_size(filter, w, h))
-        return MI355_ERR_BAD_ARG;
+    const FilterInfo* f = nullptr;
+    int rc = check_filter(filter, w, h, nframes, k, sigma, &f);
+    if (rc != MI355_OK)
+        return rc;
     constexpr int kMaxCand = 16;
     for (int i = 0; probe_ms && i < tries; i++)
         probe_ms[i] = -1.0f;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)w * h * nframes, in_bytes = npx * (size_t)mi355_filter_in_bpp(filter),
-                 out_bytes = npx * (size_t)bpp;
+    const size_t npx = (size_t)w * h * nframes;
+    const size_t in_bytes = npx * (size_t)f->in_bpp, out_bytes = npx * (size_t)f->out_bpp;
     void* in = nullptr;
     if (hipMalloc(&in, in_bytes) != hipSuccess)
         return MI355_ERR_NOMEM;
     // defined, opaque input (A = 255): the placement probe then times the path real frames take
     hipError_t e = hipMemsetAsync(in, 0xFF, in_bytes, ctx->stream);
-    int rc = (e == hipSuccess) ? MI355_OK : MI355_ERR_HIP;
+    rc = (e == hipSuccess) ? MI355_OK : MI355_ERR_HIP;
     if (e != hipSuccess)
         ctx->last_hip = (int)e;
 
@@ -1374,6 +1268,17 @@ int mi355_internal_install_generated(mi355_ctx* ctx, int k, float sigma, const f
         if (e.k == k && e.sigma_bits == fbits(sigma))
             return MI355_OK;  // already there (generated or installed by the caller: the caller's table wins)
     return install_coef(ctx, k, sigma, w_k2, false, nullptr);
+}
+
+// group.hip checks a call's filter id, frame size, k and sigma through this (hidden) hook before it posts any work:
+// check_filter for one frame, and whether the call needs the (k, sigma) table
+int mi355_internal_check_filter(int filter, int w, int h, int k, float sigma, bool* needs_table)
+{
+    const FilterInfo* f = nullptr;
+    const int rc = check_filter(filter, w, h, 1, k, sigma, &f);
+    if (rc == MI355_OK)
+        *needs_table = f->table;
+    return rc;
 }
 
 extern "C" {

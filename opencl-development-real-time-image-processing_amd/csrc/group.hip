@@ -15,7 +15,9 @@
 
 #include "../../include/mi355_imgfilter.h"
 
-int mi355_internal_install_generated(mi355_ctx* ctx, int k, float sigma, const float* w_k2);  // capi.hip
+// capi.hip
+int mi355_internal_install_generated(mi355_ctx* ctx, int k, float sigma, const float* w_k2);
+int mi355_internal_check_filter(int filter, int w, int h, int k, float sigma, bool* needs_table);
 
 namespace {
 
@@ -62,24 +64,6 @@ struct Member {
     }
 };
 
-bool filter_needs_gauss(int f)
-{
-    return f == MI355_FILTER_GAUSS || f == MI355_FILTER_PIPELINE || f == MI355_FILTER_GAUSS_GRAY8 ||
-           f == MI355_FILTER_PIPELINE_GRAY8;
-}
-
-// the median and the morphology ids take an odd 3 <= k <= their maximum and no table; checked before the group
-// allocates anything
-bool table_free_k_ok(int f, int k)
-{
-    int kmax = 0;
-    if (f == MI355_FILTER_MEDIAN || f == MI355_FILTER_MEDIAN_GRAY8)
-        kmax = MI355_MAX_MEDIAN_K;
-    else if (f >= MI355_FILTER_ERODE && f <= MI355_FILTER_CLOSE_GRAY8)
-        kmax = MI355_MAX_MORPH_K;
-    return kmax == 0 || (k >= 3 && k <= kmax && (k & 1) == 1);
-}
-
 uint32_t fbits(float f)
 {
     uint32_t u;
@@ -109,14 +93,12 @@ struct mi355_group {
         return rc;
     }
 
-    // the (k, sigma) table: generated once, the same bytes installed on every member
+    // the (k, sigma) table of an accepted call: generated once, the same bytes installed on every member
     int ensure_table(int k, float sigma)
     {
         for (auto& e : keys)
             if (e.first == k && e.second == fbits(sigma))
                 return MI355_OK;
-        if (k < 1 || k > MI355_MAX_GAUSS_K || (k & 1) == 0)
-            return MI355_ERR_BAD_ARG;  // before any sizing: a garbage k must not reach the vector below
         std::vector<float> tab((size_t)k * k);
         int rc = mi355_gauss_weights(k, sigma, tab.data());
         if (rc != MI355_OK)
@@ -278,23 +260,22 @@ MI355_API int mi355_group_set_gauss_weights(mi355_group* g, int k, float sigma, 
 MI355_API int mi355_group_filter_batched(mi355_group* g, int filter, const uint8_t* rgba, uint8_t* out, int w, int h,
                                          int nframes, int k, float sigma, double* elapsed_ms)
 {
-    if (!g || !rgba || !out || w <= 0 || h <= 0 || nframes <= 0)
+    if (!g || !rgba || !out || nframes <= 0)
         return MI355_ERR_BAD_ARG;
-    const int bpp = mi355_filter_out_bpp(filter);
-    if (bpp < 0 || !table_free_k_ok(filter, k))
-        return MI355_ERR_BAD_ARG;
+    bool table = false;
+    int rc = mi355_internal_check_filter(filter, w, h, k, sigma, &table);
+    if (rc != MI355_OK)
+        return rc;
     if (g->input_format == MI355_INPUT_BGR && mi355_filter_in_bpp(filter) == 1)
         return MI355_ERR_UNSUPPORTED;  // gray planes have no BGR form
     std::lock_guard<std::mutex> lk(g->call);
-    if (filter_needs_gauss(filter)) {
-        const int rc = g->ensure_table(k, sigma);
-        if (rc != MI355_OK)
-            return rc;
-    }
+    if (table && (rc = g->ensure_table(k, sigma)) != MI355_OK)
+        return rc;
+    const int bpp = mi355_filter_out_bpp(filter);
     const size_t fpx = (size_t)w * h, in_bpp = g->input_format == MI355_INPUT_BGR ? 3 : (size_t)mi355_filter_in_bpp(filter);
     const int n = (int)g->members.size();
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = g->all([&](Member& mb, int i) {
+    rc = g->all([&](Member& mb, int i) {
         int first = 0, count = 0;
         mi355_group_shard(i, n, nframes, &first, &count);
         if (count == 0)
@@ -310,22 +291,23 @@ MI355_API int mi355_group_filter_batched(mi355_group* g, int filter, const uint8
 MI355_API int mi355_group_filter_dev(mi355_group* g, int filter, const void* const* d_in, void* const* d_out, int w, int h,
                                      const int* nframes, int k, float sigma)
 {
-    if (!g || !d_in || !d_out || !nframes || mi355_filter_out_bpp(filter) < 0 || !table_free_k_ok(filter, k))
+    if (!g || !d_in || !d_out || !nframes)
         return MI355_ERR_BAD_ARG;
+    bool table = false;
+    int rc = mi355_internal_check_filter(filter, w, h, k, sigma, &table);
+    if (rc != MI355_OK)
+        return rc;
     for (size_t i = 0; i < g->members.size(); i++)
         if (nframes[i] < 0)
             return MI355_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(g->call);
-    if (filter_needs_gauss(filter)) {
-        const int rc = g->ensure_table(k, sigma);
-        if (rc != MI355_OK)
-            return rc;
-    }
+    if (table && (rc = g->ensure_table(k, sigma)) != MI355_OK)
+        return rc;
     return g->all([&](Member& mb, int i) {
         if (nframes[i] == 0)
             return (int)MI355_OK;
-        const int rc = mi355_filter_dev(mb.ctx, filter, d_in[i], d_out[i], w, h, nframes[i], k, sigma);
-        return rc != MI355_OK ? rc : mi355_sync(mb.ctx);
+        const int r = mi355_filter_dev(mb.ctx, filter, d_in[i], d_out[i], w, h, nframes[i], k, sigma);
+        return r != MI355_OK ? r : mi355_sync(mb.ctx);
     });
 }
 

@@ -38,20 +38,17 @@ OUT_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 1, FILTER_GAUSS: 4, FILTER_SOBEL: 1, FI
            FILTER_GAUSS_GRAY8: 1, FILTER_SOBEL_GRAY8: 1, FILTER_PIPELINE_GRAY8: 1}
 IN_BPP = {FILTER_GRAY: 4, FILTER_GRAY1: 4, FILTER_GAUSS: 4, FILTER_SOBEL: 4, FILTER_PIPELINE: 4,
           FILTER_GAUSS_GRAY8: 1, FILTER_SOBEL_GRAY8: 1, FILTER_PIPELINE_GRAY8: 1}
-# ids outside IN_BPP / OUT_BPP (which list the filters 0-7); every lookup goes through _in_bpp / _out_bpp
-_MORE_BPP = {FILTER_MEDIAN: (4, 4), FILTER_MEDIAN_GRAY8: (1, 1),
-             FILTER_ERODE: (4, 4), FILTER_DILATE: (4, 4), FILTER_OPEN: (4, 4), FILTER_CLOSE: (4, 4),
-             FILTER_ERODE_GRAY8: (1, 1), FILTER_DILATE_GRAY8: (1, 1), FILTER_OPEN_GRAY8: (1, 1),
-             FILTER_CLOSE_GRAY8: (1, 1), FILTER_EQUALIZE_GRAY8: (1, 1), FILTER_OTSU_GRAY8: (1, 1)}
 
 
 def _in_bpp(filt):
     """Bytes per input pixel of any filter id (None for an unknown id, which the library then rejects)."""
-    return IN_BPP[filt] if filt in IN_BPP else _MORE_BPP.get(filt, (None, None))[0]
+    n = load_library().mi355_filter_in_bpp(int(filt))
+    return n if n > 0 else None
 
 
 def _out_bpp(filt):
-    return OUT_BPP[filt] if filt in OUT_BPP else _MORE_BPP[filt][1]
+    n = load_library().mi355_filter_out_bpp(int(filt))
+    return n if n > 0 else None
 
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)

@@ -213,18 +213,29 @@ def test_any_byte_alignment_and_the_aliasing_rules(ctx, pkg, oracle):
 
 
 def test_gray8_gaussian_ids_reject_a_bad_k(ctx, pkg):
+    """A bad k or sigma of the four Gaussian ids (gray8 and RGBA) is MI355_ERR_BAD_ARG through every entry point."""
     y = hash_noise(8, 8, 1)
-    d_in, d_out = ctx.alloc(64), ctx.alloc(64)
+    d_in, d_out = ctx.alloc(256), ctx.alloc(256)
+    bad = [(k, 1.5) for k in (0, 2, 4, 65, -3)] + [(5, s) for s in (0.0, float("inf"), float("nan"))]
     try:
-        ctx.h2d(d_in, y)
-        for filt in (pkg.FILTER_GAUSS_GRAY8, pkg.FILTER_PIPELINE_GRAY8):
-            for k in (0, 2, 4, 65, -3):
-                with pytest.raises(pkg.Mi355Error) as e:
-                    ctx.filter_dev(filt, d_in, d_out, 8, 8, 1, k, 1.5)
-                assert e.value.code == -1, (filt, k)
-                with pytest.raises(pkg.Mi355Error) as e:
-                    ctx._host_gray8(filt, y, k, 1.5)
-                assert e.value.code == -1, (filt, k)
+        ctx.h2d(d_in, _rgba(y))
+        with pkg.Group([0]) as g:
+            for filt in (pkg.FILTER_GAUSS_GRAY8, pkg.FILTER_PIPELINE_GRAY8, pkg.FILTER_GAUSS, pkg.FILTER_PIPELINE):
+                gray8 = filt in (pkg.FILTER_GAUSS_GRAY8, pkg.FILTER_PIPELINE_GRAY8)
+                frames = y[None] if gray8 else _rgba(y)[None]
+                calls = {
+                    "filter_dev": lambda k, s: ctx.filter_dev(filt, d_in, d_out, 8, 8, 1, k, s),
+                    "host": lambda k, s: (ctx._host_gray8 if gray8 else ctx._host)(filt, frames, k, s),
+                    "stream": lambda k, s: ctx.stream(filt, frames, k=k, sigma=s),
+                    "pool_alloc": lambda k, s: ctx.pool_alloc(filt, 8, 8, 1, k=k, sigma=s, tries=1),
+                    "group.filter_batched": lambda k, s: g.filter_batched(filt, frames, k=k, sigma=s),
+                    "group.filter_dev": lambda k, s: g.filter_dev(filt, [d_in], [d_out], 8, 8, [1], k, s),
+                }
+                for k, sigma in bad:
+                    for name, call in calls.items():
+                        with pytest.raises(pkg.Mi355Error) as e:
+                            call(k, sigma)
+                        assert e.value.code == -1, (filt, k, sigma, name)
     finally:
         ctx.sync()
         ctx.free(d_in)
