@@ -3,10 +3,14 @@
 // (src/GaussianBlur/GaussianBlur.cpp:243-256: ky outer, kx inner, separate multiply and add).  A separable fp32
 // evaluation S differs from S_cpu by at most delta_bound(); wherever S is further than that from an integer,
 // trunc(S) IS the CPU byte, and the few values within it are recomputed with exact_sum(), the CPU path's own chain.
+// exact_blur_row() is that stage for one row of one channel, ExactTables / make_exact_tables() / exact_tables_ok() its
+// host side; gray8.hip's LDS-tiled stage shares only delta_bound_k().
 #pragma once
 #include <cmath>
+#include <utility>
 
 #include "common.hpp"
+#include "kernels.hpp"
 
 namespace mi355 {
 
@@ -27,8 +31,8 @@ __device__ __forceinline__ float dppr(float v)  // lane l <- lane l+1
 // (u + 1 + t) % K, t = 0 .. K-1, and the rows are visited in IMAGE order, top to bottom — arrival order for a band
 // walking down, the reverse for a band walking up (UP).  u is a constant after unrolling, so every register index
 // is static.  Runs under a wave-uniform branch: EXEC is full, the DPP reads see every lane.
-// PX = pixels per lane (4; 8 in pipe_slide8.hip).
-template <int K, int J, bool UP, int PX = 4>
+// PX = pixels per lane (4 or 8).
+template <int K, int J, bool UP, int PX>
 __device__ __forceinline__ float exact_sum(const float (&g)[K][PX], int u, const float* __restrict__ w2)
 {
     constexpr int R = K / 2;
@@ -116,6 +120,112 @@ __device__ __forceinline__ void flat_windows(const float (&g)[K][PX], float (&S)
     }
 }
 
+template <int N>
+__device__ __forceinline__ float min_tree(const float* t)
+{
+    if constexpr (N == 1)
+        return t[0];
+    else
+        return fminf(min_tree<N / 2>(t), min_tree<N / 2>(t + N / 2));
+}
+
+// Pixel position J of every lane: one wave-uniform branch, only positions some lane flagged pay the chain.
+template <int K, int PX, int J>
+__device__ __forceinline__ void exact_position(const float (&g)[K][PX], int u, bool up, const float* __restrict__ w2,
+                                               float (&S)[PX], const float (&t)[PX], float two_delta)
+{
+    if (__builtin_amdgcn_ballot_w64(t[J] < two_delta) != 0) {
+        if (up) {
+            S[J] = exact_sum<K, J, true, PX>(g, u, w2);
+            // keeps the two chains in arms of their own.  hipcc simplifies this helper before it inlines it, while g is
+            // still a pointer: it then sinks both chains into one whose ring slots are a run-time select, and the
+            // callers' rings leave the registers for scratch memory.
+            asm volatile("; band walks upward");
+        } else {
+            S[J] = exact_sum<K, J, false, PX>(g, u, w2);
+        }
+    }
+}
+
+template <int K, int PX, int... J>
+__device__ __forceinline__ void exact_positions(const float (&g)[K][PX], int u, bool up, const float* __restrict__ w2,
+                                                float (&S)[PX], const float (&t)[PX], float two_delta,
+                                                std::integer_sequence<int, J...>)
+{
+    (exact_position<K, PX, J>(g, u, up, w2, S, t, two_delta), ...);
+}
+
+// PX per-pixel values of a lane, local to exact_blur_row.  A struct and not a bare array: hipcc optimises the stage as a
+// function of its own before it inlines it, and there AMDGPUPromoteAlloca turns a bare float[PX] into a <PX x float>
+// vector, which stays one in the kernels (register tuples: 58 spilled VGPRs in the 8-pixel k = 5 pipeline).  A struct
+// it leaves alone, and SROA splits it into scalars once the caller's row loop is unrolled.
+template <int PX>
+struct LaneRow {
+    float a[PX];
+};
+
+// The blurred row whose window just completed, for one channel: S[0 .. PX-1] = the CPU path's sums of this lane's
+// pixels (+ delta where no exception was taken: the same truncation), after CLAMP, ready for the caller's truncation.
+//   g, u      : the ring; the window's arrival rows i-2R .. i sit in slots (u + 1 + t) % K, u a constant after unrolling
+//   up        : the band walks upward (wave-uniform)
+//   wv[d]     : the separable factor at distance d from the centre; delta = ExactTables::delta, two_delta = 2 delta
+//   w2, flat  : the 2-D table and the workgroup's flat_chain() table in LDS
+//   stores, keep_px : a lane that stores nothing takes no exceptions in the flat-window detour except for pixel keep_px,
+//               the one a neighbour lane reads from it (-1: none)
+//   FLAT      : compile the flat-window detour in
+// Must be called with EXEC full (DPP reads, ballots).
+template <int K, int PX, bool CLAMP, bool FLAT = true>
+__device__ __forceinline__ void exact_blur_row(const float (&g)[K][PX], int u, bool up, const float (&wv)[K / 2 + 1],
+                                               float delta, float two_delta, const float* __restrict__ w2,
+                                               const float* flat, bool stores, int keep_px, float (&S)[PX])
+{
+    constexpr int R = K / 2;
+    // vertical pass, symmetric pair form (the pair sums are exact integers <= 510; reads the same whichever way the band
+    // walks)
+    LaneRow<PX> v, t;  // t = fract(S'): exact; S' > 0
+#pragma unroll
+    for (int e = 0; e < PX; e++) {
+        float acc = wv[0] * g[(u + 1 + R) % K][e];
+#pragma unroll
+        for (int d = 1; d <= R; d++)
+            acc = __builtin_fmaf(wv[d], g[(u + 1 + R - d) % K][e] + g[(u + 1 + R + d) % K][e], acc);
+        v.a[e] = acc;
+    }
+    // horizontal pass, same form; neighbour-lane taps through DPP.  S' = S + delta rides on the centre tap, so "S within
+    // delta of an integer n" reads "fract(S') < 2 delta", one-sided, and floor(S') = floor(S) everywhere else
+#pragma unroll
+    for (int px = 0; px < PX; px++) {
+        float acc = __builtin_fmaf(wv[0], v.a[px], delta);
+#pragma unroll
+        for (int d = 1; d <= R; d++) {
+            const int a = px - d, b = px + d;
+            const float va = (a < 0) ? dppl(v.a[PX + a]) : v.a[a];
+            const float vb = (b > PX - 1) ? dppr(v.a[b - PX]) : v.a[b];
+            acc = __builtin_fmaf(wv[d], va + vb, acc);
+        }
+        S[px] = acc;
+        t.a[px] = __builtin_amdgcn_fractf(acc);
+    }
+    const uint64_t flagged = __builtin_amdgcn_ballot_w64(min_tree<PX>(t.a) < two_delta);
+    if (__builtin_expect(flagged != 0, 0)) {
+        if (FLAT && dense_flags(flagged)) {  // flat content: constant windows take a table read, not the chain
+            if (!stores) {
+#pragma unroll
+                for (int J = 0; J < PX; J++)
+                    if (J != keep_px)
+                        t.a[J] = 1.0f;
+            }
+            flat_windows<K, PX>(g, S, t.a, two_delta, flat);
+        }
+        exact_positions<K, PX>(g, u, up, w2, S, t.a, two_delta, std::make_integer_sequence<int, PX>{});
+    }
+    if constexpr (CLAMP) {
+#pragma unroll
+        for (int px = 0; px < PX; px++)
+            S[px] = fminf(S[px], 255.0f);
+    }
+}
+
 // u(x) = half an ulp of a float of magnitude <= x
 inline double half_ulp(double x)
 {
@@ -128,15 +238,11 @@ inline double half_ulp(double x)
 
 // |S - S_cpu| <= delta for every window of bytes, where S is the kernel's separable pair-form evaluation with w1 and
 // S_cpu the CPU path's k*k-term float sum with w2.  Everything is non-negative (checked by the caller), so partial
-// sums never exceed the final ones.  Runtime-k form (gray8.hip); delta_bound<K> below is the same function.
+// sums never exceed the final ones.
 inline double delta_bound_k(int K, const float* w1, const float* w2)
 {
     const int R = K / 2;
-    double sum2 = 0.0, max2 = 0.0, sum1 = 0.0, mismatch = 0.0;
-    for (int i = 0; i < K * K; i++) {
-        sum2 += (double)w2[i];
-        max2 = std::fmax(max2, (double)w2[i]);
-    }
+    double sum1 = 0.0, mismatch = 0.0;
     for (int i = 0; i < K; i++)
         sum1 += (double)w1[i];
     for (int i = 0; i < K; i++)
@@ -152,7 +258,6 @@ inline double delta_bound_k(int K, const float* w1, const float* w2)
         cum += (double)w2[i];
         e_cpu += half_ulp(255.0 * (double)w2[i]) + half_ulp(255.0 * cum + 1e-3);
     }
-    (void)max2;
     // kernel, vertical: acc = w(0) g_c, then acc = fma(w(d), g_{c-d} + g_{c+d}, acc), d = 1 .. R (the integer pair sums
     // are exact): R + 1 roundings, the one after distance d of a value <= 255 * c_d, c_d = w(0) + 2 (w(1) + ... + w(d))
     const double tv = 255.0 * sum1;
@@ -175,16 +280,45 @@ inline double delta_bound_k(int K, const float* w1, const float* w2)
         e_chain += half_ulp(tv * c_d + 0.011);
     }
     const double e_h = e_v * sum1 + e_pairs + e_chain;
-    (void)sum2;
     // every term above is a worst case already; the margin only covers the double arithmetic of this function
     return 1.02 * (e_cpu + e_h + 255.0 * mismatch) + 1e-7;
 }
 
+// The kernels' tables: host values, passed by value as a kernel argument.
 template <int K>
-double delta_bound(const float* w1, const float* w2)
+struct ExactTables {
+    float w1[K];      // separable factor (symmetric: w1[j] == w1[K-1-j])
+    float w2[K * K];  // the reference's 2-D table, row-major [ky][kx] — read only by the exact chains
+    float delta;      // |S - S_cpu| bound
+};
+
+// *wsum = the factor's sum in double: 255 wsum^2 bounds S, which decides the callers' CLAMP instantiation
+template <int K>
+inline ExactTables<K> make_exact_tables(const GaussCoef& coef, double* wsum)
 {
-    return delta_bound_k(K, w1, w2);
+    ExactTables<K> tab;
+    *wsum = 0.0;
+    for (int j = 0; j < K; j++) {
+        tab.w1[j] = coef.h_w1d[j];
+        *wsum += (double)coef.h_w1d[j];
+    }
+    for (int j = 0; j < K * K; j++)
+        tab.w2[j] = coef.h_w2d[j];
+    tab.delta = (float)delta_bound_k(K, tab.w1, tab.w2);
+    return tab;
 }
 
+// The exact-by-exception kernels need a separable table whose factor is symmetric (the pair form) and a useful error
+// bound; anything else is only reachable through mi355_ctx_set_gauss_weights.  coef.k is odd and at most 7 here.
+inline bool exact_tables_ok(const GaussCoef& coef)
+{
+    const int k = coef.k;
+    if (!coef.separable || !coef.h_w2d)
+        return false;
+    for (int j = 0; j < k / 2; j++)
+        if (coef.h_w1d[j] != coef.h_w1d[k - 1 - j])
+            return false;
+    return delta_bound_k(k, coef.h_w1d, coef.h_w2d) < 0.01;
+}
 
 }  // namespace mi355

@@ -34,19 +34,11 @@ namespace {
 
 constexpr int kWavesPerBlock = kSlideWavesPerBlock;
 
-template <int K>
-struct ETables {
-    float w1[K];
-    float w2[K * K];
-    float delta;
-    uint32_t alpha255;  // the CPU chain's byte for an all-255 window, already shifted to bits 31:24
-};
-
 template <int R, bool CLAMP>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const uint8_t* __restrict__ in,
                                                                          uint8_t* __restrict__ out, int w, int h,
                                                                          int nstrips, int lanes_out, BandPlan plan,
-                                                                         ETables<2 * R + 1> tab)
+                                                                         ExactTables<2 * R + 1> tab, uint32_t alpha255)
 {
     constexpr int K = 2 * R + 1;
     __shared__ float flat[256];  // flat[c] = the CPU path's chain over a window that is c everywhere (exact_common.hpp)
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const 
 #pragma unroll
         for (int u = 0; u < PF; u++)
             q[u] = load_row(u);
-        uint32_t n_alpha = 0u, alpha_hi = tab.alpha255;  // 3-channel walk: (A ^ 0xFF) << 24 and the byte of an all-A window
+        uint32_t n_alpha = 0u, alpha_hi = alpha255;  // 3-channel walk: (A ^ 0xFF) << 24 and the byte of an all-A window
         float g[NCH][K][4];  // ring of the last K rows, per channel; slot = arrival index % K
 #pragma unroll
         for (int c = 0; c < NCH; c++)
@@ -147,64 +139,16 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const 
                     uint32_t px[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
                     for (int c = 0; c < NCH; c++) {
-                        // window = arrival rows i-2R .. i = slots (u+1+t) % K; vertical pass, symmetric pair form
-                        float v[4];
+                        // the row whose window (arrival rows i-2R .. i) just completed.  Halo and idle lanes store
+                        // nothing: no exceptions on their behalf (keep_px = -1).  The constant-window detour is left out
+                        // at k = 7: with the ring of 4 x 7 rows its extra live values push the kernel from 198 VGPRs into
+                        // scratch memory.
+                        float S[4];
+                        exact_blur_row<K, 4, CLAMP, (R <= 2)>(g[c], u, up, wv, delta, two_delta, tab.w2, flat, stores, -1,
+                                                              S);
 #pragma unroll
-                        for (int e = 0; e < 4; e++) {
-                            float acc = wv[0] * g[c][(u + 1 + R) % K][e];
-#pragma unroll
-                            for (int d = 1; d <= R; d++)
-                                acc = __builtin_fmaf(wv[d], g[c][(u + 1 + R - d) % K][e] + g[c][(u + 1 + R + d) % K][e], acc);
-                            v[e] = acc;
-                        }
-                        // horizontal pass; S' = S + delta rides on the centre tap (one-sided integer test)
-                        float S[4], t[4];
-#pragma unroll
-                        for (int e = 0; e < 4; e++) {
-                            float acc = __builtin_fmaf(wv[0], v[e], delta);
-#pragma unroll
-                            for (int d = 1; d <= R; d++) {
-                                const int a = e - d, b = e + d;
-                                const float va = (a < 0) ? dppl(v[4 + a]) : v[a];
-                                const float vb = (b > 3) ? dppr(v[b - 4]) : v[b];
-                                acc = __builtin_fmaf(wv[d], va + vb, acc);
-                            }
-                            S[e] = acc;
-                            t[e] = __builtin_amdgcn_fractf(acc);
-                        }
-                        const float tmin = fminf(fminf(t[0], t[1]), fminf(t[2], t[3]));
-                        const uint64_t flagged = __builtin_amdgcn_ballot_w64(tmin < two_delta);
-                        if (__builtin_expect(flagged != 0, 0)) {
-                            // (k = 7 is left out: with the ring of 4 x 7 rows the extra live values push the kernel
-                            // from 198 VGPRs into scratch memory)
-                            if (R <= 2 && dense_flags(flagged)) {  // flat content: constant windows take a table read
-                                if (!stores) {           // halo and idle lanes store nothing: no exceptions on their behalf
-#pragma unroll
-                                    for (int J = 0; J < 4; J++)
-                                        t[J] = 1.0f;
-                                }
-                                flat_windows<K, 4>(g[c], S, t, two_delta, flat);
-                            }
-#define MI355_EXACT_PX(J)                                                         \
-    if (__builtin_amdgcn_ballot_w64(t[J] < two_delta) != 0) {                       \
-        if (up)                                                                   \
-            S[J] = exact_sum<K, J, true>(g[c], u, tab.w2);                        \
-        else                                                                      \
-            S[J] = exact_sum<K, J, false>(g[c], u, tab.w2);                       \
-    }
-                            MI355_EXACT_PX(0)
-                            MI355_EXACT_PX(1)
-                            MI355_EXACT_PX(2)
-                            MI355_EXACT_PX(3)
-#undef MI355_EXACT_PX
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; e++) {
-                            float sum = S[e];
-                            if constexpr (CLAMP)
-                                sum = fminf(sum, 255.0f);
-                            px[e] |= (uint32_t)sum << (8 * c);  // uchar(clamp(sum, 0, 255)): truncation
-                        }
+                        for (int e = 0; e < 4; e++)
+                            px[e] |= (uint32_t)S[e] << (8 * c);  // uchar(clamp(sum, 0, 255)): truncation
                     }
                     if constexpr (NCH == 3) {
 #pragma unroll
@@ -238,30 +182,23 @@ hipError_t launch_r(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int
     constexpr int kWavesPerSimd = (R == 1) ? 5 : (R == 2 ? 3 : 2);
     if (!make_band_plan(h, sp.nstrips, nframes, kWavesPerSimd, kRows, kRows, kRows, 0.0, kRows / 2, &plan))
         return hipErrorInvalidValue;
-    ETables<K> tab;
-    double wsum = 0.0;
-    for (int j = 0; j < K; j++) {
-        tab.w1[j] = coef.h_w1d[j];
-        wsum += (double)coef.h_w1d[j];
-    }
-    for (int j = 0; j < K * K; j++)
-        tab.w2[j] = coef.h_w2d[j];
-    tab.delta = (float)delta_bound<K>(tab.w1, tab.w2);
+    double wsum;
+    const ExactTables<K> tab = make_exact_tables<K>(coef, &wsum);
     // the CPU path's value for an all-255 window: its own chain (this translation unit is built with
     // -ffp-contract=off: one float multiply and one float add per tap), clamped and truncated
     float chain = 0.0f;
     for (int j = 0; j < K * K; j++)
         chain += 255.0f * coef.h_w2d[j];
     chain = chain < 0.0f ? 0.0f : (chain > 255.0f ? 255.0f : chain);
-    tab.alpha255 = (uint32_t)chain << 24;
+    const uint32_t alpha255 = (uint32_t)chain << 24;  // already shifted to bits 31:24
     const bool clamp = !(255.0 * wsum * wsum * 1.0001 + 0.01 < 256.0);
     const dim3 grid(plan.nblocks_a + plan.nblocks_b), block(kWavesPerBlock * 64);
     if (clamp)
         hipLaunchKernelGGL((gauss_exact_kernel<R, true>), grid, block, 0, stream, d_in, d_out, w, h, sp.nstrips, sp.lanes_out,
-                           plan, tab);
+                           plan, tab, alpha255);
     else
         hipLaunchKernelGGL((gauss_exact_kernel<R, false>), grid, block, 0, stream, d_in, d_out, w, h, sp.nstrips, sp.lanes_out,
-                           plan, tab);
+                           plan, tab, alpha255);
     return hipGetLastError();
 }
 
@@ -273,16 +210,11 @@ bool gauss_exact_supported(const uint8_t* d_in, const uint8_t* d_out, int w, int
 {
     (void)h;
     const int k = coef.k;
-    if ((k != 3 && k != 5 && k != 7) || !coef.separable || !coef.h_w2d)
+    if (k != 3 && k != 5 && k != 7)
         return false;
     if ((w & 3) != 0 || ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) != 0)
         return false;
-    for (int j = 0; j < k / 2; j++)
-        if (coef.h_w1d[j] != coef.h_w1d[k - 1 - j])
-            return false;
-    const double delta = (k == 3) ? delta_bound<3>(coef.h_w1d, coef.h_w2d)
-                                  : (k == 5 ? delta_bound<5>(coef.h_w1d, coef.h_w2d) : delta_bound<7>(coef.h_w1d, coef.h_w2d));
-    return delta < 0.01;
+    return exact_tables_ok(coef);
 }
 
 hipError_t launch_gauss_exact(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,

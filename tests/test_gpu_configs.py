@@ -630,7 +630,7 @@ def test_exact_mode_batches_and_full_frames(ctx, pkg, oracle):
         ctx.set_gauss_mode(pkg.GAUSS_FAST)
 
 
-# ---- the fused pipeline with 8 pixels per lane (csrc/pipe_slide8.hip) -----------------------------------------------
+# ---- the fused pipeline with 8 pixels per lane (csrc/pipe_slide.hip, PX = 8) ---------------------------------------
 _PIPE8_SCRIPT = r"""
 import sys
 import numpy as np
@@ -732,7 +732,7 @@ def test_data_dependent_paths_on_seeded_random_shapes_and_content(ctx, pkg, orac
 
 
 def test_pipeline_eight_pixels_per_lane():
-    """AUTO gives k = 5 launches of >= 10^9 pixels to pipe_slide8.hip (config 5's 512-frame launch above: same checksum
+    """AUTO gives k = 5 launches of >= 10^9 pixels to pipe_slide.hip's PX = 8 (config 5's 512-frame launch above: same checksum
     as the 4-pixel kernel's 8 x 64 frames, frames equal to the oracle).  Here the tuning build forces it
     (MI355_PIPE8=1) on small shapes: one strip / several strips / idle lanes, one band / several bands walking both
     ways, image edges, k = 3 and 5, noise, smooth and flat frames — bit-identical to the chained oracle."""
