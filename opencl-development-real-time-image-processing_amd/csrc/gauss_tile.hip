@@ -4,9 +4,9 @@
 // reference CPU path (src/GaussianBlur/GaussianBlur.cpp:234-261): clamp-to-edge taps, all four
 // channels, no division by the accumulated weight, truncation.
 //
-// One workgroup (256 threads = 4 waves) produces a 64x16 output tile.  The RGBA tile plus its
-// k/2 halo is staged once in LDS (one dword per pixel, clamped addresses at the image border), so
-// every input pixel is fetched from L2/HBM once per tile instead of k*k times per pixel as in the
+// The tile frame is tile_common.hpp's (64 x 16 outputs, 256 threads).  The RGBA tile plus its k/2
+// halo is staged once in LDS (one dword per pixel, clamped addresses at the image border), so every
+// input pixel is fetched from L2/HBM once per tile instead of k*k times per pixel as in the
 // reference kernel.
 //   FAST  : separable.  Pass V (vertical, k taps) turns the staged tile into float4 rows in LDS;
 //           pass H (horizontal, k taps) reads them back.  Canonical op order, shared with the
@@ -18,17 +18,31 @@
 // Bound: HBM at small k (8 B/px algorithmic); FP32 VALU at large k (2k FMA per channel).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "tile_common.hpp"
 
 namespace mi355 {
 
 namespace {
 
-constexpr int kTW = 64;
-constexpr int kTH = 16;
-constexpr int kThreads = 256;
+// LDS carve, shared by the kernel and the launcher (byte offsets): [V float4 TH*RW (FAST only)] [raw u32 RH*RW] [weights]
+struct GaussTileLayout {
+    int RW, RH, off_raw, off_wt, bytes;
+};
+
+__host__ __device__ inline GaussTileLayout gauss_tile_layout(bool exact, int k)
+{
+    GaussTileLayout L{};
+    const int R = k >> 1;
+    L.RW = kRgbaTW + 2 * R;
+    L.RH = kRgbaTH + 2 * R;
+    L.off_raw = exact ? 0 : kRgbaTH * L.RW * 16;
+    L.off_wt = L.off_raw + L.RH * L.RW * 4;
+    L.bytes = L.off_wt + (exact ? k * k : k) * 4;
+    return L;
+}
 
 template <bool EXACT>
-__global__ __launch_bounds__(kThreads) void gauss_tile_kernel(const uint32_t* __restrict__ in,
+__global__ __launch_bounds__(kRgbaTileThreads) void gauss_tile_kernel(const uint32_t* __restrict__ in,
                                                               uint32_t* __restrict__ out, int w,
                                                               int h, int tiles_x, int tiles_y, int k,
                                                               const float* __restrict__ d_wt,
@@ -36,36 +50,32 @@ __global__ __launch_bounds__(kThreads) void gauss_tile_kernel(const uint32_t* __
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int R = k >> 1;
-    const int RW = kTW + 2 * R;
-    const int RH = kTH + 2 * R;
-    // carve: [V float4 TH*RW (FAST only)] [raw u32 RH*RW] [weights]
+    const GaussTileLayout L = gauss_tile_layout(EXACT, k);
+    const int RW = L.RW, RH = L.RH;
     f32x4* V = reinterpret_cast<f32x4*>(smem);
-    uint32_t* raw = reinterpret_cast<uint32_t*>(smem + (EXACT ? 0 : (size_t)kTH * RW * 16));
+    uint32_t* raw = reinterpret_cast<uint32_t*>(smem + (size_t)L.off_raw);
     float* wt = reinterpret_cast<float*>(raw + RH * RW);
 
-    const uint32_t tile = xcd_remap(blockIdx.x, ntiles);
-    const int tx = tile % tiles_x;
-    const int ty = (tile / tiles_x) % tiles_y;
-    const size_t frame = tile / ((uint32_t)tiles_x * tiles_y);
-    const uint32_t* fin = in + frame * (size_t)w * h;
-    uint32_t* fout = out + frame * (size_t)w * h;
-    const int x0 = tx * kTW, y0 = ty * kTH;
+    const TilePos t = tile_decode(xcd_remap(blockIdx.x, ntiles), tiles_x, tiles_y, kRgbaTW, kRgbaTH);
+    const uint32_t* fin = in + t.frame * (size_t)w * h;
+    uint32_t* fout = out + t.frame * (size_t)w * h;
+    const int x0 = t.x0, y0 = t.y0;
     const int tid = threadIdx.x;
 
     const int nwt = EXACT ? k * k : k;
-    for (int i = tid; i < nwt; i += kThreads)
+    for (int i = tid; i < nwt; i += kRgbaTileThreads)
         wt[i] = d_wt[i];
-    for (int i = tid; i < RH * RW; i += kThreads) {
+    for (int i = tid; i < RH * RW; i += kRgbaTileThreads) {
         const int ly = i / RW, lx = i - ly * RW;
-        const int gy = clampi(y0 - R + ly, 0, h - 1);
-        const int gx = clampi(x0 - R + lx, 0, w - 1);
+        const int gy = border_index<kBorderClamp>(y0 - R + ly, h);
+        const int gx = border_index<kBorderClamp>(x0 - R + lx, w);
         raw[i] = fin[(size_t)gy * w + gx];
     }
     __syncthreads();
 
     if constexpr (EXACT) {
-        const int lx = tid & (kTW - 1);
-        for (int ly = tid / kTW; ly < kTH; ly += kThreads / kTW) {
+        const int lx = tid & (kRgbaTW - 1);
+        for (int ly = tid / kRgbaTW; ly < kRgbaTH; ly += kRgbaTileThreads / kRgbaTW) {
             float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
             for (int ky = 0; ky < k; ky++) {
                 const uint32_t* row = raw + (ly + ky) * RW + lx;
@@ -87,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void gauss_tile_kernel(const uint32_t* __
         }
     } else {
         // pass V: every column of the staged tile, output rows only
-        for (int i = tid; i < kTH * RW; i += kThreads) {
+        for (int i = tid; i < kRgbaTH * RW; i += kRgbaTileThreads) {
             const int ly = i / RW, cx = i - ly * RW;
             const uint32_t* col = raw + ly * RW + cx;
             uint32_t p = col[0];
@@ -113,8 +123,8 @@ __global__ __launch_bounds__(kThreads) void gauss_tile_kernel(const uint32_t* __
         }
         __syncthreads();
         // pass H
-        const int lx = tid & (kTW - 1);
-        for (int ly = tid / kTW; ly < kTH; ly += kThreads / kTW) {
+        const int lx = tid & (kRgbaTW - 1);
+        for (int ly = tid / kRgbaTW; ly < kRgbaTH; ly += kRgbaTileThreads / kRgbaTW) {
             const f32x4* vr = V + ly * RW + lx;
             f32x4 a = vr[0];
             float wv = wt[0];
@@ -140,34 +150,11 @@ __global__ __launch_bounds__(kThreads) void gauss_tile_kernel(const uint32_t* __
 hipError_t launch_gauss_tile(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h,
                              int nframes, const GaussCoef& coef, bool exact)
 {
-    const int k = coef.k, R = k / 2;
-    const int tiles_x = (w + kTW - 1) / kTW, tiles_y = (h + kTH - 1) / kTH;
-    const size_t ntiles = (size_t)tiles_x * tiles_y * nframes;
-    if (ntiles > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
-    const int RW = kTW + 2 * R, RH = kTH + 2 * R;
-    size_t lds = (size_t)RH * RW * 4 + (size_t)(exact ? k * k : k) * 4;
-    if (!exact)
-        lds += (size_t)kTH * RW * 16;
-    hipError_t e;
-    if (exact) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(gauss_tile_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(gauss_tile_kernel<true>, dim3((unsigned)ntiles), dim3(kThreads), lds, stream,
-                           reinterpret_cast<const uint32_t*>(d_in), reinterpret_cast<uint32_t*>(d_out),
-                           w, h, tiles_x, tiles_y, k, coef.d_w2d, (uint32_t)ntiles);
-    } else {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(gauss_tile_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(gauss_tile_kernel<false>, dim3((unsigned)ntiles), dim3(kThreads), lds, stream,
-                           reinterpret_cast<const uint32_t*>(d_in), reinterpret_cast<uint32_t*>(d_out),
-                           w, h, tiles_x, tiles_y, k, coef.d_w1d, (uint32_t)ntiles);
-    }
-    return hipGetLastError();
+    const TileGrid g(w, h, nframes, kRgbaTW, kRgbaTH);
+    const GaussTileLayout L = gauss_tile_layout(exact, coef.k);
+    return launch_tiles(exact ? gauss_tile_kernel<true> : gauss_tile_kernel<false>, g, kRgbaTileThreads, L.bytes, kLdsRaise,
+                        stream, reinterpret_cast<const uint32_t*>(d_in), reinterpret_cast<uint32_t*>(d_out), w, h,
+                        g.tiles_x, g.tiles_y, coef.k, exact ? coef.d_w2d : coef.d_w1d, g.n());
 }
 
 }  // namespace mi355

@@ -8,10 +8,10 @@
 //             round-half-even magnitude, saturation.  No luminance step.
 //   Pipeline  Sobel of the EXACT Gaussian, in both Gaussian modes.
 //
-// One LDS-staged kernel template for all three.  A workgroup (256 threads) produces a 256 x 32 output tile:
-//   1. stage the tile plus its halo as raw bytes in LDS: 16-byte global loads wherever a 16-pixel piece lies inside the
-//      row (any byte alignment: gfx950 global accesses need none), pixel by pixel only for the pieces that cross the
-//      image border, where the border rule (clamp for the Gaussian, reflect-101 for the Sobel alone) is applied;
+// One LDS-staged kernel template for all three, on the tile frame of tile_common.hpp.  A workgroup (256 threads)
+// produces a 256 x 32 output tile:
+//   1. stage the tile plus its halo as raw bytes in LDS, in 16-byte chunks under the filter's border
+//      rule: clamp for the Gaussian, reflect-101 for the Sobel alone;
 //   2. Gaussian: vertical then horizontal pass in the pair form of exact_common.hpp (acc = w_c g_c, then
 //      acc = fma(w_d, g_{c-d} + g_{c+d}, acc)), one pixel per thread, consecutive threads on consecutive columns
 //      (no LDS bank conflicts).  "Exact by exception": with delta = delta_bound() of the two tables, a pixel whose
@@ -20,8 +20,8 @@
 //      non-negative separable product runs that chain for every pixel (tap by tap, as the reference kernel applies it);
 //   3. Sobel from the staged bytes (Sobel alone) or from the blurred tile, which the pipeline computes one pixel wider
 //      on each side at reflect-101 coordinates, so the Sobel stage itself has no border cases;
-//   4. the output tile leaves LDS as one 16-byte store per thread and row piece (the MI355X store path prices a dword
-//      store at ~6x a dwordx4 per byte; MI355X_MICROARCH.md), byte stores only at the right edge of a ragged row.
+//   4. the output tile leaves LDS as one 16-byte store per thread and row piece (store_chunk16; the MI355X store path
+//      prices a dword store at ~6x a dwordx4 per byte; MI355X_MICROARCH.md).
 // Algorithmic bytes: 2 B/px.  k in {3, 5, 7} is compiled with a constant k (unrolled taps); everything else takes the
 // runtime-k instantiation.
 #include <cmath>
@@ -30,6 +30,7 @@
 #include "exact_common.hpp"
 #include "kernels.hpp"
 #include "slide_common.hpp"
+#include "tile_common.hpp"
 
 namespace mi355 {
 
@@ -120,13 +121,11 @@ __global__ __launch_bounds__(kG8Threads) void gray8_tile_kernel(const uint8_t* _
     uint8_t* G = smem + L.off_g;
     uint8_t* O = smem + L.off_o;
 
-    const uint32_t tile = xcd_remap(blockIdx.x, ntiles);
-    const int tx = tile % tiles_x;
-    const int ty = (tile / tiles_x) % tiles_y;
-    const size_t frame = tile / ((uint32_t)tiles_x * tiles_y);
-    const uint8_t* fin = in + frame * (size_t)w * h;
-    uint8_t* fout = out + frame * (size_t)w * h;
-    const int x0 = tx * kG8TW, y0 = ty * kG8TH;
+    constexpr Border kBorder = OP == kOpSobel ? kBorderReflect101 : kBorderClamp;  // of the staged tile
+    const TilePos t = tile_decode(xcd_remap(blockIdx.x, ntiles), tiles_x, tiles_y, kG8TW, kG8TH);
+    const uint8_t* fin = in + t.frame * (size_t)w * h;
+    uint8_t* fout = out + t.frame * (size_t)w * h;
+    const int x0 = t.x0, y0 = t.y0;
     const int sy0 = y0 - L.H, sx0 = x0 - L.H;  // image position of staged byte (0, 0)
     const int tid = threadIdx.x;
 
@@ -141,20 +140,16 @@ __global__ __launch_bounds__(kG8Threads) void gray8_tile_kernel(const uint8_t* _
     const int npieces = L.RWS / 16;
     for (int i = tid; i < L.RH * npieces; i += kG8Threads) {
         const int s = i / npieces, p = i - s * npieces;
-        const int gy = OP == kOpSobel ? reflect101(min(sy0 + s, h), h) : clampi(sy0 + s, 0, h - 1);
-        const uint8_t* row = fin + (size_t)gy * w;
+        const uint8_t* row = fin + (size_t)border_index<kBorder>(sy0 + s, h) * w;
         const int gx = sx0 + 16 * p;
         u32x4 v;
         if (gx >= 0 && gx + 16 <= w) {
-            typedef u32x4 __attribute__((aligned(1))) u32x4_a1;
             v = *reinterpret_cast<const u32x4_a1*>(row + gx);
         } else {
             uint32_t b[16];
 #pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const int x = OP == kOpSobel ? reflect101(min(gx + j, w), w) : clampi(gx + j, 0, w - 1);
-                b[j] = row[x];
-            }
+            for (int j = 0; j < 16; j++)
+                b[j] = row[border_index<kBorder>(gx + j, w)];
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 v[q] = b[4 * q] | (b[4 * q + 1] << 8) | (b[4 * q + 2] << 16) | (b[4 * q + 3] << 24);
@@ -167,8 +162,8 @@ __global__ __launch_bounds__(kG8Threads) void gray8_tile_kernel(const uint8_t* _
         // blurred tile row r / column c sits at image row gmap_y(r) / column gmap_x(c): the output tile itself for the
         // Gaussian; for the pipeline one more row / column on each side, at reflect-101 positions (the Sobel's border
         // rule applied to the blurred image), clamped first so that rows far past the image stay inside the staged tile
-        auto gmap_y = [&](int r) { return o ? reflect101(min(y0 - 1 + r, h), h) : min(y0 + r, h - 1); };
-        auto gmap_x = [&](int c) { return o ? reflect101(min(x0 - 1 + c, w), w) : min(x0 + c, w - 1); };
+        auto gmap_y = [&](int r) { return o ? border_index<kBorderReflect101>(y0 - 1 + r, h) : min(y0 + r, h - 1); };
+        auto gmap_x = [&](int c) { return o ? border_index<kBorderReflect101>(x0 - 1 + c, w) : min(x0 + c, w - 1); };
         uint8_t* dst = o ? G : O;
         const int dst_stride = o ? L.GWS : kG8TW;
         if constexpr (GM == kGmTap) {
@@ -235,15 +230,7 @@ __global__ __launch_bounds__(kG8Threads) void gray8_tile_kernel(const uint8_t* _
         const int gy = y0 + r, gx = x0 + 16 * p;
         if (gy >= h || gx >= w)
             continue;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(O + r * kG8TW + 16 * p);
-        uint8_t* dp = fout + (size_t)gy * w + gx;
-        if (gx + 16 <= w) {
-            typedef u32x4 __attribute__((aligned(1))) u32x4_a1;
-            *reinterpret_cast<u32x4_a1*>(dp) = v;
-        } else {
-            for (int j = 0; gx + j < w; j++)
-                dp[j] = (uint8_t)(v[j >> 2] >> (8 * (j & 3)));
-        }
+        store_chunk16<1>(fout + (size_t)gy * w, gx, w, *reinterpret_cast<const u32x4*>(O + r * kG8TW + 16 * p));
     }
 }
 
@@ -251,34 +238,21 @@ template <int OP, int KC, int GM>
 hipError_t launch_g8(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k,
                      const float* d_w2, const float* d_w1, float delta)
 {
-    const int tiles_x = (w + kG8TW - 1) / kG8TW, tiles_y = (h + kG8TH - 1) / kG8TH;
-    const size_t ntiles = (size_t)tiles_x * tiles_y * nframes;
-    if (ntiles > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
+    const TileGrid g(w, h, nframes, kG8TW, kG8TH);
     const G8Layout L = g8_layout(OP, GM, OP == kOpSobel ? 1 : k);
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gray8_tile_kernel<OP, KC, GM>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, L.bytes);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL((gray8_tile_kernel<OP, KC, GM>), dim3((unsigned)ntiles), dim3(kG8Threads), (size_t)L.bytes,
-                       stream, d_in, d_out, w, h, tiles_x, tiles_y, (uint32_t)ntiles, k, d_w2, d_w1, delta);
-    return hipGetLastError();
+    return launch_tiles(gray8_tile_kernel<OP, KC, GM>, g, kG8Threads, L.bytes, kLdsRaise, stream, d_in, d_out, w, h,
+                        g.tiles_x, g.tiles_y, g.n(), k, d_w2, d_w1, delta);
 }
 
+// const_k: k is 3, 5 or 7 and gets its own instantiation; otherwise the runtime-k one (KC = 0)
 template <int OP, int GM>
 hipError_t launch_g8_k(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                        const GaussCoef& coef, bool const_k, float delta)
 {
-    const int k = coef.k;
-    if (const_k) {
-        switch (k) {
-        case 3: return launch_g8<OP, 3, GM>(stream, d_in, d_out, w, h, nframes, k, coef.d_w2d, coef.d_w1d, delta);
-        case 5: return launch_g8<OP, 5, GM>(stream, d_in, d_out, w, h, nframes, k, coef.d_w2d, coef.d_w1d, delta);
-        case 7: return launch_g8<OP, 7, GM>(stream, d_in, d_out, w, h, nframes, k, coef.d_w2d, coef.d_w1d, delta);
-        default: break;
-        }
-    }
-    return launch_g8<OP, 0, GM>(stream, d_in, d_out, w, h, nframes, k, coef.d_w2d, coef.d_w1d, delta);
+    return dispatch_int(const_k ? coef.k : 0, std::integer_sequence<int, 0, 3, 5, 7>{}, [&](auto KC) {
+        return launch_g8<OP, decltype(KC)::value, GM>(stream, d_in, d_out, w, h, nframes, coef.k, coef.d_w2d, coef.d_w1d,
+                                                      delta);
+    });
 }
 
 // The pair-form separable sum stands in for the table when the table is a symmetric non-negative separable product

@@ -21,6 +21,7 @@
 //                 16-byte loads at whatever alignment the input then has, head and tail bytes as in hist_kernel.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "tile_common.hpp"
 
 #include <cfloat>
 
@@ -33,7 +34,6 @@ constexpr int kHWaves = kHThreads / kWave;
 constexpr int kHistVec = 16;  // 16-byte vectors per thread of hist_kernel: 64 KiB per block, 256 atomics per flush
 constexpr int kApplyVec = 8;  // per thread of apply_kernel: 32 KiB per block
 
-typedef u32x4 __attribute__((aligned(1))) u32x4_a1;
 
 // where the 16-byte body of a frame starts, relative to the frame, for a frame at address a of npx bytes
 __device__ __forceinline__ uint32_t head_bytes(uintptr_t a, uint32_t npx)

@@ -22,7 +22,7 @@
 //
 // Kernels (round 3: the one-thread-per-pixel restatements of the .cl files — k^2 global loads per pixel — are now only
 // the fallback for shapes the fast ones do not take):
-//   image2d_gauss_tile_kernel  one workgroup per 64 x 16 output tile; the tile + halo is staged ONCE in LDS as
+//   image2d_gauss_tile_kernel  one workgroup per 64 x 16 output tile (tile_common.hpp); tile + halo are staged ONCE in LDS as
 //                              normalised float4 texels (byte / 255.0f evaluated once per staged texel instead of once
 //                              per tap; border colour 0 written for texels outside the image), the table in LDS; a
 //                              thread owns 4 adjacent outputs and, per window row, pulls the 4 + 2*half texels it
@@ -37,6 +37,7 @@
 // around them (the entry point is the per-frame host call, mi355_image2d_rgba8).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "tile_common.hpp"
 
 namespace mi355 {
 
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void image2d_sobel_kernel(const uint32_t*
 }
 
 // ---- the fast forms ---------------------------------------------------------------------------------------------------
-constexpr int kTileW = 64, kTileH = 16;   // outputs per workgroup: 256 threads x 4 adjacent outputs
+// outputs per workgroup: kRgbaTW x kRgbaTH = 256 threads x 4 adjacent outputs
 constexpr int kImgMaxFastK = 25;          // (64 + 24) x (16 + 24) float4 texels = 55 KiB of LDS
 
 // texel (x, y) of the image as read_imagef returns it under CLK_ADDRESS_CLAMP: channel / 255.0f, (0,0,0,0) outside
@@ -137,28 +138,25 @@ __device__ __forceinline__ f32x4 read_texel(const uint32_t* __restrict__ img, in
 }
 
 template <int HALF>
-__global__ __launch_bounds__(kThreads) void image2d_gauss_tile_kernel(const uint32_t* __restrict__ in,
+__global__ __launch_bounds__(kRgbaTileThreads) void image2d_gauss_tile_kernel(const uint32_t* __restrict__ in,
                                                                       uint32_t* __restrict__ out, int w, int h,
                                                                       int tiles_x, int tiles_y,
                                                                       const float* __restrict__ table)
 {
     constexpr int K = 2 * HALF + 1;
-    constexpr int SW = kTileW + 2 * HALF, SH = kTileH + 2 * HALF;  // staged tile
+    constexpr int SW = kRgbaTW + 2 * HALF, SH = kRgbaTH + 2 * HALF;  // staged tile
     extern __shared__ __align__(16) unsigned char smem_raw[];
     f32x4* tile = reinterpret_cast<f32x4*>(smem_raw);              // [SH][SW]
     float* wt = reinterpret_cast<float*>(tile + SW * SH);          // [K*K]
 
-    const uint32_t blk = xcd_remap(blockIdx.x, gridDim.x);         // neighbouring tiles (shared halo) on one XCD
-    const int tx = (int)(blk % (uint32_t)tiles_x);
-    const int ty = (int)((blk / (uint32_t)tiles_x) % (uint32_t)tiles_y);
-    const size_t f = blk / ((uint32_t)tiles_x * (uint32_t)tiles_y);
-    const uint32_t* img = in + f * (size_t)w * h;
-    uint32_t* oimg = out + f * (size_t)w * h;
-    const int x0 = tx * kTileW, y0 = ty * kTileH;
+    const TilePos t = tile_decode(xcd_remap(blockIdx.x, gridDim.x), tiles_x, tiles_y, kRgbaTW, kRgbaTH);
+    const uint32_t* img = in + t.frame * (size_t)w * h;
+    uint32_t* oimg = out + t.frame * (size_t)w * h;
+    const int x0 = t.x0, y0 = t.y0;
 
-    for (int i = threadIdx.x; i < K * K; i += kThreads)
+    for (int i = threadIdx.x; i < K * K; i += kRgbaTileThreads)
         wt[i] = table[i];
-    for (int i = threadIdx.x; i < SW * SH; i += kThreads) {
+    for (int i = threadIdx.x; i < SW * SH; i += kRgbaTileThreads) {
         const int sy = i / SW, sx = i - sy * SW;
         tile[i] = read_texel(img, w, h, x0 + sx - HALF, y0 + sy - HALF);
     }
@@ -193,6 +191,8 @@ __global__ __launch_bounds__(kThreads) void image2d_gauss_tile_kernel(const uint
 #pragma unroll
     for (int o = 0; o < 4; o++)
         o4[o] = to_unorm8(acc[o].x) | (to_unorm8(acc[o].y) << 8) | (to_unorm8(acc[o].z) << 16) | (to_unorm8(acc[o].w) << 24);
+    // not store_chunk16: with it the HALF = 3 instantiation goes from 254 to 256 VGPRs and loses its second wave
+    // (profiles/tile_frame_vgpr.txt)
     uint32_t* dst = oimg + (size_t)oy * w + ox;
     if (ox + 3 < w && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0)) {
         *reinterpret_cast<u32x4*>(dst) = u32x4{o4[0], o4[1], o4[2], o4[3]};
@@ -283,14 +283,10 @@ hipError_t launch_gauss_tile_image(hipStream_t stream, const uint32_t* in, uint3
                                    const float* d_table)
 {
     constexpr int K = 2 * HALF + 1;
-    const int tiles_x = (w + kTileW - 1) / kTileW, tiles_y = (h + kTileH - 1) / kTileH;
-    const size_t blocks = (size_t)tiles_x * tiles_y * nframes;
-    if (blocks > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
-    const size_t lds = sizeof(f32x4) * (size_t)(kTileW + 2 * HALF) * (kTileH + 2 * HALF) + sizeof(float) * K * K;
-    hipLaunchKernelGGL((image2d_gauss_tile_kernel<HALF>), dim3((unsigned)blocks), dim3(kThreads), lds, stream, in, out, w,
-                       h, tiles_x, tiles_y, d_table);
-    return hipGetLastError();
+    const TileGrid g(w, h, nframes, kRgbaTW, kRgbaTH);
+    const size_t lds = sizeof(f32x4) * (size_t)(kRgbaTW + 2 * HALF) * (kRgbaTH + 2 * HALF) + sizeof(float) * K * K;
+    return launch_tiles(image2d_gauss_tile_kernel<HALF>, g, kRgbaTileThreads, lds, kLdsDefault, stream, in, out, w, h, g.tiles_x,
+                        g.tiles_y, d_table);
 }
 
 }  // namespace
@@ -322,21 +318,10 @@ hipError_t launch_image2d(hipStream_t stream, int filter, const uint8_t* d_in, u
     }
     if (!plain && filter == 2 && k >= 3 && k <= kImgMaxFastK && out4) {
         uint32_t* o = reinterpret_cast<uint32_t*>(d_out);
-        switch (k / 2) {
-        case 1: return launch_gauss_tile_image<1>(stream, in, o, w, h, nframes, d_table);
-        case 2: return launch_gauss_tile_image<2>(stream, in, o, w, h, nframes, d_table);
-        case 3: return launch_gauss_tile_image<3>(stream, in, o, w, h, nframes, d_table);
-        case 4: return launch_gauss_tile_image<4>(stream, in, o, w, h, nframes, d_table);
-        case 5: return launch_gauss_tile_image<5>(stream, in, o, w, h, nframes, d_table);
-        case 6: return launch_gauss_tile_image<6>(stream, in, o, w, h, nframes, d_table);
-        case 7: return launch_gauss_tile_image<7>(stream, in, o, w, h, nframes, d_table);
-        case 8: return launch_gauss_tile_image<8>(stream, in, o, w, h, nframes, d_table);
-        case 9: return launch_gauss_tile_image<9>(stream, in, o, w, h, nframes, d_table);
-        case 10: return launch_gauss_tile_image<10>(stream, in, o, w, h, nframes, d_table);
-        case 11: return launch_gauss_tile_image<11>(stream, in, o, w, h, nframes, d_table);
-        case 12: return launch_gauss_tile_image<12>(stream, in, o, w, h, nframes, d_table);
-        default: break;
-        }
+        static_assert(kImgMaxFastK == 25, "the list below instantiates half = 1 .. 12");
+        return dispatch_int(k / 2, std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>{}, [&](auto HALF) {
+            return launch_gauss_tile_image<decltype(HALF)::value>(stream, in, o, w, h, nframes, d_table);
+        });
     }
     if (filter == 0) {
         hipLaunchKernelGGL(image2d_gray_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, in, d_out, npx);

@@ -9,8 +9,8 @@
 //    A thread walks a strip of kMedStrip output rows down one column group, keeping the last k input rows in registers
 //    (a ring of k rows indexed by a compile-time phase, so it never moves a register).  Values live two per 32-bit word
 //    as u16 lanes, and every compare-exchange is one v_pk_min_u16 + one v_pk_max_u16 on two lanes at once:
-//      RGBA   a column group is 4 pixels (one 16-byte load); each pixel dword p splits once into (R, B) = p & 0x00ff00ff
-//             and (G, A) = v_perm_b32(p, zero-fill), so alpha rides along with G, and repacks with one v_lshl_or_b32;
+//      RGBA   a column group is 4 pixels (one 16-byte load); each pixel dword splits once into (R, B) and (G, A)
+//             (split_rgba, tile_common.hpp), so alpha rides along with G, and repacks with one v_lshl_or_b32;
 //      gray8  a column group is 8 pixels; word c of a row holds the pixels (x0 + c, x0 + c + 4), so the same 4-column
 //             network yields pixels x0 .. x0 + 7 in its two lanes.
 //    Halo columns (k / 2 on each side) are separate clamped loads that hit the cache lines the neighbouring thread
@@ -27,13 +27,14 @@
 //             values is 2s - 3 compare-exchanges: sum_{s=4..14}(2s - 3) = 165 compare-exchanges + med3, of whose
 //             330 + 4 min/max the last min and max of every drop are dead: 312 v_pk_min/max_u16 per word (ISA: 12480
 //             per 20 RGBA pixels), i.e. ~624 per RGBA pixel and ~156 per gray8 pixel.  Issue-bound, not memory-bound.
-// 2. Counting selection in an LDS tile (any odd k <= 7, both layouts): median_tile_kernel.  The tile and its clamped
-//    halo are staged as one dword per pixel; each channel's median is the smallest t with #(window values <= t) >=
-//    (k*k + 1) / 2, found by an 8-step bisection on t.  AUTO runs it for k = 7, MI355_IMPL_TILE for every k; it is the
-//    on-GPU cross-check of the networks.
+// 2. Counting selection in an LDS tile (any odd k <= 7, both layouts): median_tile_kernel, on the tile frame of
+//    tile_common.hpp.  The tile and its clamped halo are staged as one dword per pixel; each channel's median is the
+//    smallest t with #(window values <= t) >= (k*k + 1) / 2, found by an 8-step bisection on t.  AUTO runs it for
+//    k = 7, MI355_IMPL_TILE for every k; it is the on-GPU cross-check of the networks.
 #include "../../include/mi355_imgfilter.h"
 #include "common.hpp"
 #include "kernels.hpp"
+#include "tile_common.hpp"
 
 namespace mi355 {
 
@@ -42,10 +43,6 @@ namespace {
 constexpr int kMedThreads = 256;
 constexpr int kMedStrip = 64;  // output rows per thread of the network kernel
 
-using u16x2 = __attribute__((ext_vector_type(2))) unsigned short;
-
-__device__ __forceinline__ u16x2 pmin(u16x2 a, u16x2 b) { return __builtin_elementwise_min(a, b); }  // v_pk_min_u16
-__device__ __forceinline__ u16x2 pmax(u16x2 a, u16x2 b) { return __builtin_elementwise_max(a, b); }  // v_pk_max_u16
 __device__ __forceinline__ void cex(u16x2& a, u16x2& b)
 {
     const u16x2 lo = pmin(a, b);
@@ -53,9 +50,6 @@ __device__ __forceinline__ void cex(u16x2& a, u16x2& b)
     a = lo;
 }
 __device__ __forceinline__ u16x2 pmed3(u16x2 a, u16x2 b, u16x2 c) { return pmax(pmin(a, b), pmin(pmax(a, b), c)); }
-
-__device__ __forceinline__ u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
-__device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
 
 // k = 3: out[p] = median of columns p .. p + 2 (rows a, b, c), p = 0 .. 3
 __device__ __forceinline__ void median9_x4(const u16x2* a, const u16x2* b, const u16x2* c, u16x2* out)
@@ -116,7 +110,6 @@ __device__ __forceinline__ void load_row(const uint8_t* __restrict__ row, int x0
         const uint32_t* r32 = reinterpret_cast<const uint32_t*>(row);
         uint32_t px[NC];
         if (x0 + 4 <= w) {
-            typedef u32x4 __attribute__((aligned(4))) u32x4_a4;
             const u32x4 q = *reinterpret_cast<const u32x4_a4*>(r32 + x0);
             px[R] = q[0];
             px[R + 1] = q[1];
@@ -133,16 +126,13 @@ __device__ __forceinline__ void load_row(const uint8_t* __restrict__ row, int x0
             px[R + 4 + j] = r32[min(x0 + 4 + j, w - 1)];
         }
 #pragma unroll
-        for (int c = 0; c < NC; c++) {
-            dst[c][0] = as_u16x2(px[c] & 0x00FF00FFu);                          // (R, B)
-            dst[c][1] = as_u16x2(__builtin_amdgcn_perm(0u, px[c], 0x0C030C01u));  // (G, A)
-        }
+        for (int c = 0; c < NC; c++)
+            split_rgba(px[c], dst[c][0], dst[c][1]);
     } else {
         // bytes x0 - R .. x0 + 7 + R; word c = (x0 - R + c, x0 - R + c + 4)
         constexpr int NB = 8 + 2 * R;
         uint32_t b[NB];
         if (x0 >= 4 && x0 + 12 <= w) {
-            typedef u32x4 __attribute__((aligned(1))) u32x4_a1;
             const u32x4 q = *reinterpret_cast<const u32x4_a1*>(row + x0 - 4);  // bytes x0 - 4 .. x0 + 11
 #pragma unroll
             for (int i = 0; i < NB; i++) {
@@ -222,18 +212,11 @@ __global__ __launch_bounds__(kMedThreads) void median_net_kernel(const uint8_t* 
             }
             uint8_t* orow = fout + (size_t)y * stride;
             if constexpr (!G8) {
-                uint32_t px[4];
+                u32x4 px;
 #pragma unroll
                 for (int p = 0; p < 4; p++)
-                    px[p] = as_u32(med[p][0]) | (as_u32(med[p][1]) << 8);  // v_lshl_or_b32
-                uint32_t* o32 = reinterpret_cast<uint32_t*>(orow) + x0;
-                if (x0 + 4 <= w) {
-                    typedef u32x4 __attribute__((aligned(4))) u32x4_a4;
-                    *reinterpret_cast<u32x4_a4*>(o32) = u32x4{px[0], px[1], px[2], px[3]};
-                } else {
-                    for (int p = 0; x0 + p < w; p++)
-                        o32[p] = px[p];
-                }
+                    px[p] = join_rgba(med[p][0], med[p][1]);
+                store_chunk16<4>(orow, x0, w, px);
             } else {
                 uint32_t o[4];
 #pragma unroll
@@ -246,8 +229,6 @@ __global__ __launch_bounds__(kMedThreads) void median_net_kernel(const uint8_t* 
                                     (__builtin_amdgcn_perm(o[3], o[2], 0x0C0C0602u) << 16);
                 uint8_t* dp = orow + x0;
                 if (x0 + 8 <= w) {
-                    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-                    typedef u32x2 __attribute__((aligned(1))) u32x2_a1;
                     *reinterpret_cast<u32x2_a1*>(dp) = u32x2{d0, d1};
                 } else {
                     for (int j = 0; x0 + j < w; j++)
@@ -285,13 +266,11 @@ __global__ __launch_bounds__(kTileW* kTileH) void median_tile_kernel(const uint8
     __shared__ uint32_t s[kTileSH][kTileSW];  // one pixel per dword (gray8: the byte in bits 0-7)
     constexpr int BPP = G8 ? 1 : 4;
     const int R = k / 2;
-    const int tx = blockIdx.x % tiles_x;
-    const int ty = (blockIdx.x / tiles_x) % tiles_y;
-    const size_t frame = blockIdx.x / ((unsigned)tiles_x * tiles_y);
+    const TilePos tp = tile_decode(blockIdx.x, tiles_x, tiles_y, kTileW, kTileH);  // no XCD remap: not measured here
     const size_t fpx = (size_t)w * h;
-    const uint8_t* fin = in + frame * fpx * BPP;
-    uint8_t* fout = out + frame * fpx * BPP;
-    const int x0 = tx * kTileW, y0 = ty * kTileH;
+    const uint8_t* fin = in + tp.frame * fpx * BPP;
+    uint8_t* fout = out + tp.frame * fpx * BPP;
+    const int x0 = tp.x0, y0 = tp.y0;
     const int tid = threadIdx.x;
     for (int i = tid; i < (kTileH + 2 * R) * (kTileW + 2 * R); i += kTileW * kTileH) {
         const int r = i / (kTileW + 2 * R), c = i - r * (kTileW + 2 * R);
@@ -332,13 +311,9 @@ __global__ __launch_bounds__(kTileW* kTileH) void median_tile_kernel(const uint8
 template <bool G8>
 hipError_t launch_tile(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k)
 {
-    const int tiles_x = (w + kTileW - 1) / kTileW, tiles_y = (h + kTileH - 1) / kTileH;
-    const uint64_t nblocks = (uint64_t)tiles_x * tiles_y * nframes;
-    if (nblocks > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL((median_tile_kernel<G8>), dim3((unsigned)nblocks), dim3(kTileW * kTileH), 0, stream, d_in, d_out,
-                       w, h, k, tiles_x, tiles_y);
-    return hipGetLastError();
+    const TileGrid g(w, h, nframes, kTileW, kTileH);
+    return launch_tiles(median_tile_kernel<G8>, g, kTileW * kTileH, 0, kLdsDefault, stream, d_in, d_out, w, h, k,
+                        g.tiles_x, g.tiles_y);
 }
 
 }  // namespace
@@ -348,15 +323,14 @@ hipError_t launch_median(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out
 {
     if (k < 3 || k > MI355_MAX_MEDIAN_K || (k & 1) == 0)
         return hipErrorInvalidValue;
-    const bool tile = impl == 1 || k == 7;
-    if (tile)
+    if (impl == 1 || k == 7)
         return gray8 ? launch_tile<true>(stream, d_in, d_out, w, h, nframes, k)
                      : launch_tile<false>(stream, d_in, d_out, w, h, nframes, k);
-    if (k == 3)
-        return gray8 ? launch_net<true, 3>(stream, d_in, d_out, w, h, nframes)
-                     : launch_net<false, 3>(stream, d_in, d_out, w, h, nframes);
-    return gray8 ? launch_net<true, 5>(stream, d_in, d_out, w, h, nframes)
-                 : launch_net<false, 5>(stream, d_in, d_out, w, h, nframes);
+    return dispatch_int(k, std::integer_sequence<int, 3, 5>{}, [&](auto K) {
+        constexpr int kc = decltype(K)::value;
+        return gray8 ? launch_net<true, kc>(stream, d_in, d_out, w, h, nframes)
+                     : launch_net<false, kc>(stream, d_in, d_out, w, h, nframes);
+    });
 }
 
 }  // namespace mi355

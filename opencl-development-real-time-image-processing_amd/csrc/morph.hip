@@ -3,11 +3,10 @@
 // centre, odd 3 <= k <= MI355_MAX_MORPH_K, every channel on its own (alpha included), clamp-to-edge (BORDER_REPLICATE)
 // borders, frames independent.  Every output byte is an input byte: the kernel is tested for bit-identity only.
 //
-// One kernel, morph_kernel<G8, K, OP>, serves all eight ids (the impl knob does not select anything here).  A block of
-// 256 threads owns a TW x TH output tile of one frame:
+// One kernel, morph_kernel<G8, K, OP>, serves all eight ids (the impl knob does not select anything here), on the tile
+// frame of tile_common.hpp.  A block of 256 threads owns a TW x TH output tile of one frame:
 //   load    the tile plus a halo of H = r (one stage) or 2r (OPEN / CLOSE) rows and HC >= H columns (HC rounded up to
-//           one 16-byte chunk) goes to the LDS buffer `raw` as pixels, rows clamped, 16-byte global loads for every
-//           chunk inside the frame and clamped single-pixel loads for the chunks that cross its left or right edge;
+//           one 16-byte chunk) goes to the LDS buffer `raw` as pixels, rows clamped, 16-byte loads inside the frame, clamped pixel loads across its edges;
 //   stage   a separable min (ERODE) or max (DILATE): the H pass reads runs of NR pixels (+ 2r halo) of a row of `raw`
 //           (consecutive lanes: consecutive rows), takes the window min of each and writes words to `hb`; the V pass
 //           reads NV rows (+ 2r) of a word column of `hb` (consecutive lanes: consecutive columns) and writes the
@@ -16,17 +15,16 @@
 //   fix-up  (OPEN / CLOSE, border tiles only) the first stage produced the tile plus r on every side; its positions
 //           outside the frame are overwritten with the value at the clamped position, so the second stage sees the
 //           clamp-to-edge border of the intermediate frame, not a first stage extended past the edge;
-//   store   16-byte global stores of the tile (single pixels / bytes across the right edge).
-// Words are two u16 lanes and every min is one v_pk_min_u16 for two values: RGBA splits each pixel into (R, B) =
-// p & 0x00ff00ff and (G, A) = v_perm_b32; gray8 packs pixels (x, x + NR / 2) of one run.  The window min of a run of N
+//   store   16-byte global stores of the tile (store_chunk16).
+// Words are two u16 lanes and every min is one v_pk_min_u16 for two values: RGBA splits each pixel into (R, B) and
+// (G, A) (split_rgba); gray8 packs pixels (x, x + NR / 2) of one run.  The window min of a run of N
 // outputs is either the plain k - 1 mins per output or window doubling (m_2s[i] = min(m_s[i], m_s[i + s]) up to the
 // largest power of two P <= k, then min(m_P[i], m_P[i + k - P])), whichever costs fewer mins at compile time: about
 // log2(k) + 1 per output instead of k - 1, so k = 17 costs no more than a few times k = 3.
 #include "../../include/mi355_imgfilter.h"
 #include "common.hpp"
 #include "kernels.hpp"
-
-#include <type_traits>
+#include "tile_common.hpp"
 
 namespace mi355 {
 
@@ -34,20 +32,8 @@ namespace {
 
 constexpr int kMorThreads = 256;
 
-using u16x2 = __attribute__((ext_vector_type(2))) unsigned short;
-
-__device__ __forceinline__ u16x2 pmin(u16x2 a, u16x2 b) { return __builtin_elementwise_min(a, b); }  // v_pk_min_u16
-__device__ __forceinline__ u16x2 pmax(u16x2 a, u16x2 b) { return __builtin_elementwise_max(a, b); }  // v_pk_max_u16
 template <bool MAX>
 __device__ __forceinline__ u16x2 pop(u16x2 a, u16x2 b) { return MAX ? pmax(a, b) : pmin(a, b); }
-__device__ __forceinline__ u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
-__device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-
-// 16 bytes of frame: RGBA rows are dword-aligned, gray8 rows may start at any byte
-typedef u32x4 __attribute__((aligned(1))) u32x4_a1;
-typedef u32x4 __attribute__((aligned(4))) u32x4_a4;
-template <bool G8>
-using px_chunk = typename std::conditional<G8, u32x4_a1, u32x4_a4>::type;
 
 constexpr int pow2_floor(int k) { return k >= 16 ? 16 : k >= 8 ? 8 : k >= 4 ? 4 : k >= 2 ? 2 : 1; }
 
@@ -136,11 +122,8 @@ __device__ __forceinline__ void minmax_stage(uint32_t* raw, uint32_t* hb)
             const uint32_t* src = raw + (size_t)(row0 + i) * G::RAWP + col;
             u16x2 rb[NR + K - 1], ga[NR + K - 1], orb[NR], oga[NR];
 #pragma unroll
-            for (int j = 0; j < NR + K - 1; j++) {
-                const uint32_t p = src[j];
-                rb[j] = as_u16x2(p & 0x00FF00FFu);                          // (R, B)
-                ga[j] = as_u16x2(__builtin_amdgcn_perm(0u, p, 0x0C030C01u));  // (G, A)
-            }
+            for (int j = 0; j < NR + K - 1; j++)
+                split_rgba(src[j], rb[j], ga[j]);
             window_min<NR, K, MAX>(rb, orb);
             window_min<NR, K, MAX>(ga, oga);
             uint32_t* d0 = hb + (size_t)i * G::HBP + q * NWR;
@@ -202,7 +185,7 @@ __device__ __forceinline__ void minmax_stage(uint32_t* raw, uint32_t* hb)
 #pragma unroll
             for (int j = 0; j < NV; j++)
                 if (t0 + j < OH)
-                    dst[(size_t)j * G::RAWP] = as_u32(orb[j]) | (as_u32(oga[j]) << 8);
+                    dst[(size_t)j * G::RAWP] = join_rgba(orb[j], oga[j]);
         } else {
             const uint32_t* s0 = hb + (size_t)t0 * G::HBP + c;
             u16x2 v[NV + K - 1], o[NV];
@@ -239,13 +222,11 @@ __global__ __launch_bounds__(kMorThreads) void morph_kernel(const uint8_t* __res
     __shared__ __attribute__((aligned(16))) uint32_t raw[G::RAW_DW];
     __shared__ __attribute__((aligned(16))) uint32_t hb[G::HB_DW];
     const int tid = threadIdx.x;
-    const int tx = blockIdx.x % tiles_x;
-    const int ty = (blockIdx.x / tiles_x) % tiles_y;
-    const size_t frame = blockIdx.x / ((unsigned)tiles_x * tiles_y);
+    const TilePos tp = tile_decode(blockIdx.x, tiles_x, tiles_y, G::TW, G::TH);  // no XCD remap: not measured here
     const size_t fbytes = (size_t)w * h * BPP;
-    const uint8_t* fin = in + frame * fbytes;
-    uint8_t* fout = out + frame * fbytes;
-    const int x0 = tx * G::TW, y0 = ty * G::TH;
+    const uint8_t* fin = in + tp.frame * fbytes;
+    uint8_t* fout = out + tp.frame * fbytes;
+    const int x0 = tp.x0, y0 = tp.y0;
     uint8_t* raw8 = reinterpret_cast<uint8_t*>(raw);
 
     // load: raw row a, column l = frame (clamp(y0 - H + a), clamp(x0 - HC + l))
@@ -258,7 +239,7 @@ __global__ __launch_bounds__(kMorThreads) void morph_kernel(const uint8_t* __res
             const uint8_t* row = fin + (size_t)gy * w * BPP;
             u32x4 v;
             if (gx >= 0 && gx + PXC <= w) {
-                v = *reinterpret_cast<const px_chunk<G8>*>(row + (size_t)gx * BPP);
+                v = *reinterpret_cast<const chunk16<BPP>*>(row + (size_t)gx * BPP);
             } else if constexpr (!G8) {
                 const uint32_t* r32 = reinterpret_cast<const uint32_t*>(row);
 #pragma unroll
@@ -315,17 +296,7 @@ __global__ __launch_bounds__(kMorThreads) void morph_kernel(const uint8_t* __res
             continue;
         const uint32_t* sp = raw + (size_t)(G::H + t) * G::RAWP_DW + (G::HC * BPP) / 4 + 4 * j;
         const u32x4 v = {sp[0], sp[1], sp[2], sp[3]};
-        uint8_t* row = fout + (size_t)gy * w * BPP;
-        if (gx + PXC <= w) {
-            *reinterpret_cast<px_chunk<G8>*>(row + (size_t)gx * BPP) = v;
-        } else if constexpr (!G8) {
-            uint32_t* r32 = reinterpret_cast<uint32_t*>(row);
-            for (int p = 0; gx + p < w; p++)
-                r32[gx + p] = v[p];
-        } else {
-            for (int p = 0; gx + p < w; p++)
-                row[gx + p] = (uint8_t)(v[p >> 2] >> (8 * (p & 3)));
-        }
+        store_chunk16<BPP>(fout + (size_t)gy * w * BPP, gx, w, v);
     }
 }
 
@@ -333,37 +304,9 @@ template <bool G8, int K, int OP>
 hipError_t launch_k(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes)
 {
     using G = Geom<G8, K, (OP >= 2)>;
-    const int tiles_x = (w + G::TW - 1) / G::TW, tiles_y = (h + G::TH - 1) / G::TH;
-    const uint64_t nblocks = (uint64_t)tiles_x * tiles_y * nframes;
-    if (nblocks > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL((morph_kernel<G8, K, OP>), dim3((unsigned)nblocks), dim3(kMorThreads), 0, stream, d_in, d_out,
-                       w, h, tiles_x, tiles_y);
-    return hipGetLastError();
-}
-
-template <bool G8, int OP>
-hipError_t launch_any_k(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k)
-{
-    switch (k) {
-    case 3: return launch_k<G8, 3, OP>(stream, d_in, d_out, w, h, nframes);
-    case 5: return launch_k<G8, 5, OP>(stream, d_in, d_out, w, h, nframes);
-    case 7: return launch_k<G8, 7, OP>(stream, d_in, d_out, w, h, nframes);
-    case 9: return launch_k<G8, 9, OP>(stream, d_in, d_out, w, h, nframes);
-    case 11: return launch_k<G8, 11, OP>(stream, d_in, d_out, w, h, nframes);
-    case 13: return launch_k<G8, 13, OP>(stream, d_in, d_out, w, h, nframes);
-    case 15: return launch_k<G8, 15, OP>(stream, d_in, d_out, w, h, nframes);
-    case 17: return launch_k<G8, 17, OP>(stream, d_in, d_out, w, h, nframes);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int OP>
-hipError_t launch_op(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k,
-                     bool gray8)
-{
-    return gray8 ? launch_any_k<true, OP>(stream, d_in, d_out, w, h, nframes, k)
-                 : launch_any_k<false, OP>(stream, d_in, d_out, w, h, nframes, k);
+    const TileGrid g(w, h, nframes, G::TW, G::TH);
+    return launch_tiles(morph_kernel<G8, K, OP>, g, kMorThreads, 0, kLdsDefault, stream, d_in, d_out, w, h, g.tiles_x,
+                        g.tiles_y);
 }
 
 }  // namespace
@@ -371,15 +314,16 @@ hipError_t launch_op(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, in
 hipError_t launch_morph(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k,
                         int op, bool gray8)
 {
-    static_assert(MI355_MAX_MORPH_K == 17, "launch_any_k instantiates k = 3 .. 17");
+    static_assert(MI355_MAX_MORPH_K == 17, "the list below instantiates k = 3 .. 17");
     if (k < 3 || k > MI355_MAX_MORPH_K || (k & 1) == 0 || op < 0 || op > 3)
         return hipErrorInvalidValue;
-    switch (op) {
-    case 0: return launch_op<0>(stream, d_in, d_out, w, h, nframes, k, gray8);
-    case 1: return launch_op<1>(stream, d_in, d_out, w, h, nframes, k, gray8);
-    case 2: return launch_op<2>(stream, d_in, d_out, w, h, nframes, k, gray8);
-    default: return launch_op<3>(stream, d_in, d_out, w, h, nframes, k, gray8);
-    }
+    return dispatch_int(op, std::make_integer_sequence<int, 4>{}, [&](auto OP) {
+        return dispatch_int(k, std::integer_sequence<int, 3, 5, 7, 9, 11, 13, 15, 17>{}, [&](auto K) {
+            constexpr int kc = decltype(K)::value, opc = decltype(OP)::value;
+            return gray8 ? launch_k<true, kc, opc>(stream, d_in, d_out, w, h, nframes)
+                         : launch_k<false, kc, opc>(stream, d_in, d_out, w, h, nframes);
+        });
+    });
 }
 
 }  // namespace mi355

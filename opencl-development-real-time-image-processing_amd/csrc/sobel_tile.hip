@@ -19,16 +19,33 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "slide_common.hpp"
+#include "tile_common.hpp"
 
 namespace mi355 {
 
 namespace {
 
-constexpr int kTW = 64;
-constexpr int kTH = 16;
-constexpr int kThreads = 256;
-constexpr int kLW = kTW + 2;  // luma tile with 1-px halo
-constexpr int kLH = kTH + 2;
+constexpr int kLW = kRgbaTW + 2;  // luma tile with 1-px halo
+constexpr int kLH = kRgbaTH + 2;
+
+// LDS carve of the pipeline kernel, shared with its launcher (offsets in 4-byte words):
+// [G float GH*GW] [V float kLH*GW (FAST)] [B int kLH*kLW] [weights]
+struct PipeTileLayout {
+    int GW, GH, off_v, off_b, off_wt, bytes;
+};
+
+__host__ __device__ inline PipeTileLayout pipe_tile_layout(bool exact, int k)
+{
+    PipeTileLayout L{};
+    const int R = k >> 1;
+    L.GW = kRgbaTW + 2 * R + 2;
+    L.GH = kRgbaTH + 2 * R + 2;
+    L.off_v = L.GH * L.GW;
+    L.off_b = L.off_v + (exact ? 0 : kLH * L.GW);
+    L.off_wt = L.off_b + kLH * kLW;
+    L.bytes = (L.off_wt + (exact ? k * k : k)) * 4;
+    return L;
+}
 
 // Sobel of the luma tile L (kLH x kLW ints in LDS) -> 4 consecutive pixels per thread.
 __device__ __forceinline__ void sobel_from_tile(const int* L, uint8_t* fout, int w, int h, int x0,
@@ -66,26 +83,21 @@ __device__ __forceinline__ void sobel_from_tile(const int* L, uint8_t* fout, int
     }
 }
 
-__global__ __launch_bounds__(kThreads) void sobel_tile_kernel(const uint32_t* __restrict__ in,
+__global__ __launch_bounds__(kRgbaTileThreads) void sobel_tile_kernel(const uint32_t* __restrict__ in,
                                                               uint8_t* __restrict__ out, int w, int h,
                                                               int tiles_x, int tiles_y,
                                                               uint32_t ntiles, int vec_store)
 {
     __shared__ int L[kLH * kLW];
-    const uint32_t tile = xcd_remap(blockIdx.x, ntiles);
-    const int tx = tile % tiles_x;
-    const int ty = (tile / tiles_x) % tiles_y;
-    const size_t frame = tile / ((uint32_t)tiles_x * tiles_y);
-    const uint32_t* fin = in + frame * (size_t)w * h;
-    uint8_t* fout = out + frame * (size_t)w * h;
-    const int x0 = tx * kTW, y0 = ty * kTH;
+    const TilePos t = tile_decode(xcd_remap(blockIdx.x, ntiles), tiles_x, tiles_y, kRgbaTW, kRgbaTH);
+    const uint32_t* fin = in + t.frame * (size_t)w * h;
+    uint8_t* fout = out + t.frame * (size_t)w * h;
+    const int x0 = t.x0, y0 = t.y0;
     const int tid = threadIdx.x;
 
-    for (int i = tid; i < kLH * kLW; i += kThreads) {
+    for (int i = tid; i < kLH * kLW; i += kRgbaTileThreads) {
         const int ly = i / kLW, lx = i - ly * kLW;
-        // positions beyond (w, h) are never consumed by a stored pixel: fold them onto w / h first
-        const int py = min(y0 - 1 + ly, h), px = min(x0 - 1 + lx, w);
-        const int gy = reflect101(py, h), gx = reflect101(px, w);
+        const int gy = border_index<kBorderReflect101>(y0 - 1 + ly, h), gx = border_index<kBorderReflect101>(x0 - 1 + lx, w);
         L[i] = (int)luma_px_fast(fin[(size_t)gy * w + gx]);
     }
     __syncthreads();
@@ -93,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void sobel_tile_kernel(const uint32_t* __
 }
 
 template <bool EXACT>
-__global__ __launch_bounds__(kThreads) void pipeline_tile_kernel(const uint32_t* __restrict__ in,
+__global__ __launch_bounds__(kRgbaTileThreads) void pipeline_tile_kernel(const uint32_t* __restrict__ in,
                                                                  uint8_t* __restrict__ out, int w,
                                                                  int h, int tiles_x, int tiles_y,
                                                                  int k, const float* __restrict__ d_wt,
@@ -101,37 +113,34 @@ __global__ __launch_bounds__(kThreads) void pipeline_tile_kernel(const uint32_t*
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int R = k >> 1;
-    const int GW = kTW + 2 * R + 2, GH = kTH + 2 * R + 2;
-    // carve: [G float GH*GW] [V float kLH*GW (FAST)] [B int kLH*kLW] [weights]
+    const PipeTileLayout L = pipe_tile_layout(EXACT, k);
+    const int GW = L.GW, GH = L.GH;
     float* G = reinterpret_cast<float*>(smem);
-    float* V = G + GH * GW;
-    int* B = reinterpret_cast<int*>(V + (EXACT ? 0 : kLH * GW));
-    float* wt = reinterpret_cast<float*>(B + kLH * kLW);
+    float* V = G + L.off_v;
+    int* B = reinterpret_cast<int*>(G + L.off_b);
+    float* wt = G + L.off_wt;
 
-    const uint32_t tile = xcd_remap(blockIdx.x, ntiles);
-    const int tx = tile % tiles_x;
-    const int ty = (tile / tiles_x) % tiles_y;
-    const size_t frame = tile / ((uint32_t)tiles_x * tiles_y);
-    const uint32_t* fin = in + frame * (size_t)w * h;
-    uint8_t* fout = out + frame * (size_t)w * h;
-    const int x0 = tx * kTW, y0 = ty * kTH;
+    const TilePos t = tile_decode(xcd_remap(blockIdx.x, ntiles), tiles_x, tiles_y, kRgbaTW, kRgbaTH);
+    const uint32_t* fin = in + t.frame * (size_t)w * h;
+    uint8_t* fout = out + t.frame * (size_t)w * h;
+    const int x0 = t.x0, y0 = t.y0;
     const int tid = threadIdx.x;
 
     const int nwt = EXACT ? k * k : k;
-    for (int i = tid; i < nwt; i += kThreads)
+    for (int i = tid; i < nwt; i += kRgbaTileThreads)
         wt[i] = d_wt[i];
     // gray tile, clamp-to-edge: G(ly,lx) <-> image (y0-1-R+ly, x0-1-R+lx)
-    for (int i = tid; i < GH * GW; i += kThreads) {
+    for (int i = tid; i < GH * GW; i += kRgbaTileThreads) {
         const int ly = i / GW, lx = i - ly * GW;
-        const int gy = clampi(y0 - 1 - R + ly, 0, h - 1);
-        const int gx = clampi(x0 - 1 - R + lx, 0, w - 1);
+        const int gy = border_index<kBorderClamp>(y0 - 1 - R + ly, h);
+        const int gx = border_index<kBorderClamp>(x0 - 1 - R + lx, w);
         G[i] = luma_px_fast(fin[(size_t)gy * w + gx]);
     }
     __syncthreads();
 
     // blurred-and-regrayed tile: B(by,bx) <-> image (y0-1+by, x0-1+bx)
     if constexpr (EXACT) {
-        for (int i = tid; i < kLH * kLW; i += kThreads) {
+        for (int i = tid; i < kLH * kLW; i += kRgbaTileThreads) {
             const int by = i / kLW, bx = i - by * kLW;
             float s = 0.0f;
             for (int ky = 0; ky < k; ky++) {
@@ -144,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void pipeline_tile_kernel(const uint32_t*
             B[i] = (int)luma_rgb(b, b, b);
         }
     } else {
-        for (int i = tid; i < kLH * GW; i += kThreads) {
+        for (int i = tid; i < kLH * GW; i += kRgbaTileThreads) {
             const int by = i / GW, cx = i - by * GW;
             const float* col = G + by * GW + cx;
             float v = wt[0] * col[0];
@@ -153,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void pipeline_tile_kernel(const uint32_t*
             V[i] = v;
         }
         __syncthreads();
-        for (int i = tid; i < kLH * kLW; i += kThreads) {
+        for (int i = tid; i < kLH * kLW; i += kRgbaTileThreads) {
             const int by = i / kLW, bx = i - by * kLW;
             const float* vr = V + by * GW + bx;
             float o = wt[0] * vr[0];
@@ -167,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void pipeline_tile_kernel(const uint32_t*
     // Sobel reads the blurred image with BORDER_REFLECT_101: halo positions that fall outside the
     // image (x = -1, x = w, y = -1, y = h) take the value of their mirror, which is an in-image
     // position of this same tile.  Only out-of-image entries are written, only in-image ones read.
-    for (int i = tid; i < kLH * kLW; i += kThreads) {
+    for (int i = tid; i < kLH * kLW; i += kRgbaTileThreads) {
         const int by = i / kLW, bx = i - by * kLW;
         const int iy = y0 - 1 + by, ix = x0 - 1 + bx;
         const bool oy = (iy < 0 || iy >= h), ox = (ix < 0 || ix >= w);
@@ -188,15 +197,10 @@ hipError_t launch_sobel(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out,
 {
     if (impl != 1 && sobel_slide_supported(d_in, d_out, w, h))
         return launch_sobel_slide(stream, d_in, d_out, w, h, nframes);
-    const int tiles_x = (w + kTW - 1) / kTW, tiles_y = (h + kTH - 1) / kTH;
-    const size_t ntiles = (size_t)tiles_x * tiles_y * nframes;
-    if (ntiles > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
+    const TileGrid g(w, h, nframes, kRgbaTW, kRgbaTH);
     const int vec = ((w & 3) == 0) && ((reinterpret_cast<uintptr_t>(d_out) & 3u) == 0);
-    hipLaunchKernelGGL(sobel_tile_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, stream,
-                       reinterpret_cast<const uint32_t*>(d_in), d_out, w, h, tiles_x, tiles_y,
-                       (uint32_t)ntiles, vec);
-    return hipGetLastError();
+    return launch_tiles(sobel_tile_kernel, g, kRgbaTileThreads, 0, kLdsDefault, stream, reinterpret_cast<const uint32_t*>(d_in),
+                        d_out, w, h, g.tiles_x, g.tiles_y, g.n(), vec);
 }
 
 hipError_t launch_pipeline(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h,
@@ -219,35 +223,12 @@ hipError_t launch_pipeline(hipStream_t stream, const uint8_t* d_in, uint8_t* d_o
     }
     if (impl != 1 && pipe_slide_supported(d_in, d_out, w, h, coef, 4))
         return launch_pipe_slide(stream, d_in, d_out, w, h, nframes, coef, 4);
-    const int k = coef.k, R = k / 2;
-    const int tiles_x = (w + kTW - 1) / kTW, tiles_y = (h + kTH - 1) / kTH;
-    const size_t ntiles = (size_t)tiles_x * tiles_y * nframes;
-    if (ntiles > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
-    const int GW = kTW + 2 * R + 2, GH = kTH + 2 * R + 2;
-    size_t lds = (size_t)GH * GW * 4 + (size_t)kLH * kLW * 4 + (size_t)(exact ? k * k : k) * 4;
-    if (!exact)
-        lds += (size_t)kLH * GW * 4;
+    const TileGrid g(w, h, nframes, kRgbaTW, kRgbaTH);
+    const PipeTileLayout L = pipe_tile_layout(exact, coef.k);
     const int vec = ((w & 3) == 0) && ((reinterpret_cast<uintptr_t>(d_out) & 3u) == 0);
-    hipError_t e;
-    if (exact) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(pipeline_tile_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(pipeline_tile_kernel<true>, dim3((unsigned)ntiles), dim3(kThreads), lds,
-                           stream, reinterpret_cast<const uint32_t*>(d_in), d_out, w, h, tiles_x,
-                           tiles_y, k, coef.d_w2d, (uint32_t)ntiles, vec);
-    } else {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(pipeline_tile_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(pipeline_tile_kernel<false>, dim3((unsigned)ntiles), dim3(kThreads), lds,
-                           stream, reinterpret_cast<const uint32_t*>(d_in), d_out, w, h, tiles_x,
-                           tiles_y, k, coef.d_w1d, (uint32_t)ntiles, vec);
-    }
-    return hipGetLastError();
+    return launch_tiles(exact ? pipeline_tile_kernel<true> : pipeline_tile_kernel<false>, g, kRgbaTileThreads, L.bytes, kLdsRaise,
+                        stream, reinterpret_cast<const uint32_t*>(d_in), d_out, w, h, g.tiles_x, g.tiles_y, coef.k,
+                        exact ? coef.d_w2d : coef.d_w1d, g.n(), vec);
 }
 
 }  // namespace mi355

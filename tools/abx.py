@@ -9,6 +9,8 @@ the builds are timed alternately on one input pool and one output pool.
     python3 tools/abx.py --libs B,ab/lib_x.so,ab/lib_y.so [--rounds 3] [--launches 12] -- <workload> [-- <workload> ...]
     workload: --filter gauss --k 5 --frames 256 --width 3840 --height 2160 [--random-alpha | --alpha-const 128 |
               --alpha-split] [--synth-mode N] [--mode exact] [--impl valu]
+    --filter: gray gray1 gauss sobel pipeline, gauss_gray8 sobel_gray8 pipeline_gray8, median[_gray8],
+              erode dilate open close [_gray8]; the *_gray8 inputs are seeded noise (the alpha / photo options are RGBA's)
 "B" = the in-tree product build, "T" = the in-tree tuning build.  Prints one line per (workload, build): median
 TB/s over the rounds, all rounds, and the output checksum (builds that should agree bit for bit must print the same).
 """
@@ -21,8 +23,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
-ALGO_BPP = {"gauss": 8, "gray": 8, "gray1": 5, "sobel": 5, "pipeline": 5}
-FILTER_ID = {"gray": 0, "gray1": 1, "gauss": 2, "sobel": 3, "pipeline": 4}
+FILTER_ID = {"gray": 0, "gray1": 1, "gauss": 2, "sobel": 3, "pipeline": 4,
+             "gauss_gray8": 5, "sobel_gray8": 6, "pipeline_gray8": 7, "median": 16, "median_gray8": 17,
+             "erode": 24, "dilate": 25, "open": 26, "close": 27,
+             "erode_gray8": 28, "dilate_gray8": 29, "open_gray8": 30, "close_gray8": 31}
 
 
 def workload_parser():
@@ -68,6 +72,13 @@ def main():
     hargs = hp.parse_args(head)
     if not sets:
         sets = [[]]
+    # the alpha / photo options edit a 4-channel input: refuse them on one-byte filters before any GPU work
+    for s in sets:
+        a = workload_parser().parse_args(s)
+        if a.filter not in FILTER_ID:
+            hp.error("unknown --filter %s (one of: %s)" % (a.filter, " ".join(FILTER_ID)))
+        if a.filter.endswith("_gray8") and (a.photo or a.random_alpha or a.alpha_split or a.alpha_const >= 0 or a.then_alpha >= 0):
+            hp.error("--filter %s has a one-byte input: --photo and the --*alpha* options are for RGBA filters" % a.filter)
 
     import torch
     pkg = entry.load_package()
@@ -116,10 +127,15 @@ def main():
         a = wp.parse_args(s)
         w, h, F = a.width, a.height, a.frames
         filt = FILTER_ID[a.filter]
-        out_bpp = pkg.imgfilter.OUT_BPP[filt]
-        d_in = torch.empty((F, h, w, 4), dtype=torch.uint8, device=dev)
+        in_bpp, out_bpp = pkg.imgfilter._in_bpp(filt), pkg.imgfilter._out_bpp(filt)
         d_out = torch.empty((F, h, w, out_bpp), dtype=torch.uint8, device=dev)
-        builds[0][1].synth_dev(d_in.data_ptr(), w, h, F, first_frame=0, seed=0x5EED, mode=a.synth_mode)
+        if in_bpp == 1:  # single-channel input: seeded noise (the synthetic scenes are RGBA)
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(0x5EED)
+            d_in = torch.randint(0, 256, (F, h, w, 1), dtype=torch.uint8, device=dev, generator=gen)
+        else:
+            d_in = torch.empty((F, h, w, 4), dtype=torch.uint8, device=dev)
+            builds[0][1].synth_dev(d_in.data_ptr(), w, h, F, first_frame=0, seed=0x5EED, mode=a.synth_mode)
         if a.photo:
             import numpy as np
             from PIL import Image
@@ -141,7 +157,7 @@ def main():
         for _, ctx in builds:
             ctx.set_gauss_mode(pkg.GAUSS_EXACT if a.mode == "exact" else pkg.GAUSS_FAST)
             ctx.set_impl({"auto": pkg.IMPL_AUTO, "tile": pkg.IMPL_TILE, "mfma": pkg.IMPL_MFMA, "valu": pkg.IMPL_VALU}[a.impl])
-        algo = ALGO_BPP[a.filter] * F * w * h
+        algo = (in_bpp + out_bpp) * F * w * h  # algorithmic bytes: every pixel read once and written once
         res = {label: [] for label, _ in builds}
         sums = {}
         # clocks up before the first timed round
