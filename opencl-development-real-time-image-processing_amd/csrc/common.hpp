@@ -12,10 +12,48 @@
 #include <stdint.h>
 
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 
 namespace mi355 {
 
 constexpr int kWave = 64;
+
+// ---- host: launch-time choices as template arguments, and the predicates the launchers share -----------------------
+// f(std::integral_constant<int, K>{}) for the K of the list that equals v; hipErrorInvalidValue when none does
+template <int... Ks, typename F>
+hipError_t dispatch_int(int v, std::integer_sequence<int, Ks...>, F&& f)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Ks && ((e = f(std::integral_constant<int, Ks>{})), true)) || ...);
+    return e;
+}
+
+// f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+hipError_t dispatch_bool(bool v, F&& f)
+{
+    return v ? f(std::true_type{}) : f(std::false_type{});
+}
+
+inline bool aligned_to(const void* p, size_t n)  // n a power of two
+{
+    return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0;
+}
+
+// RGBA rows that the 16-byte row accesses of the aligned instantiations cannot take: a width that is no multiple of 4, or
+// a buffer short of the alignment its accesses assume -> the RAGGED instantiation
+inline bool rows_ragged(int w, const void* d_in, size_t in_align, const void* d_out, size_t out_align)
+{
+    return (w & 3) != 0 || !aligned_to(d_in, in_align) || !aligned_to(d_out, out_align);
+}
+
+// float -> u8 needs its upper clamp (the CLAMP instantiations) unless 255 * (sum of the separable factor)^2 stays below
+// 256: every normalised Gaussian does, externally installed tables may not.  slack widens the test for the caller.
+inline bool gauss_upper_clamp(double wsum, double slack = 0.0)
+{
+    return !(255.0 * wsum * wsum * 1.0001 + slack < 256.0);
+}
 
 // MI355_TUNE_* environment overrides (band heights, strip widths, kernel selection) exist for tuning sweeps
 // and for the test that proves outputs do not depend on the work decomposition.  They are compiled in only
@@ -264,6 +302,19 @@ __device__ __forceinline__ int reflect101(int p, int len)
 __device__ __forceinline__ int clampi(int v, int lo, int hi)
 {
     return v < lo ? lo : (v > hi ? hi : v);
+}
+
+// clamp: BORDER_REPLICATE (Gaussian, median, morphology); reflect101: BORDER_REFLECT_101 (Sobel).  Positions beyond
+// len are never consumed by a stored pixel; folding them onto len first bounds reflect101's loop to one turn.
+enum Border { kBorderClamp, kBorderReflect101 };
+
+template <Border B>
+__device__ __forceinline__ int border_index(int p, int len)
+{
+    if constexpr (B == kBorderClamp)
+        return clampi(p, 0, len - 1);
+    else
+        return reflect101(min(p, len), len);
 }
 
 // float -> u8 exactly as the CPU path: uchar(std::clamp(sum, 0.f, 255.f)) (truncation)

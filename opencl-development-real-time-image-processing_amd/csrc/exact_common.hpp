@@ -11,20 +11,9 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "slide_common.hpp"
 
 namespace mi355 {
-
-__device__ __forceinline__ float dppl(float v)  // lane l <- lane l-1
-{
-    return __builtin_bit_cast(float,
-                              __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, true));
-}
-
-__device__ __forceinline__ float dppr(float v)  // lane l <- lane l+1
-{
-    return __builtin_bit_cast(float,
-                              __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
-}
 
 // The CPU path's own sum for pixel J of every lane (GaussianBlur.cpp:243-256: ky outer, kx inner, float multiply
 // then float add, starting from 0), from the ring of gray rows: the window's arrival rows sit in slots
@@ -43,7 +32,7 @@ __device__ __forceinline__ float exact_sum(const float (&g)[K][PX], int u, const
 #pragma unroll
         for (int kx = 0; kx < K; kx++) {
             const int col = J - R + kx;
-            const float val = (col < 0) ? dppl(r[PX + col]) : ((col > PX - 1) ? dppr(r[col - PX]) : r[col]);
+            const float val = (col < 0) ? dpp_left(r[PX + col]) : ((col > PX - 1) ? dpp_right(r[col - PX]) : r[col]);
             sum = sum + val * w2[ky * K + kx];  // -ffp-contract=off: v_mul_f32 then v_add_f32
         }
     }
@@ -98,10 +87,10 @@ __device__ __forceinline__ void flat_windows(const float (&g)[K][PX], float (&S)
     }
 #pragma unroll
     for (int i = 0; i < R; i++) {
-        mn[R - 1 - i] = dppl(mn[R + PX - 1 - i]);  // column -1 - i = the left lane's column PX - 1 - i
-        mx[R - 1 - i] = dppl(mx[R + PX - 1 - i]);
-        mn[R + PX + i] = dppr(mn[R + i]);          // column PX + i = the right lane's column i
-        mx[R + PX + i] = dppr(mx[R + i]);
+        mn[R - 1 - i] = dpp_left(mn[R + PX - 1 - i]);  // column -1 - i = the left lane's column PX - 1 - i
+        mx[R - 1 - i] = dpp_left(mx[R + PX - 1 - i]);
+        mn[R + PX + i] = dpp_right(mn[R + i]);          // column PX + i = the right lane's column i
+        mx[R + PX + i] = dpp_right(mx[R + i]);
     }
 #pragma unroll
     for (int J = 0; J < PX; J++) {
@@ -199,8 +188,8 @@ __device__ __forceinline__ void exact_blur_row(const float (&g)[K][PX], int u, b
 #pragma unroll
         for (int d = 1; d <= R; d++) {
             const int a = px - d, b = px + d;
-            const float va = (a < 0) ? dppl(v.a[PX + a]) : v.a[a];
-            const float vb = (b > PX - 1) ? dppr(v.a[b - PX]) : v.a[b];
+            const float va = (a < 0) ? dpp_left(v.a[PX + a]) : v.a[a];
+            const float vb = (b > PX - 1) ? dpp_right(v.a[b - PX]) : v.a[b];
             acc = __builtin_fmaf(wv[d], va + vb, acc);
         }
         S[px] = acc;

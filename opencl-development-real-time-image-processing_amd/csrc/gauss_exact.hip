@@ -32,13 +32,10 @@ namespace mi355 {
 
 namespace {
 
-constexpr int kWavesPerBlock = kSlideWavesPerBlock;
-
 template <int R, bool CLAMP>
-__global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const uint8_t* __restrict__ in,
-                                                                         uint8_t* __restrict__ out, int w, int h,
-                                                                         int nstrips, int lanes_out, BandPlan plan,
-                                                                         ExactTables<2 * R + 1> tab, uint32_t alpha255)
+__global__ __launch_bounds__(kSlideWavesPerBlock * 64) void gauss_exact_kernel(
+    const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int w, int h, int nstrips, int lanes_out, BandPlan plan,
+    ExactTables<2 * R + 1> tab, uint32_t alpha255)
 {
     constexpr int K = 2 * R + 1;
     __shared__ float flat[256];  // flat[c] = the CPU path's chain over a window that is c everywhere (exact_common.hpp)
@@ -48,28 +45,16 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const 
     SlideItem it;
     if (!slide_item(plan, nstrips, h, &it))
         return;  // after the only barrier
-    const int strip = it.strip, y0 = it.y0, nout = it.nout;
-    const size_t frame = it.frame;
     const bool up = (it.band & 1) != 0;  // wave-uniform
-
-    const int q_lane = strip * lanes_out + lane - 1;
-    const int quads = w >> 2;  // w % 4 == 0 (gauss_exact_supported)
-    const int q_load = clampi(q_lane, 0, min(quads - 1, (strip + 1) * lanes_out));  // idle lanes re-load the halo quad
-    const bool left_of_image = q_lane < 0, right_of_image = q_lane >= quads;
-    const bool edge_strip = (strip == 0) || (4 * (strip * lanes_out + 63) > w);  // wave-uniform
-    const int q_end = min((strip + 1) * lanes_out, quads);
-    const bool stores = (lane >= 1) && (q_lane < q_end);
-
-    // output rows y0 .. y0+nout-1 need input rows y0-R .. y0+nout-1+R; arrival index i counts them in walking order
-    const int nin = nout + 2 * R;
-    const int y_first = up ? y0 + nout - 1 + R : y0 - R;
-    const int y_step = up ? -1 : 1;
+    const SlideGeom G = slide_geom<4>(it.strip, lanes_out, lane, w, 16u, 16u);  // w % 4 == 0 (gauss_exact_supported)
+    // output rows y0 .. y0+nout-1 need input rows y0-R .. y0+nout-1+R, clamp-to-edge (GaussianBlur.cpp:241)
+    const BandWalk W = band_walk(up, it.y0, it.nout, R, h);
+    const int nin = W.nin, nout = it.nout;
 
     const size_t row_bytes = (size_t)w * 4;
-    const auto fin = uniform_ptr(in + frame * row_bytes * h);
-    const auto fout = uniform_ptr(out + frame * row_bytes * h);
-    uint32_t in_off = (uint32_t)q_load * 16u;
-    uint32_t out_off = (uint32_t)(stores ? q_lane : 0) * 16u;
+    const auto fin = uniform_ptr(in + it.frame * row_bytes * h);
+    const auto fout = uniform_ptr(out + it.frame * row_bytes * h);
+    uint32_t in_off = G.in_off, out_off = G.out_off;
 
     float wv[R + 1];  // wv[d] = weight at distance d from the centre
 #pragma unroll
@@ -78,8 +63,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const 
     const float delta = tab.delta, two_delta = 2.0f * tab.delta;
 
     auto load_row = [&](int i) -> u32x4 {
-        const int y = clampi(y_first + y_step * min(i, nin - 1), 0, h - 1);  // clamp-to-edge rows (GaussianBlur.cpp:241)
-        const auto rowp = fin + (size_t)y * row_bytes;
+        const auto rowp = fin + (size_t)in_row<kBorderClamp>(W, i) * row_bytes;
         lane_offset_here(in_off);
         return gload<u32x4>(rowp + in_off);
     };
@@ -124,12 +108,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const 
                     if (__builtin_amdgcn_ballot_w64(a < 0xFF000000u) != 0 && i < nin)
                         return false;
                 }
-                if (edge_strip) {
-                    if (left_of_image)
-                        p = u32x4{p.x, p.x, p.x, p.x};  // clamp-to-edge columns: replicate column 0
-                    if (right_of_image)
-                        p = u32x4{p.w, p.w, p.w, p.w};  // replicate column w-1
-                }
+                if (G.edge_strip)
+                    edge_clamp_cols(p, G.left_of_image, G.right_of_image);
 #pragma unroll
                 for (int c = 0; c < NCH; c++)
 #pragma unroll
@@ -144,8 +124,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const 
                         // at k = 7: with the ring of 4 x 7 rows its extra live values push the kernel from 198 VGPRs into
                         // scratch memory.
                         float S[4];
-                        exact_blur_row<K, 4, CLAMP, (R <= 2)>(g[c], u, up, wv, delta, two_delta, tab.w2, flat, stores, -1,
-                                                              S);
+                        exact_blur_row<K, 4, CLAMP, (R <= 2)>(g[c], u, up, wv, delta, two_delta, tab.w2, flat, G.stores,
+                                                              -1, S);
 #pragma unroll
                         for (int e = 0; e < 4; e++)
                             px[e] |= (uint32_t)S[e] << (8 * c);  // uchar(clamp(sum, 0, 255)): truncation
@@ -156,9 +136,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void gauss_exact_kernel(const 
                             px[e] |= alpha_hi;
                     }
                     const int cidx = i - 2 * R;  // completed output row in arrival order
-                    const int m = up ? y0 + nout - 1 - cidx : y0 + cidx;
-                    if (stores && cidx < nout) {
-                        const auto rowp = fout + (size_t)m * row_bytes;
+                    if (G.stores && cidx < nout) {
+                        const auto rowp = fout + (size_t)out_row(W, cidx) * row_bytes;
                         lane_offset_here(out_off);
                         gstore_nt<u32x4>(rowp + out_off, u32x4{px[0], px[1], px[2], px[3]});
                     }
@@ -191,15 +170,11 @@ hipError_t launch_r(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int
         chain += 255.0f * coef.h_w2d[j];
     chain = chain < 0.0f ? 0.0f : (chain > 255.0f ? 255.0f : chain);
     const uint32_t alpha255 = (uint32_t)chain << 24;  // already shifted to bits 31:24
-    const bool clamp = !(255.0 * wsum * wsum * 1.0001 + 0.01 < 256.0);
-    const dim3 grid(plan.nblocks_a + plan.nblocks_b), block(kWavesPerBlock * 64);
-    if (clamp)
-        hipLaunchKernelGGL((gauss_exact_kernel<R, true>), grid, block, 0, stream, d_in, d_out, w, h, sp.nstrips, sp.lanes_out,
-                           plan, tab, alpha255);
-    else
-        hipLaunchKernelGGL((gauss_exact_kernel<R, false>), grid, block, 0, stream, d_in, d_out, w, h, sp.nstrips, sp.lanes_out,
-                           plan, tab, alpha255);
-    return hipGetLastError();
+    // (the 0.01 on top of the shared test is this launcher's own, of unrecorded origin: kept as it is)
+    return dispatch_bool(gauss_upper_clamp(wsum, 0.01), [&](auto CL) {
+        return launch_slide(gauss_exact_kernel<R, CL.value>, plan, stream, d_in, d_out, w, h, sp.nstrips, sp.lanes_out,
+                            plan, tab, alpha255);
+    });
 }
 
 }  // namespace
@@ -212,7 +187,7 @@ bool gauss_exact_supported(const uint8_t* d_in, const uint8_t* d_out, int w, int
     const int k = coef.k;
     if (k != 3 && k != 5 && k != 7)
         return false;
-    if ((w & 3) != 0 || ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) != 0)
+    if (rows_ragged(w, d_in, 16, d_out, 16))
         return false;
     return exact_tables_ok(coef);
 }
@@ -220,12 +195,8 @@ bool gauss_exact_supported(const uint8_t* d_in, const uint8_t* d_out, int w, int
 hipError_t launch_gauss_exact(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                               const GaussCoef& coef)
 {
-    switch (coef.k) {
-    case 3: return launch_r<1>(stream, d_in, d_out, w, h, nframes, coef);
-    case 5: return launch_r<2>(stream, d_in, d_out, w, h, nframes, coef);
-    case 7: return launch_r<3>(stream, d_in, d_out, w, h, nframes, coef);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_int(coef.k, std::integer_sequence<int, 3, 5, 7>{},
+                        [&](auto K) { return launch_r<K.value / 2>(stream, d_in, d_out, w, h, nframes, coef); });
 }
 
 }  // namespace mi355

@@ -342,7 +342,7 @@ bool gauss_mfma_reg_supported(const uint8_t* d_in, const uint8_t* d_out, int w, 
 {
     if (coef.k > 17 || coef.k < 3 || !coef.separable || !coef.h_w2d)
         return false;
-    if ((w & 3) != 0 || ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) != 0)
+    if ((w & 3) != 0 || !aligned_to(d_in, 16) || !aligned_to(d_out, 16))
         return false;
     if ((size_t)w * h * 4 >= 0x7FFFFFFFull)
         return false;

@@ -39,26 +39,10 @@ namespace mi355 {
 
 namespace {
 
-constexpr int kWavesPerBlock = kSlideWavesPerBlock;
-
 template <int K>
 struct Weights {
     float w[K];
 };
-
-__device__ __forceinline__ float dpp_from_left(float v)
-{
-    // lane l <- lane l-1 (lane 0 gets 0: it is a halo lane, its result is never stored)
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, true));
-}
-
-__device__ __forceinline__ float dpp_from_right(float v)
-{
-    // lane l <- lane l+1 (lane 63 gets 0: never an output lane)
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
-}
 
 __device__ __forceinline__ float ubyte_f32(uint32_t p, int c)
 {
@@ -197,14 +181,13 @@ struct SlideLane {
     global_ptr<const uint8_t> fin;  // wave-uniform frame bases, pinned in SGPR pairs (slide_common.hpp)
     global_ptr<uint8_t> fout;
     size_t row_bytes;
-    uint32_t in_off, out_off;
+    SlideGeom g;  // (RAGGED, w >= 4: g.in_off is the shifted load's, see edge)
     int y0, nout, nin, h;
-    bool left_of_image, right_of_image, edge_strip, stores;
     // RAGGED variant (width % 4 != 0 or buffers not 16-byte aligned): lanes of an edge strip that overlap the row's right
     // end load the row's last four pixels and shift them into place (slide_common.hpp: RaggedEdge; six v_cndmask per row,
     // edge strips only, no divergent branch).  Images narrower than 4 pixels keep the per-pixel form (px_off).
     uint32_t px_off[4];   // w < 4: byte offsets of the 4 (clamped) pixels inside a row
-    int x_lane, w;        // first pixel of the lane (may be < 0 or >= w), image width
+    int w;
     RaggedEdge edge;
 };
 
@@ -247,18 +230,16 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
 {
     constexpr int K = 2 * R + 1;
     static_assert((NCH == 4) == (AMODE == 0), "AMODE 1 / 2 belong to the 3-channel pass");
-    uint32_t in_off = L.in_off, out_off = L.out_off;
+    uint32_t in_off = L.g.in_off, out_off = L.g.out_off;
+    const BandWalk W = band_walk(UP, L.y0, L.nout, R, L.h);  // an UP band walks from its bottom-most input row up
     // AMODE 2: (A ^ 0xFF) << 24 for the alpha value A the rows seen last carry — alpha_hi = alpha_tab[A] — and how many
     // consecutive rows, the current one included, carry it.  The first row sets them (run = 0 forces the first test to
     // take the "value changes" branch only if the row is not 255; 255 is where alpha_hi starts).
     uint32_t cur_nA = 0u;
     int run = 0;
     auto load_row = [&](int i) -> u32x4 {
-        // rows past the band's last input re-read that last row (an L1/L2 hit, never consumed); an UP band
-        // walks from its bottom-most input row to its top-most one
-        const int ii = min(i, L.nin - 1);
-        const int y = clampi(UP ? L.y0 + L.nout - 1 + R - ii : L.y0 - R + ii, 0, L.h - 1);
-        const auto rowp = L.fin + (size_t)y * L.row_bytes;  // SGPR pair; + 32-bit lane offset = saddr form
+        // SGPR pair; + 32-bit lane offset = saddr form
+        const auto rowp = L.fin + (size_t)in_row<kBorderClamp>(W, i) * L.row_bytes;
         if constexpr (R <= 2)  // (k = 9: the asm statements keep hipcc from unrolling the trip; k = 7: -4 %)
             lane_offset_here(in_off);
         if constexpr (RAGGED) {
@@ -321,15 +302,15 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
                 __builtin_amdgcn_s_barrier();
             }
             q[(u + PF) % K] = load_row(i + PF);
-            if (L.edge_strip) {  // wave-uniform
+            if (L.g.edge_strip) {  // wave-uniform
+                // (in place, not edge_clamp_cols: slide_common.hpp says why)
                 if constexpr (!RAGGED) {
-                    // halo lanes outside the image replicate the edge pixel (clamp-to-edge columns)
-                    if (L.left_of_image)
+                    if (L.g.left_of_image)
                         p = u32x4{p.x, p.x, p.x, p.x};
-                    if (L.right_of_image)
+                    if (L.g.right_of_image)
                         p = u32x4{p.w, p.w, p.w, p.w};
                 } else if (L.w >= 4) {
-                    if (L.left_of_image)
+                    if (L.g.left_of_image)
                         p = u32x4{p.x, p.x, p.x, p.x};
                     ragged_shift_clamp(p, L.edge);  // lanes past the row's end: pixel w - 1 replicated
                 }
@@ -432,9 +413,9 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
                                 const int s = px - R + t;
                                 float src;
                                 if (s < 0)
-                                    src = dpp_from_left(v[(4 + s) * NCH + c]);
+                                    src = dpp_left(v[(4 + s) * NCH + c]);
                                 else if (s > 3)
-                                    src = dpp_from_right(v[(s - 4) * NCH + c]);
+                                    src = dpp_right(v[(s - 4) * NCH + c]);
                                 else
                                     src = v[s * NCH + c];
                                 sum = (t == 0) ? wv[0] * src : __builtin_fmaf(wv[t], src, sum);
@@ -446,15 +427,15 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
                             o[px] |= alpha_hi;
                     }
                 }
-                if (L.stores) {
-                    const auto rowp = L.fout + (size_t)(UP ? L.y0 + L.nout - 1 - m : L.y0 + m) * L.row_bytes;
+                if (L.g.stores) {
+                    const auto rowp = L.fout + (size_t)out_row(W, m) * L.row_bytes;
                     if constexpr (R <= 2)
                         lane_offset_here(out_off);
                     if constexpr (RAGGED) {
-                        if (L.edge_strip && L.x_lane + 3 >= L.w) {  // the last quad of a row may be partial
+                        if (L.g.edge_strip && L.g.x_lane + 3 >= L.w) {  // the last quad of a row may be partial
 #pragma unroll
                             for (int j = 0; j < 4; j++)
-                                if (L.x_lane + j < L.w)
+                                if (L.g.x_lane + j < L.w)
                                     gstore_a4<uint32_t>(rowp + out_off + 4 * j, o[j]);
                         } else {
                             gstore_a4<u32x4>(rowp + out_off, o);
@@ -475,12 +456,11 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
 // instead of 2).  Kernel MODE 3 leaves flags[work] = 0 (band done) or 1; kernel MODE 4 redoes the flagged bands
 // and exits at once everywhere else (gauss_wide.hip does the same).
 template <int R, bool CLAMP, bool RAGGED, int MODE, bool LOCKSTEP>
-__global__ __launch_bounds__(kWavesPerBlock * 64, (R == 3 && MODE == 3) ? 3 : 1) void gauss_slide_kernel(
+__global__ __launch_bounds__(kSlideWavesPerBlock * 64, (R == 3 && MODE == 3) ? 3 : 1) void gauss_slide_kernel(
     const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int w, int h, int nstrips, int lanes_out,
     BandPlan plan, Weights<2 * R + 1> wts, uint32_t alpha_hi, const uint32_t* __restrict__ alpha_tab,
     uint32_t* __restrict__ flags)
 {
-    const int quads = (w + 3) >> 2;  // RAGGED: the last quad of a row may hold fewer than 4 pixels
     constexpr int K = 2 * R + 1;
     const int lane = threadIdx.x & 63;
     SlideItem it;
@@ -490,38 +470,24 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (R == 3 && MODE == 3) ? 3 : 1)
         if (flags[it.work] == 0)  // wave-uniform
             return;
     }
-    const int strip = it.strip;
-
-    const int q_lane = strip * lanes_out + lane - 1;  // this lane's pixel-quad column
-    // replicated at the image border; lanes right of the strip's right halo lane (never read by a storing lane)
-    // re-load the halo quad instead of the next strip's data
-    const int q_load = clampi(q_lane, 0, min(quads - 1, (strip + 1) * lanes_out));
-    const int q_end = min((strip + 1) * lanes_out, quads);
     SlideLane L;
-    L.left_of_image = q_lane < 0;
-    L.right_of_image = q_lane >= quads;
-    // edge strip = a wave that touches pixels outside [0, w): wave-uniform
-    L.edge_strip = (strip == 0) || (4 * (strip * lanes_out + 63) > w);
-    L.stores = (lane >= 1) && (q_lane < q_end);
+    L.g = slide_geom<4>(it.strip, lanes_out, lane, w, 16u, 16u);  // RAGGED: the last quad of a row may be partial
     L.y0 = it.y0;
     L.nout = it.nout;
     L.nin = it.nout + 2 * R;
     L.h = h;
     L.w = w;
-    L.x_lane = 4 * q_lane;
     L.row_bytes = (size_t)w * 4;
     L.fin = uniform_ptr(in + it.frame * L.row_bytes * h);  // uniform base; lanes add a 32-bit offset
     L.fout = uniform_ptr(out + it.frame * L.row_bytes * h);
-    L.in_off = (uint32_t)q_load * 16u;
-    L.out_off = (uint32_t)(L.stores ? q_lane : 0) * 16u;
     L.edge = RaggedEdge{false, false, false, false};
     if constexpr (RAGGED) {
         if (w >= 4)
-            L.in_off = ragged_edge_setup(q_lane, q_load, w, &L.edge);
+            L.g.in_off = ragged_edge_setup(L.g.q_lane, L.g.q_load, w, &L.edge);
     }
 #pragma unroll
     for (int j = 0; j < 4; j++)
-        L.px_off[j] = (uint32_t)clampi(4 * q_lane + j, 0, w - 1) * 4u;
+        L.px_off[j] = (uint32_t)clampi(L.g.x_lane + j, 0, w - 1) * 4u;
 
     // weights live in VGPRs: the DPP forms (v_mul_f32_dpp / v_fmac_f32_dpp) take no SGPR operand
     float wv[K];
@@ -603,54 +569,41 @@ hipError_t launch_r(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int
     if (!slide_plan<R>(w, h, nframes, &sp, &plan) || (kSplit && !d_flags))
         return hipErrorInvalidValue;
     const int nstrips = sp.nstrips, lanes_out = sp.lanes_out;
-    const bool ragged = (w & 3) != 0 ||
-                        (((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) != 0);
+    const bool ragged = rows_ragged(w, d_in, 16, d_out, 16);
     Weights<K> wts;
     for (int j = 0; j < K; j++)
         wts.w[j] = coef.h_w1d[j];
     double wsum = 0.0;
     for (int j = 0; j < K; j++)
         wsum += (double)coef.h_w1d[j];
-    const bool clamp = !(255.0 * wsum * wsum * 1.0001 < 256.0);  // externally installed tables may overflow
     // constant alpha bytes of the fast path: the canonical chains on an all-A channel, evaluated by the host when
     // the table was installed (kernels.hpp: gauss_const_alpha); A = 255, the usual case, travels by value
     if (!coef.d_alpha_tab)
         return hipErrorInvalidValue;
     const uint32_t alpha_hi = coef.h_alpha_tab[255];
     const uint32_t* alpha_tab = coef.d_alpha_tab;
-    const dim3 grid(plan.nblocks_a + plan.nblocks_b), block(kWavesPerBlock * 64);
-    // lock-step rows (see the row loop) where a workgroup is kWavesPerBlock adjacent strips of one band — with 5 strips
-    // per row (width 1023) the coupled waves belong to different bands and the same barrier costs 4 %, on one-strip
-    // frames 7 % — and the launch is several times what the chip holds at once (1-4 4K frames, cache-resident: -1.2 %)
-    const bool lockstep = R <= 2 && !ragged && nstrips % kWavesPerBlock == 0 && plan.nwork_b == 0 && plan.nwork_a >= 8192u;
-#define MI355_LAUNCH1(CL, RG, MD, LS)                                                                               \
-    hipLaunchKernelGGL((gauss_slide_kernel<R, CL, RG, MD, LS>), grid, block, 0, stream, d_in, d_out, w, h, nstrips, \
-                       lanes_out, plan, wts, alpha_hi, alpha_tab, d_flags)
-#define MI355_LAUNCH(CL, RG)                  \
-    do {                                      \
-        if constexpr (kSplit) {               \
-            MI355_LAUNCH1(CL, RG, 3, false);  \
-            MI355_LAUNCH1(CL, RG, 4, false);  \
-        } else if constexpr (!RG) {           \
-            if (lockstep)                     \
-                MI355_LAUNCH1(CL, RG, 0, true);  \
-            else                              \
-                MI355_LAUNCH1(CL, RG, 0, false); \
-        } else {                              \
-            MI355_LAUNCH1(CL, RG, 0, false);  \
-        }                                     \
-    } while (0)
-    if (clamp && ragged)
-        MI355_LAUNCH(true, true);
-    else if (clamp)
-        MI355_LAUNCH(true, false);
-    else if (ragged)
-        MI355_LAUNCH(false, true);
-    else
-        MI355_LAUNCH(false, false);
-#undef MI355_LAUNCH
-#undef MI355_LAUNCH1
-    return hipGetLastError();
+    // lock-step rows (see the row loop) where a workgroup is kSlideWavesPerBlock adjacent strips of one band — with 5
+    // strips per row (width 1023) the coupled waves belong to different bands and the same barrier costs 4 %, on
+    // one-strip frames 7 % — and the launch is several times what the chip holds at once (1-4 4K frames, cache-resident: -1.2 %)
+    const bool lockstep =
+        R <= 2 && !ragged && nstrips % kSlideWavesPerBlock == 0 && plan.nwork_b == 0 && plan.nwork_a >= 8192u;
+    auto launch = [&](auto kernel) {
+        return launch_slide(kernel, plan, stream, d_in, d_out, w, h, nstrips, lanes_out, plan, wts, alpha_hi, alpha_tab,
+                            d_flags);
+    };
+    return dispatch_bool(gauss_upper_clamp(wsum), [&](auto CL) {  // externally installed tables may overflow
+        return dispatch_bool(ragged, [&](auto RG) {
+            if constexpr (kSplit) {
+                const hipError_t e = launch(gauss_slide_kernel<R, CL.value, RG.value, 3, false>);
+                return e != hipSuccess ? e : launch(gauss_slide_kernel<R, CL.value, RG.value, 4, false>);
+            } else if constexpr (RG.value) {
+                return launch(gauss_slide_kernel<R, CL.value, true, 0, false>);
+            } else {
+                return dispatch_bool(
+                    lockstep, [&](auto LS) { return launch(gauss_slide_kernel<R, CL.value, false, 0, LS.value>); });
+            }
+        });
+    });
 }
 
 }  // namespace
@@ -662,32 +615,26 @@ bool gauss_slide_supported(const uint8_t* d_in, const uint8_t* d_out, int w, int
     if (k != 3 && k != 5 && k != 7 && k != 9)
         return false;
     // any width: rows that are not 16-byte aligned take the RAGGED variant; pixels are dwords
-    return ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u) == 0;
+    return aligned_to(d_in, 4) && aligned_to(d_out, 4);
 }
 
 size_t gauss_slide_flag_items(int w, int h, int nframes, int k)
 {
     StripPlan sp;
     BandPlan plan;
-    bool ok = false;
-    switch (k) {  // only the two-kernel variants (k = 7, 9) use flags
-    case 7: ok = slide_plan<3>(w, h, nframes, &sp, &plan); break;
-    case 9: ok = slide_plan<4>(w, h, nframes, &sp, &plan); break;
-    default: break;
-    }
-    return ok ? (size_t)plan.nwork_a + plan.nwork_b : 0;
+    // only the two-kernel variants (k = 7, 9) use flags
+    const hipError_t e = dispatch_int(k, std::integer_sequence<int, 7, 9>{}, [&](auto K) {
+        return slide_plan<K.value / 2>(w, h, nframes, &sp, &plan) ? hipSuccess : hipErrorInvalidValue;
+    });
+    return e == hipSuccess ? (size_t)plan.nwork_a + plan.nwork_b : 0;
 }
 
 hipError_t launch_gauss_slide(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h,
                               int nframes, const GaussCoef& coef, uint32_t* d_flags)
 {
-    switch (coef.k) {
-    case 3: return launch_r<1>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
-    case 5: return launch_r<2>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
-    case 7: return launch_r<3>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
-    case 9: return launch_r<4>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_int(coef.k, std::integer_sequence<int, 3, 5, 7, 9>{}, [&](auto K) {
+        return launch_r<K.value / 2>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
+    });
 }
 
 }  // namespace mi355

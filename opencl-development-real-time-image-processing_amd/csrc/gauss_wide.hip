@@ -26,9 +26,6 @@ namespace mi355 {
 
 namespace {
 
-constexpr int kWavesPerBlock = kSlideWavesPerBlock;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-
 template <int K>
 struct WWeights {
     float w[K];
@@ -40,9 +37,8 @@ struct WideLane {
     f32x4* vr;  // this wave's LDS row: entry R + p holds pixel p of the strip (p = 0..127), R padding entries per
                 // side; even entries first, then odd entries (see gauss_wide_band)
     size_t row_bytes;
-    uint32_t in_off, out_off;
+    SlideGeom g;
     int y0, nout, nin, h, lane;
-    bool left_of_image, right_of_image, edge_strip, stores;
 };
 
 // One pass over the band with NCH channels per pixel: 4 = general; 3 = opaque fast path (see gauss_slide.hip):
@@ -51,9 +47,9 @@ template <int R, int NCH>
 __device__ __forceinline__ bool gauss_wide_band(const WideLane& L, const float (&wv)[2 * R + 1], uint32_t alpha_hi)
 {
     constexpr int K = 2 * R + 1;
+    const BandWalk W = band_walk(false, L.y0, L.nout, R, L.h);
     auto load_row = [&](int i) -> u32x2 {
-        const int y = clampi(L.y0 - R + min(i, L.nin - 1), 0, L.h - 1);
-        return *reinterpret_cast<const u32x2*>(L.fin + (size_t)y * L.row_bytes + L.in_off);
+        return *reinterpret_cast<const u32x2*>(L.fin + (size_t)in_row<kBorderClamp>(W, i) * L.row_bytes + L.g.in_off);
     };
     constexpr int PF = 3;
     u32x2 q[K];
@@ -83,10 +79,10 @@ __device__ __forceinline__ bool gauss_wide_band(const WideLane& L, const float (
             const int i = base + u;  // rows of a last partial trip run with their store masked off
             u32x2 p = q[u];
             q[(u + PF) % K] = load_row(i + PF);
-            if (L.edge_strip) {
-                if (L.left_of_image)
+            if (L.g.edge_strip) {
+                if (L.g.left_of_image)
                     p = u32x2{p.x, p.x};  // clamp-to-edge columns: replicate pixel 0
-                if (L.right_of_image)
+                if (L.g.right_of_image)
                     p = u32x2{p.y, p.y};  // replicate pixel w-1
             }
             if constexpr (NCH == 3) {
@@ -144,7 +140,7 @@ __device__ __forceinline__ bool gauss_wide_band(const WideLane& L, const float (
                 // (and the next row's stores must stay behind this row's reads)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-                if (L.stores && m < L.nout) {
+                if (L.g.stores && m < L.nout) {
                     // uchar(clamp(v, 0, 255)) = floor, then v_cvt_pk_u8_f32 (exact on integers, saturates both ways,
                     // inserts the byte): 2 ops per channel instead of max + min + cvt + shift + or
                     u32x2 r;
@@ -156,7 +152,7 @@ __device__ __forceinline__ bool gauss_wide_band(const WideLane& L, const float (
                         r.y = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_floorf(o1[c]), (uint32_t)c, r.y);
                     }
                     __builtin_nontemporal_store(
-                        r, reinterpret_cast<u32x2*>(L.fout + (size_t)(L.y0 + m) * L.row_bytes + L.out_off));
+                        r, reinterpret_cast<u32x2*>(L.fout + (size_t)out_row(W, m) * L.row_bytes + L.g.out_off));
                 }
             }
         }
@@ -166,13 +162,13 @@ __device__ __forceinline__ bool gauss_wide_band(const WideLane& L, const float (
 
 // NCH = 3: kernel A (opaque pass, writes flags[work]); NCH = 4: kernel B (redoes the bands kernel A flagged)
 template <int R, int NCH>
-__global__ __launch_bounds__(kWavesPerBlock * 64, (NCH == 3 && R <= 6) ? 3 : 2) void gauss_wide_kernel(
+__global__ __launch_bounds__(kSlideWavesPerBlock * 64, (NCH == 3 && R <= 6) ? 3 : 2) void gauss_wide_kernel(
     const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int pairs /* w/2 */, int h, int nstrips,
     int lanes_out, BandPlan plan, WWeights<2 * R + 1> wts, uint32_t alpha_hi, uint32_t* __restrict__ flags)
 {
     constexpr int K = 2 * R + 1;
     constexpr int H = (R + 1) / 2;  // halo lanes per side (2 px each)
-    __shared__ f32x4 vrow[kWavesPerBlock][128 + 2 * R + 2];  // two planes of (128 + 2R + 2) / 2 entries
+    __shared__ f32x4 vrow[kSlideWavesPerBlock][128 + 2 * R + 2];  // two planes of (128 + 2R + 2) / 2 entries
     SlideItem it;
     if (!slide_item(plan, nstrips, h, &it))
         return;
@@ -183,14 +179,9 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (NCH == 3 && R <= 6) ? 3 : 2) 
     WideLane L;
     L.vr = vrow[threadIdx.x >> 6];
     L.lane = threadIdx.x & 63;
-    const int strip = it.strip;
-    const int q_lane = strip * lanes_out + L.lane - H;  // this lane's pixel-pair column
-    const int q_load = clampi(q_lane, 0, pairs - 1);
-    const int q_end = min((strip + 1) * lanes_out, pairs);
-    L.left_of_image = q_lane < 0;
-    L.right_of_image = q_lane >= pairs;
-    L.edge_strip = (strip == 0) || (strip * lanes_out + 64 - H > pairs);  // wave-uniform
-    L.stores = (L.lane >= H) && (q_lane < q_end);
+    // a lane's pixel pair is the "quad"; idle lanes keep loading their own (clamped) pair: which lines they touch is part
+    // of the measured kernel
+    L.g = slide_geom<2, H, false>(it.strip, lanes_out, L.lane, 2 * pairs, 8u, 8u);
     L.y0 = it.y0;
     L.nout = it.nout;
     L.nin = it.nout + 2 * R;
@@ -198,8 +189,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (NCH == 3 && R <= 6) ? 3 : 2) 
     L.row_bytes = (size_t)pairs * 8;
     L.fin = in + it.frame * L.row_bytes * h;
     L.fout = out + it.frame * L.row_bytes * h;
-    L.in_off = (uint32_t)q_load * 8u;
-    L.out_off = (uint32_t)(L.stores ? q_lane : 0) * 8u;
 
     float wv[K];
 #pragma unroll
@@ -236,21 +225,16 @@ hipError_t launch_r(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int
     WWeights<K> wts;
     for (int j = 0; j < K; j++)
         wts.w[j] = coef.h_w1d[j];
-    // constant alpha byte of the opaque fast path: the canonical chains on an all-255 channel, in float
-    float vc = wts.w[0] * 255.0f;
-    for (int t = 1; t < K; t++)
-        vc = std::fmaf(wts.w[t], 255.0f, vc);
-    float hc = wts.w[0] * vc;
-    for (int t = 1; t < K; t++)
-        hc = std::fmaf(wts.w[t], vc, hc);
-    hc = hc < 0.0f ? 0.0f : (hc > 255.0f ? 255.0f : hc);
-    const uint32_t alpha_hi = (uint32_t)hc << 24;
-    const dim3 grid(plan.nblocks_a + plan.nblocks_b), block(kWavesPerBlock * 64);
-    hipLaunchKernelGGL((gauss_wide_kernel<R, 3>), grid, block, 0, stream, d_in, d_out, pairs, h, nstrips, lanes_out,
-                       plan, wts, alpha_hi, d_flags);
-    hipLaunchKernelGGL((gauss_wide_kernel<R, 4>), grid, block, 0, stream, d_in, d_out, pairs, h, nstrips, lanes_out,
-                       plan, wts, alpha_hi, d_flags);
-    return hipGetLastError();
+    // constant alpha byte of the opaque fast path: gauss_const_alpha(h_w1d, k, 255) << 24, as in gauss_slide.hip
+    if (!coef.d_alpha_tab)
+        return hipErrorInvalidValue;
+    const uint32_t alpha_hi = coef.h_alpha_tab[255];
+    auto launch = [&](auto kernel) {
+        return launch_slide(kernel, plan, stream, d_in, d_out, pairs, h, nstrips, lanes_out, plan, wts, alpha_hi,
+                            d_flags);
+    };
+    const hipError_t e = launch(gauss_wide_kernel<R, 3>);
+    return e != hipSuccess ? e : launch(gauss_wide_kernel<R, 4>);
 }
 
 }  // namespace
@@ -262,34 +246,28 @@ bool gauss_wide_supported(const uint8_t* d_in, const uint8_t* d_out, int w, int 
         return false;
     if ((w & 1) != 0)
         return false;
-    return ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 7u) == 0;
+    return aligned_to(d_in, 8) && aligned_to(d_out, 8);
 }
+
+constexpr std::integer_sequence<int, 11, 13, 15, 17> kWideKs{};
 
 size_t gauss_wide_flag_items(int w, int h, int nframes, int k)
 {
     int pairs, nstrips, lanes_out;
     BandPlan plan;
-    bool ok = false;
-    switch (k) {
-    case 11: ok = wide_plan<5>(w, h, nframes, pairs, nstrips, lanes_out, &plan); break;
-    case 13: ok = wide_plan<6>(w, h, nframes, pairs, nstrips, lanes_out, &plan); break;
-    case 15: ok = wide_plan<7>(w, h, nframes, pairs, nstrips, lanes_out, &plan); break;
-    case 17: ok = wide_plan<8>(w, h, nframes, pairs, nstrips, lanes_out, &plan); break;
-    default: break;
-    }
-    return ok ? (size_t)plan.nwork_a + plan.nwork_b : 0;
+    const hipError_t e = dispatch_int(k, kWideKs, [&](auto K) {
+        return wide_plan<K.value / 2>(w, h, nframes, pairs, nstrips, lanes_out, &plan) ? hipSuccess
+                                                                                       : hipErrorInvalidValue;
+    });
+    return e == hipSuccess ? (size_t)plan.nwork_a + plan.nwork_b : 0;
 }
 
 hipError_t launch_gauss_wide(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                              const GaussCoef& coef, uint32_t* d_flags)
 {
-    switch (coef.k) {
-    case 11: return launch_r<5>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
-    case 13: return launch_r<6>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
-    case 15: return launch_r<7>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
-    case 17: return launch_r<8>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_int(coef.k, kWideKs, [&](auto K) {
+        return launch_r<K.value / 2>(stream, d_in, d_out, w, h, nframes, coef, d_flags);
+    });
 }
 
 }  // namespace mi355

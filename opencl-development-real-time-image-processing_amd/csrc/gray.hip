@@ -159,8 +159,7 @@ hipError_t launch_gray(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, 
                        int nframes, bool one_channel)
 {
     const size_t npx = (size_t)w * h * nframes;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(d_in) & 15u) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(d_out) & (one_channel ? 3u : 15u)) == 0);
+    const bool aligned = aligned_to(d_in, 16) && aligned_to(d_out, one_channel ? 4 : 16);
     const size_t nquads = aligned ? npx / 4 : 0;
     // grid-stride; measured on MI355X (profiles/r01_membench.txt): a flat 16 B/lane stream runs 5.3 TB/s with
     // 2,048 blocks, 6.2-6.4 TB/s with >= 8k blocks and non-temporal loads + stores; this kernel: 4.8 / 5.6 / 5.9 / 6.3 TB/s at 2k / 8k / 64k / 256k+ blocks
@@ -185,12 +184,9 @@ hipError_t launch_gray(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, 
         BandPlan plan;
         if (!make_band_plan(h, nstrips, nframes, 8, kStripRows, kStripRows, kStripRows, 0.0, 0, &plan))
             return hipErrorInvalidValue;
-        const dim3 grid(plan.nblocks_a + plan.nblocks_b), block(kSlideWavesPerBlock * 64);
-        if (one_channel)
-            hipLaunchKernelGGL(gray_strip_kernel<true>, grid, block, 0, stream, d_in, d_out, quads, h, nstrips, plan);
-        else
-            hipLaunchKernelGGL(gray_strip_kernel<false>, grid, block, 0, stream, d_in, d_out, quads, h, nstrips, plan);
-        return hipGetLastError();
+        return dispatch_bool(one_channel, [&](auto ONE_CH) {
+            return launch_slide(gray_strip_kernel<ONE_CH.value>, plan, stream, d_in, d_out, quads, h, nstrips, plan);
+        });
     }
     if (nquads) {
         const unsigned grid = grid_for(nquads, kGrayThreads * kGrayIlp, kCap);

@@ -300,7 +300,7 @@ hipError_t launch_image2d(hipStream_t stream, int filter, const uint8_t* d_in, u
     if (blocks > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     const uint32_t* in = reinterpret_cast<const uint32_t*>(d_in);
-    const bool in16 = (reinterpret_cast<uintptr_t>(d_in) & 15u) == 0, out4 = (reinterpret_cast<uintptr_t>(d_out) & 3u) == 0;
+    const bool in16 = aligned_to(d_in, 16), out4 = aligned_to(d_out, 4);
     // the per-pixel kernels below stay as the fallback (MI355_IMAGE2D_PLAIN=1 in the tuning build forces them: the A/B
     // partner and the test that both forms give the same bytes)
     const bool plain = tune_env("MI355_IMAGE2D_PLAIN") != nullptr;

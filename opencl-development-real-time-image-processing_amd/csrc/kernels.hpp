@@ -1,6 +1,7 @@
 // kernels.hpp — host-callable launchers of the gfx950 kernels (one .hip file each).
 // All launchers enqueue on `stream` and return the hipError_t of the launch.
-// The LDS-tiled kernels (gauss_tile, sobel_tile, gray8, morph, median, image2d) share their frame: tile_common.hpp.
+// The LDS-tiled kernels (gauss_tile, sobel_tile, gray8, morph, median, image2d) share their frame: tile_common.hpp;
+// the register-resident sliding-window kernels theirs: slide_common.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,7 +54,7 @@ hipError_t launch_gauss(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out,
 hipError_t launch_gauss_tile(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h,
                              int nframes, const GaussCoef& coef, bool exact);
 
-// register-resident sliding-window kernel (k = 3,5,7,9; width % 4 == 0; 16-byte aligned buffers)
+// register-resident sliding-window kernel (k = 3,5,7,9; any width, dword-aligned pointers)
 bool gauss_slide_supported(const uint8_t* d_in, const uint8_t* d_out, int w, int h, int k);
 size_t gauss_slide_flag_items(int w, int h, int nframes, int k);
 hipError_t launch_gauss_slide(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h,

@@ -49,8 +49,6 @@ namespace mi355 {
 
 namespace {
 
-constexpr int kWavesPerBlock = kSlideWavesPerBlock;
-
 // One input row of a lane: PX RGBA pixels, one 16-byte load per four.
 template <int PX>
 struct PixRow {
@@ -62,7 +60,7 @@ struct PixRow {
 // reflected column x = w of the blurred image may sit anywhere inside a lane.  PX = 4 only.
 // PX = 8 holds twice the registers per lane: it is compiled for 4 waves per SIMD (PX = 4 asks for nothing: 1).
 template <int R, int PX, bool CLAMP, bool RAGGED>
-__global__ __launch_bounds__(kWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_slide_kernel(
+__global__ __launch_bounds__(kSlideWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_slide_kernel(
     const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int w, int h, int nstrips,
     int lanes_out, BandPlan plan, ExactTables<2 * R + 1> tab)
 {
@@ -78,37 +76,26 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_sli
     SlideItem it;
     if (!slide_item(plan, nstrips, h, &it))
         return;  // (pipeline: after the only barrier)
-    const int strip = it.strip, y0 = it.y0, nout = it.nout;
-    const size_t frame = it.frame;
+    const int y0 = it.y0, nout = it.nout;
     const bool up = (it.band & 1) != 0;  // wave-uniform
 
-    // a "quad" is the PX pixels of one lane
-    const int q_lane = strip * lanes_out + lane - 1;
-    const int quads = (w + PX - 1) >> (PX == 8 ? 3 : 2);
-    const int q_load = clampi(q_lane, 0, min(quads - 1, (strip + 1) * lanes_out));  // idle lanes re-load the halo quad
-    const bool left_of_image = q_lane < 0, right_of_image = q_lane >= quads;
-    const bool edge_strip = (strip == 0) || (PX * (strip * lanes_out + 63) > w);  // wave-uniform
-    const int x_lane = PX * q_lane;
-    const int jw = w - x_lane;  // RAGGED: position of column x = w inside this lane, if 0 <= jw <= 3
-    const int q_end = min((strip + 1) * lanes_out, quads);
-    const bool stores = (lane >= 1) && (q_lane < q_end);
-    const int keep_px = (lane == 0) ? PX - 1 : ((q_lane == q_end) ? 0 : -1);  // the pixel a halo lane's neighbour reads
+    // a "quad" is the PX pixels of one lane; one byte out per pixel
+    const SlideGeom G = slide_geom<PX>(it.strip, lanes_out, lane, w, 4u * PX, (uint32_t)PX);
+    const int jw = w - G.x_lane;  // RAGGED: position of column x = w inside this lane, if 0 <= jw <= 3
+    // the pixel a halo lane's neighbour reads
+    const int keep_px = (lane == 0) ? PX - 1 : ((G.q_lane == G.q_end) ? 0 : -1);
 
-    // output rows y0 .. y0+nout-1 need blurred rows y0-1 .. y0+nout, which need gray rows y0-1-R .. y0+nout+R;
-    // "arrival index" i = 0 .. nin-1 counts them in walking order (top down, or bottom up for odd bands)
-    const int nin = nout + 2 + 2 * R;
-    const int y_first = up ? y0 + nout + R : y0 - 1 - R;
-    const int y_step = up ? -1 : 1;
+    // output rows y0 .. y0+nout-1 need blurred rows y0-1 .. y0+nout, which need gray rows y0-1-R .. y0+nout+R
+    // (clamp-to-edge)
+    const BandWalk W = band_walk(up, y0, nout, R + 1, h);
+    const int nin = W.nin;
 
     const size_t row_bytes = (size_t)w * 4;
-    const auto fin = uniform_ptr(in + frame * row_bytes * h);
-    const auto fout = uniform_ptr(out + frame * (size_t)w * h);
-    uint32_t in_off = (uint32_t)q_load * (4u * PX);
-    uint32_t out_off = (uint32_t)(stores ? q_lane : 0) * (uint32_t)PX;
+    const auto fin = uniform_ptr(in + it.frame * row_bytes * h);
+    const auto fout = uniform_ptr(out + it.frame * (size_t)w * h);
+    uint32_t in_off = G.in_off, out_off = G.out_off;
     uint32_t px_off[4];  // RAGGED edge strips: the gray image clamps
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-        px_off[j] = (uint32_t)clampi(x_lane + j, 0, w - 1) * 4u;
+    ragged_px_offsets<kBorderClamp>(G.x_lane, w, px_off);
 
     float wv[R + 1];  // wv[d] = weight at distance d from the centre
 #pragma unroll
@@ -117,20 +104,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_sli
     const float delta = tab.delta, two_delta = 2.0f * tab.delta;
 
     auto load_row = [&](int i) -> PixRow<PX> {
-        const int y = clampi(y_first + y_step * min(i, nin - 1), 0, h - 1);  // gray rows: clamp-to-edge
-        const auto rowp = fin + (size_t)y * row_bytes;  // SGPR pair; + 32-bit lane offset = saddr form
+        // SGPR pair; + 32-bit lane offset = saddr form
+        const auto rowp = fin + (size_t)in_row<kBorderClamp>(W, i) * row_bytes;
         lane_offset_here(in_off);
         PixRow<PX> r;
         if constexpr (RAGGED) {
-            // edge strips: only the lanes that overlap the row's ends address their pixels one by one; the others take
-            // the unaligned 16-byte access of the interior strips (gauss_slide.hip: +9 % at width 1023, +55 % at 427)
-            if (edge_strip && !(x_lane >= 0 && x_lane + 3 < w)) {
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    r.v[0][j] = gload<uint32_t>(rowp + px_off[j]);
-            } else {
-                r.v[0] = gload_a4<u32x4>(rowp + in_off);
-            }
+            r.v[0] = ragged_row_load(rowp, G, w, in_off, px_off);
         } else {
 #pragma unroll
             for (int n = 0; n < PX / 4; n++)
@@ -171,14 +150,14 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_sli
             PixRow<PX> p = q[u];
             q[(u + PF) % K] = load_row(i + PF);
             if constexpr (!RAGGED) {
-                if (edge_strip) {
-                    if (left_of_image) {  // gray image clamps: replicate column 0
+                if (G.edge_strip) {  // (in place, not edge_clamp_cols: slide_common.hpp says why)
+                    if (G.left_of_image) {  // gray image clamps: replicate column 0
                         const uint32_t c0 = p.v[0].x;
 #pragma unroll
                         for (int n = 0; n < PX / 4; n++)
                             p.v[n] = u32x4{c0, c0, c0, c0};
                     }
-                    if (right_of_image) {  // replicate column w-1
+                    if (G.right_of_image) {  // replicate column w-1
                         const uint32_t c1 = p.v[PX / 4 - 1].w;
 #pragma unroll
                         for (int n = 0; n < PX / 4; n++)
@@ -196,26 +175,26 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_sli
                 // the blurred row that just completed (window = arrival rows i-2R .. i = slots (u+1+t) % K); a halo
                 // lane owes its neighbour one blurred pixel, idle lanes none
                 float S[PX];
-                exact_blur_row<K, PX, CLAMP>(g, u, up, wv, delta, two_delta, tab.w2, flat, stores, keep_px, S);
+                exact_blur_row<K, PX, CLAMP>(g, u, up, wv, delta, two_delta, tab.w2, flat, G.stores, keep_px, S);
                 float* lb = l[s3];
 #pragma unroll
                 for (int px = 0; px < PX; px++) {
                     const uint32_t bq = (uint32_t)S[px];  // truncation, as the Gaussian call stores it
                     lb[px] = (float)lut[bq];              // luma(b,b,b) re-applied
                 }
-                if (edge_strip) {
+                if (G.edge_strip) {
                     // the blurred image reflects (BORDER_REFLECT_101): x = -1 <- x = 1, x = w <- x = w-2
-                    const float from_right = dppr(lb[1]);      // lane+1's pixel 1
-                    const float from_left = dppl(lb[PX - 2]);  // lane-1's last pixel but one
-                    if (left_of_image)
+                    const float from_right = dpp_right(lb[1]);      // lane+1's pixel 1
+                    const float from_left = dpp_left(lb[PX - 2]);  // lane-1's last pixel but one
+                    if (G.left_of_image)
                         lb[PX - 1] = from_right;
                     if constexpr (!RAGGED) {
-                        if (right_of_image)
+                        if (G.right_of_image)
                             lb[0] = from_left;
                     } else {
                         // column x = w is pixel jw of this lane; its mirror x = w-2 is pixel jw-2 of this
                         // lane or pixel jw+2 of the lane to the left (w >= 4 here)
-                        const float from_left3 = dppl(lb[3]);
+                        const float from_left3 = dpp_left(lb[3]);
                         const float l0 = lb[0], l1 = lb[1];
                         if (jw == 0)
                             lb[0] = from_left;
@@ -230,7 +209,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_sli
                 // blurred arrival row c = i - 2R sits at image row yb(c); the Sobel row between the last
                 // three blurred rows is m = yb(c - 1)
                 const int c = i - 2 * R;
-                const int m = up ? y0 + nout - c + 1 : y0 - 2 + c;
+                const int m = out_row(W, c - 2);
                 if (c >= 2 && m >= y0 && m < y0 + nout) {
                     const float* lm = l[(s3 + 2) % 3];  // blurred row m
                     const float* lo = l[(s3 + 1) % 3];  // the neighbour row that arrived first
@@ -256,8 +235,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_sli
                             cd[j] = lb[j] - lo[j];  // sign depends on the walking direction; only gy^2 is used
                         }
                     }
-                    const float csl = dppl(cs[PX - 1]), csr = dppr(cs[0]);
-                    const float cdl = dppl(cd[PX - 1]), cdr = dppr(cd[0]);
+                    const float csl = dpp_left(cs[PX - 1]), csr = dpp_right(cs[0]);
+                    const float cdl = dpp_left(cd[PX - 1]), cdr = dpp_right(cd[0]);
                     float gxs[PX], gys[PX];
 #pragma unroll
                     for (int j = 0; j < PX; j++) {
@@ -278,14 +257,14 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PX == 8 ? 4 : 1) void pipe_sli
                         asm volatile("" : "+v"(r[0]), "+v"(r[1]));
                     else
                         asm volatile("" : "+v"(r[0]));
-                    if (stores) {
+                    if (G.stores) {
                         const auto rowp = fout + (size_t)m * w;
                         lane_offset_here(out_off);
                         if constexpr (RAGGED) {
-                            if (edge_strip && x_lane + 3 >= w) {  // the last quad of a row may be partial
+                            if (G.edge_strip && G.x_lane + 3 >= w) {  // the last quad of a row may be partial
 #pragma unroll
                                 for (int j = 0; j < 4; j++)
-                                    if (x_lane + j < w)
+                                    if (G.x_lane + j < w)
                                         rowp[out_off + j] = (uint8_t)(r[0] >> (8 * j));
                             } else {
                                 gstore_a1<uint32_t>(rowp + out_off, r[0]);
@@ -349,27 +328,16 @@ hipError_t launch_r(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int
         return hipErrorInvalidValue;
     double wsum;
     const ExactTables<K> tab = make_exact_tables<K>(coef, &wsum);
-    const bool clamp = !(255.0 * wsum * wsum * 1.0001 < 256.0);
-    const bool ragged = PX == 4 && ((w & 3) != 0 || (reinterpret_cast<uintptr_t>(d_in) & 15u) != 0 ||
-                                    (reinterpret_cast<uintptr_t>(d_out) & 3u) != 0);
-    const dim3 grid(plan.nblocks_a + plan.nblocks_b), block(kWavesPerBlock * 64);
-#define MI355_LAUNCH(CL, RG)                                                                                    \
-    hipLaunchKernelGGL((pipe_slide_kernel<R, PX, CL, RG>), grid, block, 0, stream, d_in, d_out, w, h, nstrips,  \
-                       lanes_out, plan, tab)
-    if (ragged) {
-        if constexpr (PX == 4) {
-            if (clamp)
-                MI355_LAUNCH(true, true);
+    const bool ragged = PX == 4 && rows_ragged(w, d_in, 16, d_out, 4);
+    return dispatch_bool(gauss_upper_clamp(wsum), [&](auto CL) {
+        return dispatch_bool(ragged, [&](auto RG) {
+            if constexpr (PX == 4 || !RG.value)  // 8 pixels per lane: aligned rows only
+                return launch_slide(pipe_slide_kernel<R, PX, CL.value, RG.value>, plan, stream, d_in, d_out, w, h,
+                                    nstrips, lanes_out, plan, tab);
             else
-                MI355_LAUNCH(false, true);
-        }
-    } else if (clamp) {
-        MI355_LAUNCH(true, false);
-    } else {
-        MI355_LAUNCH(false, false);
-    }
-#undef MI355_LAUNCH
-    return hipGetLastError();
+                return hipErrorInvalidValue;  // (never reached: ragged implies PX == 4)
+        });
+    });
 }
 
 }  // namespace
@@ -382,26 +350,26 @@ bool pipe_slide_supported(const uint8_t* d_in, const uint8_t* d_out, int w, int 
     const int k = coef.k;
     if (k != 3 && k != 5 && k != 7)
         return false;
-    if (w < 4 || h < 2 || !exact_tables_ok(coef) || (reinterpret_cast<uintptr_t>(d_in) & 3u) != 0)
+    if (w < 4 || h < 2 || !exact_tables_ok(coef) || !aligned_to(d_in, 4))
         return false;
     if (px == 4)
         return true;
     if (px != 8 || k == 7 || (w & 7) != 0 || w < 16)
         return false;
-    return (reinterpret_cast<uintptr_t>(d_in) & 15u) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7u) == 0;
+    return aligned_to(d_in, 16) && aligned_to(d_out, 8);
 }
 
 hipError_t launch_pipe_slide(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                              const GaussCoef& coef, int px)
 {
-    switch (coef.k * 10 + px) {
-    case 34: return launch_r<1, 4>(stream, d_in, d_out, w, h, nframes, coef);
-    case 54: return launch_r<2, 4>(stream, d_in, d_out, w, h, nframes, coef);
-    case 74: return launch_r<3, 4>(stream, d_in, d_out, w, h, nframes, coef);
-    case 38: return launch_r<1, 8>(stream, d_in, d_out, w, h, nframes, coef);
-    case 58: return launch_r<2, 8>(stream, d_in, d_out, w, h, nframes, coef);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_int(coef.k, std::integer_sequence<int, 3, 5, 7>{}, [&](auto K) {
+        return dispatch_int(px, std::integer_sequence<int, 4, 8>{}, [&](auto PX) {
+            if constexpr (PX.value == 4 || K.value <= 5)  // 8 pixels per lane: k = 3, 5
+                return launch_r<K.value / 2, PX.value>(stream, d_in, d_out, w, h, nframes, coef);
+            else
+                return hipErrorInvalidValue;
+        });
+    });
 }
 
 }  // namespace mi355

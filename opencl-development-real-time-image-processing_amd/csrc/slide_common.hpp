@@ -1,5 +1,20 @@
-// slide_common.hpp — work decomposition shared by the register-resident sliding-window kernels
-// (gauss_slide.hip, sobel_slide.hip, pipe_slide.hip).
+// slide_common.hpp — the frame every register-resident sliding-window kernel shares (gauss_slide, gauss_exact,
+// gauss_wide, sobel_slide, pipe_slide, the strip kernel of gray; gauss_mfma_reg takes the strip plan only).
+//   host    StripPlan / BandPlan: how a batch is cut into work items; launch_slide: grid from the plan,
+//           kSlideWavesPerBlock waves per block, the launch error returned.
+//   device  slide_item: work item -> (frame, band, strip); slide_geom<PX>: what a lane of a strip with one halo lane per
+//           side loads, stores and replicates (gauss_wide: H halo lanes of pixel pairs, q_load without the cap);
+//           band_walk / in_row<B> / out_row: arrival index -> image row under the filter's border rule, completed row
+//           -> output row, walking down or up; dpp_left / dpp_right (+ _or): the neighbour lane's value;
+//           edge_clamp_cols / edge_reflect_cols: the halo lanes' column rule at load time; ragged_px_offsets<B> +
+//           ragged_row_load: the per-pixel edge loads of the RAGGED Sobel and pipeline (the Gaussian's shifted 16-byte
+//           form is RaggedEdge); uniform_ptr, lane_offset_here, gload / gstore.
+// Every device helper is __forceinline__.  What stays per kernel: lane_offset_here (it has to sit in the basic block of
+// its access, and gauss_slide wants it at R <= 2 only); gauss_wide's pixel-pair replication (u32x2); and the column
+// replication of gauss_slide and pipe_slide, written in place: hipcc returns edge_clamp_cols' two arms as selects, which
+// is free in gauss_exact's edge strips but took gauss_slide's k = 3 kernels from 82 to 79 VGPRs, 6 waves per SIMD where
+// the band plan was measured at 5 (profiles/slide_frame_vgpr.txt), and cost the pipeline's 8-pixel k = 5 kernel 1.3 % on
+// frames of flat patches, --synth-mode 2 (4.186 against 4.242 TB/s, profiles/slide_frame_ab.txt section 2).
 //
 // A work item is one wave walking one (frame, band of rows, strip of <= 62 lanes + 2 halo lanes).
 // Band height trades two costs measured on MI355X:
@@ -118,6 +133,14 @@ inline bool make_band_plan(int h, int nstrips, int nframes, int waves_per_simd, 
 }
 
 #ifdef __HIPCC__
+template <typename... KArgs, typename... Args>
+hipError_t launch_slide(void (*kernel)(KArgs...), const BandPlan& plan, hipStream_t stream, Args... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(plan.nblocks_a + plan.nblocks_b), dim3(kSlideWavesPerBlock * 64), 0, stream,
+                       static_cast<KArgs>(args)...);
+    return hipGetLastError();
+}
+
 // Pins a wave-uniform row pointer in an SGPR pair.  Without it hipcc reassociates `frame + y * row_bytes +
 // lane_offset` into (frame + lane_offset) + y * row_bytes and spends a v_mov + v_mad_u64_u32 + v_add per row
 // access; with it the access uses the `saddr + 32-bit voffset` form and the row address costs no VALU at all.
@@ -234,6 +257,117 @@ __device__ __forceinline__ bool slide_item(const BandPlan& plan, int nstrips, in
     it->y0 = (tail ? plan.y_split : 0) + band * band_rows;
     it->nout = min(band_rows, (tail ? h : plan.y_split) - it->y0);
     return true;
+}
+
+// The lane's place in its strip: 62 (or lanes_out) output lanes plus one halo lane per side, PX pixels per lane ("quad" =
+// the PX pixels of one lane; a ragged last quad counts).  Lanes outside the image load the edge quad and replicate or
+// reflect it (edge_*_cols); lanes right of the strip's right halo lane, never read by a storing lane, re-load the halo
+// quad (same cache line) instead of the next strip's data.  edge_strip (wave-uniform): the wave touches pixels outside
+// [0, w).  in_off / out_off: byte offsets inside a row, from the bytes a lane reads / writes per row.
+struct SlideGeom {
+    int q_lane, q_load, q_end, x_lane;
+    bool left_of_image, right_of_image, edge_strip, stores;
+    uint32_t in_off, out_off;
+};
+
+// HALO halo lanes per side; CAP_LOAD = false (gauss_wide): idle lanes load their own quad, clamped to the row only.
+template <int PX, int HALO = 1, bool CAP_LOAD = true>
+__device__ __forceinline__ SlideGeom slide_geom(int strip, int lanes_out, int lane, int w, uint32_t bytes_in,
+                                                uint32_t bytes_out)
+{
+    static_assert(HALO == 1 || !CAP_LOAD, "the cap is written for one halo lane");
+    const int quads = (w + PX - 1) >> (PX == 8 ? 3 : (PX == 4 ? 2 : 1));
+    SlideGeom g;
+    g.q_lane = strip * lanes_out + lane - HALO;
+    g.q_load = clampi(g.q_lane, 0, CAP_LOAD ? min(quads - 1, (strip + 1) * lanes_out) : quads - 1);
+    g.q_end = min((strip + 1) * lanes_out, quads);
+    g.x_lane = PX * g.q_lane;
+    g.left_of_image = g.q_lane < 0;
+    g.right_of_image = g.q_lane >= quads;
+    g.edge_strip = (strip == 0) || (PX * (strip * lanes_out + 64 - HALO) > w);
+    g.stores = (lane >= HALO) && (g.q_lane < g.q_end);
+    g.in_off = (uint32_t)g.q_load * bytes_in;
+    g.out_off = (uint32_t)(g.stores ? g.q_lane : 0) * bytes_out;
+    return g;
+}
+
+// A band of nout output rows from y0 on needs the input rows y0 - halo .. y0 + nout - 1 + halo; arrival index i counts
+// them in walking order (top down, or bottom up when `up`: a compile-time constant folds away).  Rows past the band's
+// last input re-read that last row (a cache hit, never consumed).
+struct BandWalk {
+    int y_first, y_step, halo, nin, h;
+};
+
+__device__ __forceinline__ BandWalk band_walk(bool up, int y0, int nout, int halo, int h)
+{
+    return BandWalk{up ? y0 + nout - 1 + halo : y0 - halo, up ? -1 : 1, halo, nout + 2 * halo, h};
+}
+
+template <Border B>
+__device__ __forceinline__ int in_row(const BandWalk& b, int i)
+{
+    return border_index<B>(b.y_first + b.y_step * min(i, b.nin - 1), b.h);
+}
+
+__device__ __forceinline__ int out_row(const BandWalk& b, int m)  // m-th completed row in arrival order
+{
+    return b.y_first + b.y_step * (m + b.halo);
+}
+
+// lane l <- lane l-1 / l+1 (lane 0 / 63 gets 0: a halo lane, its result is never stored); _or: that lane takes `edge`
+// instead (a DPP move without bound_ctrl leaves the destination, pre-loaded with `edge`, untouched there)
+template <int CTRL, bool ZERO>  // 0x138 = wave_shr:1, 0x130 = wave_shl:1
+__device__ __forceinline__ float dpp_move(float v, float edge)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge),
+                                                                 __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, ZERO));
+}
+__device__ __forceinline__ float dpp_left(float v) { return dpp_move<0x138, true>(v, 0.0f); }
+__device__ __forceinline__ float dpp_right(float v) { return dpp_move<0x130, true>(v, 0.0f); }
+__device__ __forceinline__ float dpp_left_or(float v, float edge) { return dpp_move<0x138, false>(v, edge); }
+__device__ __forceinline__ float dpp_right_or(float v, float edge) { return dpp_move<0x130, false>(v, edge); }
+
+// Halo lanes outside the image, edge strips only.  Clamp-to-edge columns (Gaussian, the pipeline's gray image): the edge
+// pixel replicated; reflect-101 (Sobel): the only halo pixel ever read is the one next to the image.
+__device__ __forceinline__ void edge_clamp_cols(u32x4& p, bool left_of_image, bool right_of_image)
+{
+    if (left_of_image)
+        p = u32x4{p.x, p.x, p.x, p.x};
+    if (right_of_image)
+        p = u32x4{p.w, p.w, p.w, p.w};
+}
+
+__device__ __forceinline__ void edge_reflect_cols(u32x4& p, bool left_of_image, bool right_of_image)
+{
+    if (left_of_image)
+        p.w = p.y;  // x = -1  <-  x = 1   (lane holds pixels 0..3)
+    if (right_of_image)
+        p.x = p.z;  // x = w   <-  x = w-2 (lane holds pixels w-4..w-1)
+}
+
+// RAGGED edge strips of the Sobel and pipeline kernels (PX = 4): only the lanes that overlap the row's ends address their
+// four pixels one by one, each column under the border rule (x in [-1, w] is all that is read); the others take the
+// unaligned 16-byte access of the interior strips (gauss_slide.hip: +9 % at width 1023, +55 % at 427).
+template <Border B>
+__device__ __forceinline__ void ragged_px_offsets(int x_lane, int w, uint32_t (&px_off)[4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        px_off[j] = (uint32_t)border_index<B>(clampi(x_lane + j, -1, w), w) * 4u;
+}
+
+__device__ __forceinline__ u32x4 ragged_row_load(global_ptr<const uint8_t> rowp, const SlideGeom& g, int w,
+                                                 uint32_t in_off, const uint32_t (&px_off)[4])
+{
+    u32x4 r;
+    if (g.edge_strip && !(g.x_lane >= 0 && g.x_lane + 3 < w)) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            r[j] = gload<uint32_t>(rowp + px_off[j]);
+    } else {
+        r = gload_a4<u32x4>(rowp + in_off);
+    }
+    return r;
 }
 #endif
 

@@ -28,20 +28,6 @@ namespace mi355 {
 
 namespace {
 
-constexpr int kWavesPerBlock = kSlideWavesPerBlock;
-
-__device__ __forceinline__ float dpp_left(float v)  // lane l <- lane l-1
-{
-    return __builtin_bit_cast(float,
-                              __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, true));
-}
-
-__device__ __forceinline__ float dpp_right(float v)  // lane l <- lane l+1
-{
-    return __builtin_bit_cast(float,
-                              __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
-}
-
 // RAGGED = width % 4 != 0 or unaligned buffers: interior strips use unaligned 16-byte row accesses, the two
 // edge strips address their pixels one by one through reflect-101 (which also covers the partial last quad),
 // and the output row (1 byte per pixel, width bytes long) is written byte by byte in the edge strips.
@@ -53,12 +39,11 @@ __device__ __forceinline__ float dpp_right(float v)  // lane l <- lane l+1
 // LOCKSTEP = false; from 2^28 pixels the aligned-strip kernel below takes over (profiles/r03_sobel_lockstep_ab.txt).
 // A wave that runs out of rows simply ends: s_barrier waits for the waves of the group that have not terminated.
 template <bool RAGGED, bool LOCKSTEP>
-__global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_slide_kernel(
+__global__ __launch_bounds__(kSlideWavesPerBlock * 64) void sobel_slide_kernel(
     const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int w, int h, int nstrips, int lanes_out,
     BandPlan plan)
 {
     constexpr int K = 3;
-    const int quads = (w + 3) >> 2;
     const int lane = threadIdx.x & 63;
     SlideItem it;
     __shared__ uint8_t gray_lut[256];  // luma(v, v, v): the ambiguous case of gray pixels without FP64 (common.hpp)
@@ -66,56 +51,29 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_slide_kernel(
     __syncthreads();
     if (!slide_item(plan, nstrips, h, &it))
         return;  // after the only barrier
-    const int strip = it.strip, y0 = it.y0, nout = it.nout;
-    const size_t frame = it.frame;
-
-    const int q_lane = strip * lanes_out + lane - 1;
-    // lanes right of the strip's right halo lane are never read by a storing lane: they re-load the halo quad
-    // (same address = same cache line) instead of the next strip's data
-    const int q_load = clampi(q_lane, 0, min(quads - 1, (strip + 1) * lanes_out));
-    const bool left_of_image = q_lane < 0, right_of_image = q_lane >= quads;
-    const bool edge_strip = (strip == 0) || (4 * (strip * lanes_out + 63) > w);  // wave-uniform
-    const int q_end = min((strip + 1) * lanes_out, quads);
-    const bool stores = (lane >= 1) && (q_lane < q_end);
-    const int x_lane = 4 * q_lane;
-
-    const int nin = nout + 2;
+    const SlideGeom G = slide_geom<4>(it.strip, lanes_out, lane, w, 16u, 4u);  // one byte out per pixel
 
     const size_t row_bytes = (size_t)w * 4;
-    const auto fin = uniform_ptr(in + frame * row_bytes * h);
-    const auto fout = uniform_ptr(out + frame * (size_t)w * h);  // one byte per pixel
-    uint32_t in_off = (uint32_t)q_load * 16u;
-    uint32_t out_off = (uint32_t)(stores ? q_lane : 0) * 4u;
-    uint32_t px_off[4];  // RAGGED edge strips: BORDER_REFLECT_101 of each pixel column (x <= w is all that is read)
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-        px_off[j] = (uint32_t)reflect101(clampi(x_lane + j, -1, w), w) * 4u;
+    const auto fin = uniform_ptr(in + it.frame * row_bytes * h);
+    const auto fout = uniform_ptr(out + it.frame * (size_t)w * h);
+    uint32_t in_off = G.in_off, out_off = G.out_off;
+    uint32_t px_off[4];  // RAGGED edge strips: BORDER_REFLECT_101 of each pixel column
+    ragged_px_offsets<kBorderReflect101>(G.x_lane, w, px_off);
 
     // Odd bands walk UP (the stencil is symmetric under a vertical flip: gy only changes sign, and it is squared;
     // all arithmetic is exact, so the bits do not change).  A down-walking band and the up-walking band below it
     // then read their two shared boundary rows at the same moment — the end of both walks — and the second reader
     // hits L2 instead of HBM; likewise the up-walking band and the down-walking one below it at their start.
-    const bool up = (it.band & 1) != 0;
+    const BandWalk W = band_walk((it.band & 1) != 0, it.y0, it.nout, 1, h);
+    const int nin = W.nin, nout = it.nout;
     auto load_row = [&](int i) -> u32x4 {
-        const int ii = min(i, nin - 1);
-        const int y = reflect101(up ? y0 + nout - ii : y0 - 1 + ii, h);
-        const auto rowp = fin + (size_t)y * row_bytes;  // SGPR pair; + 32-bit lane offset = saddr form
+        // SGPR pair; + 32-bit lane offset = saddr form
+        const auto rowp = fin + (size_t)in_row<kBorderReflect101>(W, i) * row_bytes;
         lane_offset_here(in_off);
-        if constexpr (RAGGED) {
-            u32x4 r;
-            // edge strips: only the lanes that overlap the row's ends address their pixels one by one; the others take
-            // the unaligned 16-byte access of the interior strips (gauss_slide.hip: +9 % at width 1023, +55 % at 427)
-            if (edge_strip && !(x_lane >= 0 && x_lane + 3 < w)) {
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    r[j] = gload<uint32_t>(rowp + px_off[j]);
-            } else {
-                r = gload_a4<u32x4>(rowp + in_off);
-            }
-            return r;
-        } else {
+        if constexpr (RAGGED)
+            return ragged_row_load(rowp, G, w, in_off, px_off);
+        else
             return gload<u32x4>(rowp + in_off);
-        }
     };
 
     constexpr int PF = 3;
@@ -138,13 +96,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_slide_kernel(
                 __builtin_amdgcn_s_barrier();
             q[(u + PF) % K] = load_row(i + PF);
             if constexpr (!RAGGED) {
-                if (edge_strip) {
-                    // BORDER_REFLECT_101 columns: the only halo pixel ever read is the one next to the image
-                    if (left_of_image)
-                        p.w = p.y;  // x = -1  <-  x = 1   (lane holds pixels 0..3)
-                    if (right_of_image)
-                        p.x = p.z;  // x = w   <-  x = w-2 (lane holds pixels w-4..w-1)
-                }
+                if (G.edge_strip)
+                    edge_reflect_cols(p, G.left_of_image, G.right_of_image);
             }
             luma_quad_fast(p, L[u], gray_lut, gray_run);
 
@@ -168,14 +121,14 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_slide_kernel(
             const float gxs[4] = {gx0, gx1, gx2, gx3}, gys[4] = {gy0, gy1, gy2, gy3};
             const uint32_t r = sobel_mag_quad(gxs, gys);
             const int m = i - 2;
-            if (stores && m >= 0 && m < nout) {
-                const auto rowp = fout + (size_t)(up ? y0 + nout - 1 - m : y0 + m) * w;
+            if (G.stores && m >= 0 && m < nout) {
+                const auto rowp = fout + (size_t)out_row(W, m) * w;
                 lane_offset_here(out_off);
                 if constexpr (RAGGED) {
-                    if (edge_strip && x_lane + 3 >= w) {  // the last quad of a row may be partial
+                    if (G.edge_strip && G.x_lane + 3 >= w) {  // the last quad of a row may be partial
 #pragma unroll
                         for (int j = 0; j < 4; j++)
-                            if (x_lane + j < w)
+                            if (G.x_lane + j < w)
                                 rowp[out_off + j] = (uint8_t)(r >> (8 * j));
                     } else {
                         gstore_a1<uint32_t>(rowp + out_off, r);  // rows of w bytes: any byte alignment
@@ -188,20 +141,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_slide_kernel(
     }
 }
 
-
-// lane l <- lane l-1 / l+1, and the lane that has no such neighbour (0 / 63) takes `edge` instead (a DPP move
-// without bound_ctrl leaves the destination, pre-loaded with `edge`, untouched there)
-__device__ __forceinline__ float dpp_left_or(float v, float edge)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge),
-                                                                 __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, false));
-}
-
-__device__ __forceinline__ float dpp_right_or(float v, float edge)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge),
-                                                                 __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, false));
-}
 
 // Luminance of ONE wave-uniform pixel on the scalar unit (the two halo pixels of the strip kernel below): S, the quotient
 // S / 1000 and the exception test of luma_quad_int (common.hpp) in s_bfe / s_mul / s_mul_hi — the VALU, which this kernel
@@ -225,7 +164,7 @@ __device__ __forceinline__ uint32_t luma_px_uniform(uint32_t px, const uint8_t* 
 // wave-uniform address (reflect-101 applied to it at the image border, so the arithmetic has no border cases),
 // i.e. a scalar load.  sobel_slide_kernel above spends a halo LANE per side (62 output lanes, every access shifted
 // by 16 bytes, 240-byte store spans) and remains the kernel for everything else.
-__global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_strip_kernel(
+__global__ __launch_bounds__(kSlideWavesPerBlock * 64) void sobel_strip_kernel(
     const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int quads, int h, int nstrips, BandPlan plan)
 {
     constexpr int K = 3;
@@ -236,7 +175,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_strip_kernel(
     __syncthreads();
     if (!slide_item(plan, nstrips, h, &it))
         return;  // after the only barrier
-    const int w = 4 * quads, y0 = it.y0, nout = it.nout, nin = nout + 2;
+    const int w = 4 * quads, nout = it.nout;
     const int q = it.strip * 64 + lane;
     const int q_last = min((it.strip + 1) * 64, quads) - 1;  // last quad of this strip (wave-uniform)
     const bool active = q <= q_last;
@@ -249,16 +188,15 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_strip_kernel(
     const auto fout = uniform_ptr(out + it.frame * (size_t)w * h);
     uint32_t in_off = (uint32_t)min(q, q_last) * 16u;
     uint32_t out_off = (uint32_t)min(q, q_last) * 4u;
-    const bool up = (it.band & 1) != 0;  // see sobel_slide_kernel
+    const BandWalk W = band_walk((it.band & 1) != 0, it.y0, it.nout, 1, h);  // see sobel_slide_kernel
+    const int nin = W.nin;
 
     struct Row {
         u32x4 p;
         uint32_t hl, hr;
     };
     auto load_row = [&](int i) -> Row {
-        const int ii = min(i, nin - 1);
-        const int y = reflect101(up ? y0 + nout - ii : y0 - 1 + ii, h);
-        const auto rowp = fin + (size_t)y * row_bytes;
+        const auto rowp = fin + (size_t)in_row<kBorderReflect101>(W, i) * row_bytes;
         lane_offset_here(in_off);
         Row r;
         r.p = gload<u32x4>(rowp + in_off);
@@ -314,7 +252,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void sobel_strip_kernel(
             const uint32_t res = sobel_mag_quad(gxs, gys);
             const int m = i - 2;
             if (active && m >= 0 && m < nout) {
-                const auto rowp = fout + (size_t)(up ? y0 + nout - 1 - m : y0 + m) * w;
+                const auto rowp = fout + (size_t)out_row(W, m) * w;
                 lane_offset_here(out_off);
                 gstore_nt<uint32_t>(rowp + out_off, res);
             }
@@ -328,7 +266,7 @@ bool sobel_slide_supported(const uint8_t* d_in, const uint8_t* d_out, int w, int
 {
     (void)h;
     (void)w;
-    return (reinterpret_cast<uintptr_t>(d_in) & 3u) == 0;  // pixels are dwords; everything else is handled
+    return aligned_to(d_in, 4);  // pixels are dwords; everything else is handled
 }
 
 hipError_t launch_sobel_slide(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes)
@@ -342,15 +280,13 @@ hipError_t launch_sobel_slide(hipStream_t stream, const uint8_t* d_in, uint8_t* 
     // big batches of aligned rows: the aligned-strip kernel (256 x 4K frames, same box: 5.81-5.99 TB/s against
     // 5.67-5.72 for the halo-lane kernel; 640x512 x 8000: 5.48 / 5.24; but 8 x 4K frames: 5.45 / 5.86)
     const bool big = (size_t)w * h * nframes >= ((size_t)1 << 28) || kStripMode == 2;
-    if (!kStripOff && big && (w & 3) == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15u) == 0 &&
-        (reinterpret_cast<uintptr_t>(d_out) & 3u) == 0) {
+    const bool ragged = rows_ragged(w, d_in, 16, d_out, 4);
+    if (!kStripOff && big && !ragged) {
         const int quads = w / 4, nstrips = (quads + 63) / 64;
         BandPlan plan;
         if (!make_band_plan(h, nstrips, nframes, 8, 16, 16, 16, 0.0, 8, &plan))
             return hipErrorInvalidValue;
-        hipLaunchKernelGGL(sobel_strip_kernel, dim3(plan.nblocks_a + plan.nblocks_b), dim3(kWavesPerBlock * 64), 0,
-                           stream, d_in, d_out, quads, h, nstrips, plan);
-        return hipGetLastError();
+        return launch_slide(sobel_strip_kernel, plan, stream, d_in, d_out, quads, h, nstrips, plan);
     }
     // big batches: 48-lane strips (192-byte store spans, see slide_common.hpp: +5 % on 256 x 4K frames); small
     // ones keep the fewest, widest strips (8 x 4K frames: 48 lanes would cost 8 %)
@@ -361,22 +297,14 @@ hipError_t launch_sobel_slide(hipStream_t stream, const uint8_t* d_in, uint8_t* 
     BandPlan plan;
     if (!make_band_plan(h, sp.nstrips, nframes, 8, 16, 16, 16, 0.0, 8, &plan))
         return hipErrorInvalidValue;
-    const bool ragged = (w & 3) != 0 || (reinterpret_cast<uintptr_t>(d_in) & 15u) != 0 ||
-                        (reinterpret_cast<uintptr_t>(d_out) & 3u) != 0;
     // mid-size launches of aligned rows (8 x 10^7 pixels ~ ten 4K frames, up to where the strip kernel takes over): rows in
     // lock-step, see the kernel
     const bool lockstep = !ragged && !big && (size_t)w * h * nframes >= 80000000ull;
-    const dim3 grid(plan.nblocks_a + plan.nblocks_b), block(kWavesPerBlock * 64);
-    if (ragged)
-        hipLaunchKernelGGL((sobel_slide_kernel<true, false>), grid, block, 0, stream, d_in, d_out, w, h, sp.nstrips,
-                           sp.lanes_out, plan);
-    else if (lockstep)
-        hipLaunchKernelGGL((sobel_slide_kernel<false, true>), grid, block, 0, stream, d_in, d_out, w, h, sp.nstrips,
-                           sp.lanes_out, plan);
-    else
-        hipLaunchKernelGGL((sobel_slide_kernel<false, false>), grid, block, 0, stream, d_in, d_out, w, h, sp.nstrips,
-                           sp.lanes_out, plan);
-    return hipGetLastError();
+    auto launch = [&](auto kernel) {
+        return launch_slide(kernel, plan, stream, d_in, d_out, w, h, sp.nstrips, sp.lanes_out, plan);
+    };
+    return ragged ? launch(sobel_slide_kernel<true, false>)
+                  : (lockstep ? launch(sobel_slide_kernel<false, true>) : launch(sobel_slide_kernel<false, false>));
 }
 
 }  // namespace mi355

@@ -198,7 +198,7 @@ hipError_t launch_sobel(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out,
     if (impl != 1 && sobel_slide_supported(d_in, d_out, w, h))
         return launch_sobel_slide(stream, d_in, d_out, w, h, nframes);
     const TileGrid g(w, h, nframes, kRgbaTW, kRgbaTH);
-    const int vec = ((w & 3) == 0) && ((reinterpret_cast<uintptr_t>(d_out) & 3u) == 0);
+    const int vec = ((w & 3) == 0) && aligned_to(d_out, 4);
     return launch_tiles(sobel_tile_kernel, g, kRgbaTileThreads, 0, kLdsDefault, stream, reinterpret_cast<const uint32_t*>(d_in),
                         d_out, w, h, g.tiles_x, g.tiles_y, g.n(), vec);
 }
@@ -225,7 +225,7 @@ hipError_t launch_pipeline(hipStream_t stream, const uint8_t* d_in, uint8_t* d_o
         return launch_pipe_slide(stream, d_in, d_out, w, h, nframes, coef, 4);
     const TileGrid g(w, h, nframes, kRgbaTW, kRgbaTH);
     const PipeTileLayout L = pipe_tile_layout(exact, coef.k);
-    const int vec = ((w & 3) == 0) && ((reinterpret_cast<uintptr_t>(d_out) & 3u) == 0);
+    const int vec = ((w & 3) == 0) && aligned_to(d_out, 4);
     return launch_tiles(exact ? pipeline_tile_kernel<true> : pipeline_tile_kernel<false>, g, kRgbaTileThreads, L.bytes, kLdsRaise,
                         stream, reinterpret_cast<const uint32_t*>(d_in), d_out, w, h, g.tiles_x, g.tiles_y, coef.k,
                         exact ? coef.d_w2d : coef.d_w1d, g.n(), vec);

@@ -1,15 +1,14 @@
 // tile_common.hpp — the frame every LDS-tiled kernel shares (gauss_tile, sobel_tile, gray8, morph, median, image2d):
 // a workgroup owns one TW x TH output tile of one frame; the grid is the 1-D list of all tiles of all frames.
 //   host    TileGrid counts the tiles, launch_tiles refuses more than 2^31 - 1 of them, raises the dynamic-LDS limit
-//           where the kernel's carve needs more than the default 64 KiB allows, launches, and returns the launch error;
-//           dispatch_int turns a runtime k / op / layout into a template argument.
-//   device  tile_decode: tile index -> (tx, ty, frame, x0, y0); border_index<B>: the border rule of a filter;
-//           the reduced-alignment 16-byte row chunk types and store_chunk16 (one vector store inside the row, pixel
-//           by pixel across its right edge); the packed-u16 words of the min / max kernels.
+//           where the kernel's carve needs more than the default 64 KiB allows, launches, and returns the launch error
+//           (dispatch_int, which turns a runtime k / op / layout into a template argument, is common.hpp's).
+//   device  tile_decode: tile index -> (tx, ty, frame, x0, y0); the border rule of a filter is common.hpp's
+//           border_index<B>; the reduced-alignment 16-byte row chunk types and store_chunk16 (one vector store inside
+//           the row, pixel by pixel across its right edge); the packed-u16 words of the min / max kernels.
 // Every device helper is __forceinline__: nothing here adds a call or a runtime switch to a kernel.
 #pragma once
 #include <type_traits>
-#include <utility>
 
 #include "common.hpp"
 
@@ -51,15 +50,6 @@ hipError_t launch_tiles(void (*kernel)(KArgs...), const TileGrid& g, int threads
     return hipGetLastError();
 }
 
-// f(std::integral_constant<int, K>{}) for the K of the list that equals v; hipErrorInvalidValue when none does
-template <int... Ks, typename F>
-hipError_t dispatch_int(int v, std::integer_sequence<int, Ks...>, F&& f)
-{
-    hipError_t e = hipErrorInvalidValue;
-    (void)((v == Ks && ((e = f(std::integral_constant<int, Ks>{})), true)) || ...);
-    return e;
-}
-
 // ---- device ---------------------------------------------------------------------------------------------------------
 struct TilePos {
     int tx, ty;
@@ -78,19 +68,6 @@ __device__ __forceinline__ TilePos tile_decode(uint32_t tile, int tiles_x, int t
     t.x0 = t.tx * tw;
     t.y0 = t.ty * th;
     return t;
-}
-
-// clamp: BORDER_REPLICATE (Gaussian, median, morphology); reflect101: BORDER_REFLECT_101 (Sobel).  Positions beyond
-// len are never consumed by a stored pixel; folding them onto len first bounds reflect101's loop to one turn.
-enum Border { kBorderClamp, kBorderReflect101 };
-
-template <Border B>
-__device__ __forceinline__ int border_index(int p, int len)
-{
-    if constexpr (B == kBorderClamp)
-        return clampi(p, 0, len - 1);
-    else
-        return reflect101(min(p, len), len);
 }
 
 // 16 bytes of a frame row.  RGBA rows are dword-aligned, gray8 rows may start at any byte; gfx950 global accesses need
