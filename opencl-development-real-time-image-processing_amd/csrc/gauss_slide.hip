@@ -10,7 +10,8 @@
 //  * a lane owns 4 consecutive pixels (one 16-byte global_load_dwordx4 / global_store_dwordx4);
 //    a wave owns a vertical strip of up to 62 such lanes plus one halo lane on each side, and walks
 //    down a band of rows.  Every input row of the band is loaded exactly once by exactly one
-//    coalesced 1-KiB wave access; 3 rows are kept in flight per wave (prefetch ring in VGPRs).
+//    coalesced 1-KiB wave access; 3 rows are kept in flight per wave (prefetch ring in VGPRs; the row loop is cut
+//    into prologue / whole trips / remainder so that hipcc's waits let them be: gauss_slide_band).
 //  * vertical pass first, in registers: K running accumulators per lane (one per pending output
 //    row), each new row is converted once (v_cvt_f32_ubyteN) and folded into all K of them;
 //    the accumulator that just received its last tap is the finished vertical sum `v`.
@@ -21,8 +22,8 @@
 //  * constant alpha (every A = 255 is what cv::cvtColor produces; mattes and overlays are piecewise constant): a
 //    band is first run on 3 channels; while the K rows of a window carry ONE alpha value A over the whole strip, the
 //    blurred alpha is the constant byte alpha_tab[A] (the canonical chains on an all-A window, evaluated by the
-//    host).  A row with mixed alphas, or a window that spans two values, aborts the pass and the band is redone on
-//    4 channels, so the output never depends on which pass produced it.
+//    host).  A row with mixed alphas, or a window that spans two values, ends the pass at the end of its trip of K
+//    rows and the band is redone on 4 channels, so the output never depends on which pass produced it.
 //  * RAGGED instantiation: any width and any 4-byte-aligned pointer (unaligned 16-byte interior loads,
 //    per-pixel clamped loads and predicated narrow stores in the two edge strips).
 // Algorithmic bytes: 8 B/px.  Extra traffic: halo lanes (2/62 of the loads, L2/MALL hits) and 2R
@@ -38,6 +39,31 @@
 namespace mi355 {
 
 namespace {
+
+// A row store that some lanes of the wave sit out, as ONE unconditional instruction: a non-temporal 16-byte store
+// through a buffer descriptor of the row (base = the wave-uniform row pointer, row_bytes records).  The lanes that store
+// nothing pass kRowStoreNowhere as their offset, which lies beyond any row of up to 2 GiB, and the descriptor's range
+// check drops their writes.  (An `if (stores)` around a plain store becomes a block of its own behind an s_cbranch_execz
+// — hipcc keeps that branch around any memory instruction — and the path without the store makes every wait that
+// follows count as if no store were in flight.)  The launcher keeps wider rows away from the kernels that use this.
+constexpr uint32_t kRowStoreNowhere = 0x80000000u;
+__device__ __forceinline__ void gstore_row_nt(global_ptr<uint8_t> rowp, uint32_t row_bytes, uint32_t off, u32x4 v)
+{
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)rowp, (short)0, (int)row_bytes, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (int)off, 0, 2 /* nt */);
+}
+
+// launch_slide with dynamic LDS nobody touches, to hold a kernel at fewer workgroups per CU than its registers allow (a
+// workgroup is one wave per SIMD, so workgroups per CU = waves per SIMD; 160 KiB per CU)
+constexpr uint32_t kSlideLdsForFiveWaves = 160u * 1024u / 5u - 1024u;  // 5 fit, 6 do not
+template <typename... KArgs, typename... Args>
+hipError_t launch_slide_lds(void (*kernel)(KArgs...), const BandPlan& plan, uint32_t lds_bytes, hipStream_t stream,
+                            Args... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(plan.nblocks_a + plan.nblocks_b), dim3(kSlideWavesPerBlock * 64), lds_bytes, stream,
+                       static_cast<KArgs>(args)...);
+    return hipGetLastError();
+}
 
 template <int K>
 struct Weights {
@@ -182,7 +208,7 @@ struct SlideLane {
     global_ptr<uint8_t> fout;
     size_t row_bytes;
     SlideGeom g;  // (RAGGED, w >= 4: g.in_off is the shifted load's, see edge)
-    int y0, nout, nin, h;
+    int y0, nout, h;
     // RAGGED variant (width % 4 != 0 or buffers not 16-byte aligned): lanes of an edge strip that overlap the row's right
     // end load the row's last four pixels and shift them into place (slide_common.hpp: RaggedEdge; six v_cndmask per row,
     // edge strips only, no divergent branch).  Images narrower than 4 pixels keep the per-pixel form (px_off).
@@ -206,11 +232,23 @@ __device__ __forceinline__ bool alpha_row_differs(const u32x4& p, uint32_t nA)
     return __builtin_amdgcn_ballot_w64(t < 0xFF000000u) != 0;
 }
 
-// Return codes of a pass over a band (3-channel passes only stop early; the rows stored so far are correct)
+// Return codes of a pass over a band (3-channel passes only stop early; the pass that follows redoes the whole band)
 constexpr int kBandDone = 0;          // every output row stored
 constexpr int kBandAbortUniform = 1;  // AMODE 1: a row whose alpha is uniform over the strip but not 255 — worth AMODE 2
 constexpr int kBandAbort = 2;         // a row with mixed alphas, or (AMODE 2) a window that spans two values: 4 channels
-constexpr int kBandAbortUniformFirst = 3;  // kBandAbortUniform at the band's first row: q3[0 .. PF-1] still hold the first rows
+constexpr int kBandAbortUniformFirst = 3;  // kBandAbortUniform at the band's first row: q3[0 .. PF-1] hold the first rows as loaded
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): the rows of a phase, ring slots as constants
+template <typename F, int... I>
+__device__ __forceinline__ void static_rows_impl(F&& f, std::integer_sequence<int, I...>)
+{
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_rows(F&& f)
+{
+    static_rows_impl(f, std::make_integer_sequence<int, N>{});
+}
 
 // AMODE of a 3-channel pass: 1 = alpha 255 only — the hot loop of opaque frames, exactly round 2's instruction stream —;
 // 2 = any constant, piecewise (value tracking, table loads, window check).  The kernel tries 1, then 2 only where 1
@@ -221,8 +259,27 @@ constexpr int kBandAbortUniformFirst = 3;  // kBandAbortUniform at the band's fi
 // constant-alpha fast path — alpha is not computed; while the last K rows carry one alpha value A over all 64 lanes
 // (halo included) every output gets the constant byte alpha_tab[A] (alpha_row_differs: three or four instructions per
 // row; the value changes through a scalar branch and one s_load).  A row with mixed alphas, or an output row whose window
-// spans two values, ends the pass before that row has stored anything: the rows stored so far are correct, and
-// the caller redoes the band with NCH = 4.
+// spans two values, stops the pass, and the caller redoes the band with NCH = 4.
+//
+// Shape of a pass — three phases, so that the row loop has ONE exit, at a trip boundary, and ONE path through a row:
+//   prologue   the 2R warm-up rows: loaded, tested, converted; nothing to store yet
+//   steady     nout / K whole trips of K rows; every row runs the horizontal pass and issues its store.  Row u of a
+//              trip lives in ring slot (2R + u) % K: the numbering is rotated by the prologue's length, still static
+//   remainder  the last nout % K rows, each behind a scalar guard
+// A row that would stop the pass only RECORDS that (`code`) and the loop condition looks at it once per trip.  Why:
+// hipcc places the s_waitcnt itself, from the worst path that reaches a use.  Every early `return` inside the unrolled
+// trip was a loop exit, all exits are funnelled through one latch block, and that gave the first row of a trip a
+// static predecessor that had just loaded its slot — so once per trip the wave waited for everything but its newest
+// load, stores included (vmcnt(1)), and the `m >= 0 && m < nout` branch around the store pinned the other rows at
+// the loads-only count (vmcnt(3): two rows in flight, not three).  With one exit and one path the waits count the
+// stores too (profiles/gauss_trip_waits.txt).
+// The rows of a trip that follow the offending row DO store — 3-channel bytes that may carry the wrong alpha.  They are
+// not masked: the pass that follows redoes the whole band from its first row in this same wave, so its stores to the
+// same addresses come later in program order and a wave's stores to one address stay in order (k = 7: the redo is the
+// MODE 4 kernel, after this one).  Masking them would put an EXEC write and its restore into every row of the hot
+// loop for the sake of a band that is redone anyway.
+// Row addresses are carried from row to row (+- row_bytes; the input's stops where in_row clamps), so the masked
+// store region holds the store alone.
 template <int R, bool CLAMP, int NCH, bool RAGGED, bool UP, int AMODE, bool LOCKSTEP>
 __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float (&wv)[2 * R + 1], uint32_t alpha_hi,
                                                 const uint32_t* __restrict__ alpha_tab, u32x4 (&q3)[2 * R + 1],
@@ -231,15 +288,30 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
     constexpr int K = 2 * R + 1;
     static_assert((NCH == 4) == (AMODE == 0), "AMODE 1 / 2 belong to the 3-channel pass");
     uint32_t in_off = L.g.in_off, out_off = L.g.out_off;
+    [[maybe_unused]] const uint32_t out_voff = L.g.stores ? out_off : kRowStoreNowhere;  // aligned rows: gstore_row_nt
     const BandWalk W = band_walk(UP, L.y0, L.nout, R, L.h);  // an UP band walks from its bottom-most input row up
     // AMODE 2: (A ^ 0xFF) << 24 for the alpha value A the rows seen last carry — alpha_hi = alpha_tab[A] — and how many
     // consecutive rows, the current one included, carry it.  The first row sets them (run = 0 forces the first test to
     // take the "value changes" branch only if the row is not 255; 255 is where alpha_hi starts).
     uint32_t cur_nA = 0u;
     int run = 0;
-    auto load_row = [&](int i) -> u32x4 {
+    int code = kBandDone;  // what a row records instead of leaving the loop
+    // Row pointers (SGPR pairs), carried: the input's moves while the arrival index stays inside the rows the band has
+    // — in_row<kBorderClamp>(W, i) without its multiplies —, the output's after every store (out_row never clamps).
+    const ptrdiff_t step_bytes = UP ? -(ptrdiff_t)L.row_bytes : (ptrdiff_t)L.row_bytes;
+    const int y_lo = max(L.y0 - R, 0), y_hi = min(L.y0 + L.nout - 1 + R, L.h - 1);
+    int y_in = W.y_first;  // unclamped row of the next load
+    auto in_p = L.fin + (size_t)clampi(y_in, y_lo, y_hi) * L.row_bytes;
+    auto out_p = L.fout + (size_t)out_row(W, 0) * L.row_bytes;
+    auto next_in_row = [&]() {
+        const int y_next = y_in + W.y_step;
+        in_p += (min(y_in, y_next) >= y_lo && max(y_in, y_next) <= y_hi) ? step_bytes : (ptrdiff_t)0;
+        y_in = y_next;
+    };
+    auto load_row = [&]() -> u32x4 {
         // SGPR pair; + 32-bit lane offset = saddr form
-        const auto rowp = L.fin + (size_t)in_row<kBorderClamp>(W, i) * L.row_bytes;
+        const auto rowp = in_p;
+        next_in_row();
         if constexpr (R <= 2)  // (k = 9: the asm statements keep hipcc from unrolling the trip; k = 7: -4 %)
             lane_offset_here(in_off);
         if constexpr (RAGGED) {
@@ -269,7 +341,21 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
     if (AMODE != 2 || !preloaded) {
 #pragma unroll
         for (int u = 0; u < PF; u++)
-            q[u] = load_row(u);
+            q[u] = load_row();
+    } else {
+#pragma unroll
+        for (int u = 0; u < PF; u++)
+            next_in_row();
+    }
+    if constexpr (AMODE == 1) {
+        // The band's first row, tested here, outside the loop and BEFORE its slot is touched: the edge strips replicate
+        // and (RAGGED) shift a row in place, and a row shifted by the pass that hands it over and again by the pass that
+        // takes it is a different row.  The lanes that get replicated pixels hold copies of pixels other lanes of the
+        // wave own, so the test on the row as loaded sees the same alpha values.
+        if (alpha_row_differs<true>(q[0], 0u)) {  // wave-uniform
+            const uint32_t a_row = ((uint32_t)__builtin_amdgcn_readfirstlane((int)q[0].x) >> 24) & 0xFFu;
+            return alpha_row_differs<false>(q[0], (a_row ^ 0xFFu) << 24) ? kBandAbort : kBandAbortUniformFirst;
+        }
     }
 
     // k <= 7: ring of the last K input rows, converted to float once (row i lives in slot i % K, static after
@@ -281,12 +367,12 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
     static_assert(kRing || !UP, "the accumulator form walks down only");
     float rows[K][4 * NCH] = {};
 
-    // One trip = K input rows.  Input row i completes the window of output row m = i - 2R; the first 2R rows of
-    // a band and the rows of a last partial trip only convert (scalar branch below).
-    for (int base = 0; base < L.nin; base += K) {
-#pragma unroll
-        for (int u = 0; u < K; u++) {
-            const int i = base + u;
+    // One row: arrival index i, ring slot u = i % K (a constant).  Input row i completes the window of output row
+    // m = i - 2R; OUT = false for the warm-up rows, which only convert.
+    auto do_row = [&](auto slot, auto outputs) __attribute__((always_inline)) {
+        constexpr int u = decltype(slot)::value;
+        constexpr bool OUT = decltype(outputs)::value;
+        {
             // the row is used in place where its slot is not the one the next load fills (k >= 5: PF < K) — a private copy
             // cost two v_mov_b64 per row on every strip for the sake of the edge strips' replication
             u32x4 p_copy = q[u];
@@ -294,14 +380,15 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
             if constexpr (LOCKSTEP) {
                 // Adjacent strips of a row-band in step: the four waves' 1-KiB accesses to one row reach memory together
                 // (+1.3 % on opaque 4K and 1080p batches, +1.2 % at k = 3, +1.5 % on 8- and 64-frame launches, same box
-                // and buffers; nothing on the issue-bound 4-channel pass or at k >= 7).  A wave that leaves the loop (end
-                // of band, a pass that stops) just stops arriving: s_barrier waits for the waves of the group that have
-                // not terminated, and every wave either reaches another s_barrier of this loop — in whichever pass — or
-                // ends, so nobody waits for ever.  A template parameter, not a flag: the scalar test of a flag in this
-                // loop cost launches of one or two frames 1.4 %.
+                // and buffers; nothing on the issue-bound 4-channel pass or at k >= 7).  A wave that is done with a pass
+                // (end of band, a pass that stops) just stops arriving: s_barrier waits for the waves of the group that
+                // have not terminated, and every wave either reaches another s_barrier of these rows — in whichever pass
+                // — or ends, so nobody waits for ever.  A template parameter, not a flag: the scalar test of a flag in
+                // this loop cost launches of one or two frames 1.4 %.
                 __builtin_amdgcn_s_barrier();
             }
-            q[(u + PF) % K] = load_row(i + PF);
+            if constexpr (PF < K)
+                q[(u + PF) % K] = load_row();
             if (L.g.edge_strip) {  // wave-uniform
                 // (in place, not edge_clamp_cols: slide_common.hpp says why)
                 if constexpr (!RAGGED) {
@@ -316,11 +403,10 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
                 }
             }
             if constexpr (AMODE == 1) {
-                if (alpha_row_differs<true>(p, 0u)) {  // wave-uniform: the pass ends here
+                // wave-uniform, no memory access inside: the pass ends at this trip's end; the first such row says how
+                if (alpha_row_differs<true>(p, 0u) && code == kBandDone) {
                     const uint32_t a_row = ((uint32_t)__builtin_amdgcn_readfirstlane((int)p.x) >> 24) & 0xFFu;
-                    if (alpha_row_differs<false>(p, (a_row ^ 0xFFu) << 24))
-                        return kBandAbort;
-                    return (i == 0 && PF < K) ? kBandAbortUniformFirst : kBandAbortUniform;  // (k = 3: slot 0 is refilled already)
+                    code = alpha_row_differs<false>(p, (a_row ^ 0xFFu) << 24) ? kBandAbort : kBandAbortUniform;
                 }
             }
             if constexpr (AMODE == 2) {
@@ -328,7 +414,7 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
                     const uint32_t a_new = ((uint32_t)__builtin_amdgcn_readfirstlane((int)p.x) >> 24) & 0xFFu;  // (int -> int builtin)
                     const uint32_t nA = (a_new ^ 0xFFu) << 24;
                     if (alpha_row_differs<false>(p, nA))
-                        return kBandAbort;
+                        code = kBandAbort;  // mixed alphas: the pass ends at this trip's end (what it tracks no longer matters)
                     cur_nA = nA;
                     alpha_hi = __builtin_amdgcn_readfirstlane(alpha_tab[a_new]);
                     run = 0;
@@ -359,14 +445,16 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
                     }
                 }
             }
-            const int m = i - 2 * R;  // output row whose window this input row completes
-            // warm-up rows (m < 0) and the rows of a last partial trip (m >= nout) produce no output: skip
-            // the horizontal pass and the store with a scalar branch (m and nout live in SGPRs, so EXEC
-            // stays full inside, which the DPP reads of the horizontal pass require)
-            if (m >= 0 && m < L.nout) {
+            // k = 3 (PF = K): the next load refills this row's own slot, so it is issued once the row is converted — issued
+            // first, it lands in other registers and the ring is copied round at the end of every trip, behind a wait for
+            // all loads but the newest
+            if constexpr (PF == K)
+                q[u] = load_row();
+            // (EXEC is full here, which the DPP reads of the horizontal pass require)
+            if constexpr (OUT) {
                 if constexpr (AMODE == 2) {
                     if (run < K)  // the window spans two alpha values: its blurred alpha is not a constant
-                        return kBandAbort;
+                        code = kBandAbort;
                 }
                 // vertical pass in the canonical order, top tap first: a DOWN band holds the window oldest row
                 // = top row (slot u+1 ... slot u), an UP band newest row = top row (slot u, u-1, ...) — a static
@@ -427,8 +515,13 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
                             o[px] |= alpha_hi;
                     }
                 }
-                if (L.g.stores) {
-                    const auto rowp = L.fout + (size_t)out_row(W, m) * L.row_bytes;
+                const auto rowp = out_p;
+                out_p += step_bytes;
+                if constexpr (!RAGGED) {
+                    // one unconditional instruction: a predicated store is a block of its own behind an
+                    // s_cbranch_execz, a path without a store, and the waits of every row fall back to counting loads only
+                    gstore_row_nt(rowp, (uint32_t)L.row_bytes, out_voff, o);
+                } else if (L.g.stores) {
                     if constexpr (R <= 2)
                         lane_offset_here(out_off);
                     if constexpr (RAGGED) {
@@ -446,8 +539,37 @@ __device__ __forceinline__ int gauss_slide_band(const SlideLane& L, const float 
                 }
             }
         }
+    };
+    static_rows<2 * R>([&](auto v) __attribute__((always_inline)) { do_row(v, std::false_type{}); });
+    const int ntrips = L.nout / K, rem = L.nout - ntrips * K;
+    auto trip = [&]() __attribute__((always_inline)) {
+        static_rows<K>([&](auto v) __attribute__((always_inline)) {
+            do_row(std::integral_constant<int, (2 * R + decltype(v)::value) % K>{}, std::true_type{});
+        });
+    };
+    // The first trip stands outside the loop, and the loop inside its `if`: it is reached from the prologue, with loads
+    // in flight but no stores, and as the loop's header it would hand that count to every trip.
+    // (RAGGED: its stores are predicated and narrow in the edge strips, the waits stay conservative either way — no copy)
+    constexpr int kPeeled = RAGGED ? 0 : 1;
+    if (ntrips >= kPeeled) {
+        if constexpr (kPeeled)
+            trip();
+        for (int t = kPeeled; t < ntrips && code == kBandDone; t++)
+            trip();
     }
-    return kBandDone;
+    // remainder: row v runs if v < rem (wave-uniform), nested, so that a row that does not run joins nothing but the end
+    auto rem_rows = [&](auto self, auto v) __attribute__((always_inline)) {
+        constexpr int V = decltype(v)::value;
+        if constexpr (V < K - 1) {
+            if (V < rem) {
+                do_row(std::integral_constant<int, (2 * R + V) % K>{}, std::true_type{});
+                self(self, std::integral_constant<int, V + 1>{});
+            }
+        }
+    };
+    if (code == kBandDone)
+        rem_rows(rem_rows, std::integral_constant<int, 0>{});
+    return code;
 }
 
 // MODE 0: one kernel, opaque pass then (if an alpha != 255 turns up) the general pass — k = 3, 5, where both fit
@@ -474,7 +596,6 @@ __global__ __launch_bounds__(kSlideWavesPerBlock * 64, (R == 3 && MODE == 3) ? 3
     L.g = slide_geom<4>(it.strip, lanes_out, lane, w, 16u, 16u);  // RAGGED: the last quad of a row may be partial
     L.y0 = it.y0;
     L.nout = it.nout;
-    L.nin = it.nout + 2 * R;
     L.h = h;
     L.w = w;
     L.row_bytes = (size_t)w * 4;
@@ -541,7 +662,7 @@ __global__ __launch_bounds__(kSlideWavesPerBlock * 64, (R == 3 && MODE == 3) ? 3
 }
 
 template <int R>
-bool slide_plan(int w, int h, int nframes, StripPlan* sp, BandPlan* plan)
+bool slide_plan(int w, int h, int nframes, bool ragged, StripPlan* sp, BandPlan* plan)
 {
     constexpr int K = 2 * R + 1;
     *sp = make_strip_plan(w);
@@ -552,9 +673,18 @@ bool slide_plan(int w, int h, int nframes, StripPlan* sp, BandPlan* plan)
     //          16 rows 6.23 fast / 5.50 slow against 6.10 / 5.01 for adaptive tall bands)
     //   k = 5: 24 rows (6.10 / 5.47; adaptive 6.10 / 5.05) — warm-up rows skip the horizontal pass, so short
     //          bands cost little arithmetic; the general 4-channel pass alone would prefer ~64 rows (-4 % here)
+    //          With the three-phase row loop (exact waits, profiles/gauss_trip_ab.txt section 3) the aligned kernels were
+    //          swept again, same buffers, three processes: 15 rows — three whole trips, no remainder — +2.4 % on 256 x 4K
+    //          (16 rows +1.4 %, 20 / 21 rows +0.9 %, 26 and more lose), +2.3 % on 64 frames, +4 % on 1080p x 1024, +7 % on 8
+    //          frames; launches of fewer than 2800 work items keep 24 -> 12 rows (one 4K frame: 15 rows -13 %), and so do the
+    //          ragged kernels (1023 x 819: 15 rows -3 %, 21 rows +0.5 %).
     //   k >= 7: VALU-bound, the 2R warm-up rows hurt: tall adaptive bands + short-band tail
+    if (K == 5) {
+        const bool big = (size_t)sp->nstrips * ((h + 23) / 24) * nframes >= 2800;
+        const int rows = (big && !ragged) ? 15 : 24;
+        return make_band_plan(h, sp->nstrips, nframes, 4, rows, rows, rows, 0.0, 12, plan);
+    }
     return (K == 3)   ? make_band_plan(h, sp->nstrips, nframes, 5, 12, 12, 12, 0.0, 6, plan)
-           : (K == 5) ? make_band_plan(h, sp->nstrips, nframes, 4, 24, 24, 24, 0.0, 12, plan)
                       : make_band_plan(h, sp->nstrips, nframes, 3, 96, 270, 40, 0.1, 4 * R + 4, plan);
 }
 
@@ -566,10 +696,11 @@ hipError_t launch_r(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int
     constexpr bool kSplit = R >= 3;  // two kernels + flags
     StripPlan sp;
     BandPlan plan;
-    if (!slide_plan<R>(w, h, nframes, &sp, &plan) || (kSplit && !d_flags))
+    // (the aligned kernels' row stores want rows of at most 2 GiB, gstore_row_nt; RAGGED serves any row)
+    const bool ragged = rows_ragged(w, d_in, 16, d_out, 16) || (size_t)w * 4 > kRowStoreNowhere;
+    if (!slide_plan<R>(w, h, nframes, ragged, &sp, &plan) || (kSplit && !d_flags))
         return hipErrorInvalidValue;
     const int nstrips = sp.nstrips, lanes_out = sp.lanes_out;
-    const bool ragged = rows_ragged(w, d_in, 16, d_out, 16);
     Weights<K> wts;
     for (int j = 0; j < K; j++)
         wts.w[j] = coef.h_w1d[j];
@@ -587,9 +718,12 @@ hipError_t launch_r(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int
     // one-strip frames 7 % — and the launch is several times what the chip holds at once (1-4 4K frames, cache-resident: -1.2 %)
     const bool lockstep =
         R <= 2 && !ragged && nstrips % kSlideWavesPerBlock == 0 && plan.nwork_b == 0 && plan.nwork_a >= 8192u;
+    // k = 3, aligned rows: 77 VGPRs would let a sixth wave onto each SIMD; the band plan above was measured at five, and at
+    // six the opaque 4K batch runs 1 % slower (profiles/gauss_trip_ab.txt).  Unused LDS keeps it at five workgroups per CU.
+    const uint32_t lds_bytes = (R == 1 && !ragged) ? kSlideLdsForFiveWaves : 0u;
     auto launch = [&](auto kernel) {
-        return launch_slide(kernel, plan, stream, d_in, d_out, w, h, nstrips, lanes_out, plan, wts, alpha_hi, alpha_tab,
-                            d_flags);
+        return launch_slide_lds(kernel, plan, lds_bytes, stream, d_in, d_out, w, h, nstrips, lanes_out, plan, wts, alpha_hi,
+                                alpha_tab, d_flags);
     };
     return dispatch_bool(gauss_upper_clamp(wsum), [&](auto CL) {  // externally installed tables may overflow
         return dispatch_bool(ragged, [&](auto RG) {
@@ -624,7 +758,7 @@ size_t gauss_slide_flag_items(int w, int h, int nframes, int k)
     BandPlan plan;
     // only the two-kernel variants (k = 7, 9) use flags
     const hipError_t e = dispatch_int(k, std::integer_sequence<int, 7, 9>{}, [&](auto K) {
-        return slide_plan<K.value / 2>(w, h, nframes, &sp, &plan) ? hipSuccess : hipErrorInvalidValue;
+        return slide_plan<K.value / 2>(w, h, nframes, false, &sp, &plan) ? hipSuccess : hipErrorInvalidValue;  // (k = 5 only asks)
     });
     return e == hipSuccess ? (size_t)plan.nwork_a + plan.nwork_b : 0;
 }
