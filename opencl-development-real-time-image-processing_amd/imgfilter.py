@@ -506,6 +506,12 @@ class Context:
                                              int(first_frame), ctypes.c_uint32(seed), int(mode))
         _check("mi355_synth_rgba8_dev", rc, self._h)
 
+    def bgr_to_rgba_dev(self, d_bgr, d_rgba, w, h, nframes):
+        """mi355_bgr_to_rgba8_dev: packed 3-byte BGR frames (any byte alignment) to RGBA with A = 255 (dword-aligned),
+        no synchronisation."""
+        rc = self._lib.mi355_bgr_to_rgba8_dev(self._h, _vp(int(d_bgr)), _vp(int(d_rgba)), int(w), int(h), int(nframes))
+        _check("mi355_bgr_to_rgba8_dev", rc, self._h)
+
     def checksum_dev(self, d_buf, nbytes, index_base=0):
         out = ctypes.c_uint64(0)
         rc = self._lib.mi355_checksum_dev(self._h, _vp(int(d_buf)), int(nbytes), ctypes.c_uint64(index_base),
