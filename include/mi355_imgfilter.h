@@ -325,6 +325,68 @@ int mi355_filter_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, 
 int mi355_hist_gray8_dev(mi355_ctx* ctx, const void* d_in, uint32_t* d_hist, int w, int h, int nframes);
 int mi355_otsu_thresholds_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_thresh, int w, int h, int nframes);
 
+/* ---- changing the frame size: cv::resize of 8-bit frames ----------------------------------------
+ * nframes tightly packed, independent frames of src_w x src_h become nframes frames of dst_w x dst_h.  bpp is 4 (RGBA,
+ * every channel on its own, alpha included; dword-aligned device pointers) or 1 (gray8; any byte alignment, any width
+ * >= 1).  These are entry points of their own, not filter ids: the output size differs from the input size.  The
+ * interpolations keep OpenCV's enum values.  The contract is the arithmetic below — OpenCV's plain C++ path
+ * (resize.cpp), not its IPP or OpenCL paths — operation by operation.  The library is built with -ffp-contract=off:
+ * nothing below fuses a multiply with an add.
+ *   scales    doubles, computed on the host and passed to the kernel by value:
+ *               scale_x = 1.0 / ((double)dst_w / (double)src_w),  scale_y likewise from the heights.
+ *             This is not src_w / dst_w: the two differ in the last bit for many size pairs.
+ *   identity  dst == src in both dimensions: every interpolation is a copy.
+ *   NEAREST   sx = min((int)floor(dx * scale_x), src_w - 1), sy likewise; out[dy][dx] = src[sy][sx].
+ *   LINEAR    If src_w == 2*dst_w and src_h == 2*dst_h the result is AREA's (OpenCV switches there).  Otherwise
+ *             OpenCV's fixed-point path, INTER_RESIZE_COEF_BITS = 11.
+ *             Columns, for each output column dx:
+ *               fx = (float)((dx + 0.5) * scale_x - 0.5)      evaluated in fp64, rounded once
+ *               sx = (int)floorf(fx);  fx = fx - (float)sx
+ *               if sx < 0:          sx = 0,         fx = 0
+ *               if sx >= src_w - 1: sx = src_w - 1, fx = 0
+ *               a0 = (int)rintf((1.f - fx) * 2048.f);  a1 = (int)rintf(fx * 2048.f)
+ *             (rintf rounds half to even; each coefficient is rounded on its own.)
+ *             Rows, for each output row dy:
+ *               fy = (float)((dy + 0.5) * scale_y - 0.5)
+ *               sy = (int)floorf(fy);  fy = fy - (float)sy      fy is NOT clamped
+ *               b0 = (int)rintf((1.f - fy) * 2048.f);  b1 = (int)rintf(fy * 2048.f)
+ *               r0 = clamp(sy, 0, src_h - 1);  r1 = clamp(sy + 1, 0, src_h - 1)
+ *             (both rows may be the same row; the weights stay split.)
+ *             Per channel, in int:
+ *               H(r) = src[r][sx] * a0 + src[r][min(sx + 1, src_w - 1)] * a1
+ *               out  = (((b0 * (H(r0) >> 4)) >> 16) + ((b1 * (H(r1) >> 4)) >> 16) + 2) >> 2
+ *             The result always lies in 0..255; no saturation is needed.
+ *   AREA      Offered only when src_w == n * dst_w and src_h == m * dst_h with integers 1 <= n, m <=
+ *             MI355_MAX_AREA_FACTOR; anything else (upscaling, fractional factors: different OpenCV algorithms) is
+ *             MI355_ERR_UNSUPPORTED.  sum = the int sum of the n x m block.
+ *               n == m == 2:  out = (sum + 2) >> 2
+ *               otherwise:    scale = 1.f / (float)(n * m);  out = saturate_u8(rintf((float)sum * scale))
+ *             The second form is an fp32 product rounded half to even, NOT the exactly rounded quotient (over all
+ *             n, m <= 16 the two differ for 4160 of the possible sums).
+ * MI355_ERR_BAD_ARG: a null pointer or context; bpp other than 1 or 4; an unknown interp (2 included); either shape with
+ * a size <= 0 or beyond what every call here accepts (more than 6e10 pixels, or a width of 2^29 or more); for bpp 4 a
+ * device pointer that is not dword-aligned; input and output ranges that overlap, each counted with its own shape.
+ *   mi355_resize_check    pure host function: MI355_OK, MI355_ERR_BAD_ARG or MI355_ERR_UNSUPPORTED for these values,
+ *                         before any device work.
+ *   mi355_resize_dev      the rules of mi355_filter_dev: enqueues one launch on the context's stream and returns without
+ *                         synchronising.  It allocates nothing and waits for nothing — there is no table: scales and
+ *                         sizes go by value and the per-column set-up happens in the kernel — so it can be captured into
+ *                         a hipGraph from the first call on.
+ *   mi355_resize_batched  host buffers: H2D, one launch, D2H through the context's pooled buffers, each side sized by its
+ *                         own shape; prof_ns (may be NULL) gets the six timestamps of mi355_filter_batched.  Under
+ *                         MI355_INPUT_BGR bpp 4 takes 3-byte BGR frames (the expansion counts as kernel time) and bpp 1
+ *                         is MI355_ERR_UNSUPPORTED.
+ * Not offered: streamed and group forms, mi355_pool_alloc, cubic / Lanczos / INTER_LINEAR_EXACT, row pitch and ROI. */
+#define MI355_INTERP_NEAREST 0
+#define MI355_INTERP_LINEAR 1
+#define MI355_INTERP_AREA 3
+#define MI355_MAX_AREA_FACTOR 16
+int mi355_resize_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int interp);
+int mi355_resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h,
+                     int dst_w, int dst_h, int nframes, int interp);
+int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
+                         int dst_w, int dst_h, int nframes, int interp, uint64_t prof_ns[6]);
+
 /* Synthetic frames: px = hash(seed, first_frame + f, y, x), A = 255; mode 1 = smooth
  * gradient + 4-bit noise, mode 2 = flat 64 x 64 patches (constant windows: the content that sends the
  * exact-by-exception kernels down their exception path), mode 3 = gray noise (r = g = b: every pixel on the

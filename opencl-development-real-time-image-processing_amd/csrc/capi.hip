@@ -580,6 +580,74 @@ int run_host(mi355_ctx* ctx, int filter, const uint8_t* in, uint8_t* out, int w,
                            launch);
 }
 
+// The value checks of the resize calls, before any HIP call: bytes per pixel, interpolation, both shapes; then AREA's
+// integer factors.  LINEAR at exactly half size is AREA 2 x 2, which always has them.
+int check_resize(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int interp)
+{
+    if ((bpp != 1 && bpp != 4) ||
+        (interp != MI355_INTERP_NEAREST && interp != MI355_INTERP_LINEAR && interp != MI355_INTERP_AREA) ||
+        !valid_sizes(src_w, src_h, nframes) || !valid_sizes(dst_w, dst_h, nframes))
+        return MI355_ERR_BAD_ARG;
+    if (src_w >= (1 << 29) || dst_w >= (1 << 29))  // a lane's byte offset inside a row is 32-bit
+        return MI355_ERR_BAD_ARG;
+    int nx = 0, ny = 0;
+    if (interp == MI355_INTERP_AREA && !resize_area_factors(src_w, src_h, dst_w, dst_h, &nx, &ny))
+        return MI355_ERR_UNSUPPORTED;
+    return MI355_OK;
+}
+
+int resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+               int nframes, int interp)
+{
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    const int rc = check_resize(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    if (rc != MI355_OK)
+        return rc;
+    // each side counted with its own shape; the kernel reads source rows long after other waves stored theirs
+    const size_t in_bytes = (size_t)src_w * src_h * nframes * (size_t)bpp;
+    const size_t out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
+    if ((bpp == 4 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) ||
+        overlap(d_in, in_bytes, d_out, out_bytes))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_resize(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp, src_w,
+                               src_h, dst_w, dst_h, nframes, interp));
+    return MI355_OK;
+}
+
+// H2D, one launch, D2H through the pooled buffers, each side sized by its own shape
+int resize_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+                int nframes, int interp, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = check_resize(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    if (rc != MI355_OK)
+        return rc;
+    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
+    if (bgr && bpp == 1)
+        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t in_px = (size_t)src_w * src_h * nframes;
+    const size_t in_bytes = in_px * (size_t)bpp, out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
+    rc = ensure(ctx, ctx->d_in, in_bytes);
+    if (rc == MI355_OK && bgr)
+        rc = ensure(ctx, ctx->d_raw, in_px * 3);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, out_bytes);
+    if (rc != MI355_OK)
+        return rc;
+    auto launch = [&] {
+        if (bgr)  // the BGR2RGBA expansion counts as kernel time
+            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
+                                            static_cast<uint8_t*>(ctx->d_in.p), in_px));
+        return resize_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    };
+    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
+                           launch);
+}
+
 int create_common(int device, hipStream_t stream, bool own, mi355_ctx** out)
 {
     if (!out)
@@ -970,6 +1038,23 @@ MI355_API int mi355_filter_dev(mi355_ctx* ctx, int filter, const void* d_in, voi
                                int nframes, int k, float sigma)
 {
     return dispatch_dev(ctx, filter, d_in, d_out, w, h, nframes, k, sigma);
+}
+
+MI355_API int mi355_resize_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int interp)
+{
+    return check_resize(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+}
+
+MI355_API int mi355_resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w,
+                               int dst_h, int nframes, int interp)
+{
+    return resize_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+}
+
+MI355_API int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
+                                   int dst_w, int dst_h, int nframes, int interp, uint64_t prof_ns[6])
+{
+    return resize_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, interp, prof_ns);
 }
 
 // the argument checks of the two statistics calls: mi355_filter_dev's, with `nout` bytes of 4-byte aligned output

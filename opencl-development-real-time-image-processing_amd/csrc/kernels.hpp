@@ -126,6 +126,15 @@ hipError_t launch_hist_table(hipStream_t stream, const uint32_t* d_hist, uint8_t
 hipError_t launch_lut_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, const uint8_t* d_lut, int w, int h,
                             int nframes);
 
+// cv::resize of tightly packed 8-bit frames (resize.hip): bpp 4 (RGBA, dword-aligned) or 1 (gray8, any byte alignment);
+// interp 0 nearest, 1 linear (11-bit fixed point; AREA's result at exactly half size), 3 area with integer factors
+// 1 .. kResizeMaxAreaFactor (resize_area_factors says whether a size pair has them; anything else is
+// hipErrorInvalidValue).  Scales go to the kernel by value: no table, no allocation, one launch.
+constexpr int kResizeMaxAreaFactor = 16;
+bool resize_area_factors(int src_w, int src_h, int dst_w, int dst_h, int* nx, int* ny);
+hipError_t launch_resize(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w, int src_h,
+                         int dst_w, int dst_h, int nframes, int interp);
+
 // image2d_t-mode semantics of the reference (image2d.hip): filter 0 gray / 2 gauss / 3 sobel
 hipError_t launch_image2d(hipStream_t stream, int filter, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                           int k, const float* d_table);

@@ -31,6 +31,9 @@ FILTER_ERODE_GRAY8, FILTER_DILATE_GRAY8, FILTER_OPEN_GRAY8, FILTER_CLOSE_GRAY8 =
 MAX_MORPH_K = 17
 # whole-frame statistics (MI355_FILTER_EQUALIZE_GRAY8 / OTSU_GRAY8): ids 40 and 41 (32-39 unassigned), k and sigma ignored
 FILTER_EQUALIZE_GRAY8, FILTER_OTSU_GRAY8 = 40, 41
+# cv::resize (mi355_resize_*): OpenCV's enum values; AREA only with integer factors 1 .. MAX_AREA_FACTOR
+INTERP_NEAREST, INTERP_LINEAR, INTERP_AREA = 0, 1, 3
+MAX_AREA_FACTOR = 16
 GAUSS_FAST, GAUSS_EXACT = 0, 1
 INPUT_RGBA, INPUT_BGR = 0, 1
 IMPL_AUTO, IMPL_TILE, IMPL_MFMA, IMPL_VALU = 0, 1, 2, 3
@@ -132,6 +135,9 @@ def load_library(path=None):
         "mi355_filter_dev": [_vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, ctypes.c_float],
         "mi355_hist_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci],
         "mi355_otsu_thresholds_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci],
+        "mi355_resize_check": [_ci, _ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_resize_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_resize_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _u64p],
         "mi355_synth_rgba8_dev": [_vp, _vp, _ci, _ci, _ci, _ci, ctypes.c_uint32, _ci],
         "mi355_checksum_dev": [_vp, _vp, ctypes.c_size_t, ctypes.c_uint64, _u64p],
         "mi355_stream_copy_dev": [_vp, _vp, _vp, ctypes.c_size_t],
@@ -213,6 +219,13 @@ def _batch_shape(filt, frames, in_ch):
     n, h, w, c = frames.shape
     assert c == in_ch
     return n, h, w
+
+
+def resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes=1, interp=INTERP_LINEAR):
+    """mi355_resize_check, a pure host function: the code (0 ok, -1 bad argument, -4 unsupported) a resize call with
+    these values returns before any device work."""
+    return load_library().mi355_resize_check(int(bpp), int(src_w), int(src_h), int(dst_w), int(dst_h), int(nframes),
+                                             int(interp))
 
 
 def device_count():
@@ -396,6 +409,39 @@ class Context:
         """cv::threshold(THRESH_BINARY | THRESH_OTSU) to 0 / 255 of single-channel frames (MI355_FILTER_OTSU_GRAY8)."""
         return self._host_gray8(FILTER_OTSU_GRAY8, y)
 
+    # -- changing the frame size (mi355_resize_batched) ---------------------------------------------
+    def _resize_host(self, frames, bpp, dst_w, dst_h, interp, profile):
+        n, h, w = frames.shape[:3]
+        out = np.empty((n, int(dst_h), int(dst_w), 4) if bpp == 4 else (n, int(dst_h), int(dst_w)), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_resize_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), bpp, w, h,
+                                            int(dst_w), int(dst_h), n, int(interp), prof if profile else None)
+        _check("mi355_resize_batched", rc, self._h)
+        return out, list(prof)
+
+    def resize(self, rgba, dst_w, dst_h, interp=INTERP_LINEAR, profile=False):
+        """cv::resize of (h, w, 4) / (n, h, w, 4) frames to (dst_h, dst_w), every channel on its own; interp is
+        INTERP_NEAREST, INTERP_LINEAR or INTERP_AREA (integer factors only).  Under INPUT_BGR the frames have 3 channels
+        and the result is RGBA."""
+        rgba = np.ascontiguousarray(rgba, np.uint8)
+        if rgba.ndim not in (3, 4):
+            raise Mi355Error("resize", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
+        frames = rgba[None] if rgba.ndim == 3 else rgba
+        if frames.shape[3] != getattr(self, "_in_ch", 4):
+            raise Mi355Error("resize", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
+        out, prof = self._resize_host(frames, 4, dst_w, dst_h, interp, profile)
+        if rgba.ndim == 3:
+            out = out[0]
+        return (out, prof) if profile else out
+
+    def resize_gray8(self, y, dst_w, dst_h, interp=INTERP_LINEAR):
+        """cv::resize of (h, w) / (n, h, w) single-channel frames to (dst_h, dst_w)."""
+        y = np.ascontiguousarray(y, np.uint8)
+        if y.ndim not in (2, 3):
+            raise Mi355Error("resize_gray8", -1, "expected (h, w) or (n, h, w) uint8")
+        out, _ = self._resize_host(y[None] if y.ndim == 2 else y, 1, dst_w, dst_h, interp, False)
+        return out[0] if y.ndim == 2 else out
+
     def _stats_gray8(self, fn, y, per_frame, dtype):
         y = np.ascontiguousarray(y, np.uint8)
         if y.ndim not in (2, 3):
@@ -489,6 +535,13 @@ class Context:
         rc = self._lib.mi355_filter_dev(self._h, int(filt), _vp(int(d_in)), _vp(int(d_out)), int(w), int(h),
                                         int(nframes), int(k), float(sigma))
         _check("mi355_filter_dev", rc, self._h)
+
+    def resize_dev(self, d_in, d_out, bpp, sw, sh, dw, dh, nframes, interp=INTERP_LINEAR):
+        """mi355_resize_dev: nframes frames of sw x sh at d_in to dw x dh at d_out, bpp 4 (RGBA) or 1 (gray8); one
+        launch, no synchronisation, no allocation."""
+        rc = self._lib.mi355_resize_dev(self._h, _vp(int(d_in)), _vp(int(d_out)), int(bpp), int(sw), int(sh), int(dw),
+                                        int(dh), int(nframes), int(interp))
+        _check("mi355_resize_dev", rc, self._h)
 
     def hist_gray8_dev(self, d_in, d_hist, w, h, nframes):
         """mi355_hist_gray8_dev: nframes x 256 uint32 counts to d_hist (overwritten), no synchronisation."""
