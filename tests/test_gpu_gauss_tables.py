@@ -51,6 +51,7 @@ import pytest
 
 import __graft_entry__ as entry
 import gauss_tables_ref as gt
+from large_k_cases import Report as _Report
 from test_gpu_parity import _mfma_takes
 
 pytestmark = pytest.mark.gpu
@@ -90,33 +91,6 @@ def _references(oracle, batches, k, sigma=None, weights=None):
         done = dict(zip(jobs, pool.map(one, jobs)))
     return {shape: (np.stack([done[("gauss", shape, f)] for f in range(3)]),
                     np.stack([done[("pipe", shape, f)] for f in range(3)])) for shape in batches}
-
-
-class _Report:
-    """Collects every failed comparison of one test with where it failed: which frames, channels, rows and columns."""
-
-    def __init__(self):
-        self.bad = []
-
-    def _where(self, wrong):
-        idx = np.nonzero(wrong)
-        names = {4: ("frame", "row", "col", "channel"), 3: ("frame", "row", "col"), 2: ("axis 0", "axis 1")}[wrong.ndim]
-        return ", ".join("%s %d..%d" % (n, i.min(), i.max()) for n, i in zip(names, idx))
-
-    def same(self, got, ref, *tag):
-        if not np.array_equal(got, ref):
-            wrong = got != ref
-            d = np.abs(got.astype(np.int16) - ref.astype(np.int16))
-            self.bad.append("%s: %d values differ (max |d| %d; %s)" % (tag, int(wrong.sum()), int(d.max()), self._where(wrong)))
-
-    def within(self, got, ref, tol, *tag):
-        d = np.abs(got.astype(np.int16) - ref.astype(np.int16))
-        if d.max() > tol:
-            self.bad.append("%s: max |d| %d > %d at %d values (%s)" % (tag, int(d.max()), tol, int((d > tol).sum()),
-                                                                      self._where(d > tol)))
-
-    def done(self):
-        assert not self.bad, "%d failed comparisons:\n%s" % (len(self.bad), "\n".join(self.bad[:40]))
 
 
 def _away_from_the_255_block(h, w):
@@ -254,6 +228,7 @@ import numpy as np
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
 import __graft_entry__ as entry
 import gauss_tables_ref as gt
+from large_k_cases import Report as _Report
 pkg = entry.load_package(); oracle = entry.load_oracle()
 bad = []
 with pkg.Context(0) as ctx:

@@ -150,7 +150,7 @@ def test_gauss_gray8_nonseparable_table_is_applied_tap_by_tap(ctx, pkg, oracle, 
 
 
 # ---- fused chain ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k", [3, 5, 7, 9, 17])
+@pytest.mark.parametrize("k", [3, 5, 7, 9, 17, 31, 45])
 def test_pipeline_gray8_is_sobel_of_the_exact_gaussian(ctx, pkg, oracle, modes, k):
     sigma = _sigma(k)
     frames = [hash_noise(97, 301, k), flat_patches(200, 130, k), extremes(1, 9, k), extremes(5, 1, k),

@@ -34,7 +34,7 @@ FULL = (40, 252, 2)          # the shape that gets the whole off_in x off_out pr
 MATRIX = (260, 256, 1)       # >= 2^16 pixels, w >= 64, w % 4 == 0: AUTO gives k >= 7 to the matrix cores when aligned
 OFF4 = (0, 4, 8, 12)         # pointers to 4-byte pixels
 OFF1 = (0, 1, 2, 3, 4, 8, 12)  # 1-byte-per-pixel outputs
-SIGMA = {3: 0.8, 5: 1.5, 7: 2.0, 9: 2.5, 11: 3.0, 17: 6.0, 31: 10.0}
+SIGMA = {3: 0.8, 5: 1.5, 7: 2.0, 9: 2.5, 11: 3.0, 17: 6.0, 31: 10.0, 63: 20.0}
 
 
 def reduced(ins, outs):
@@ -130,9 +130,10 @@ def test_gauss_fast_valu_kernels(ctx, pkg, oracle, k):
             _fast_gauss_same_bits(ctx, pkg, oracle, shape, opaque, k, pkg.IMPL_VALU)
 
 
-@pytest.mark.parametrize("k", [5, 31])
+@pytest.mark.parametrize("k", [5, 31, 63])
 def test_gauss_tiled_kernel(ctx, pkg, oracle, k):
-    """IMPL_TILE at k 5 and, under AUTO, k 31, which only the tiled kernel takes."""
+    """IMPL_TILE at k 5 and, under AUTO, k 31 and 63, which only the tiled kernel takes; at 63 the halo is 31 pixels on
+    frames of 3 x 3 and 9 x 8 and the carve (71,820 B) needs the raised dynamic-LDS limit."""
     for shape in SHAPES:
         _fast_gauss_same_bits(ctx, pkg, oracle, shape, False, k, pkg.IMPL_TILE if k == 5 else pkg.IMPL_AUTO)
 
@@ -190,11 +191,11 @@ def _fast_chain(ctx, pkg, oracle, shape, k):
 
 
 @pytest.mark.parametrize("impl", ["AUTO", "TILE"])
-@pytest.mark.parametrize("k", [3, 5, 7, 9])
+@pytest.mark.parametrize("k", [3, 5, 7, 9, 63])
 def test_pipeline(ctx, pkg, oracle, k, impl):
     """pipe_slide (k <= 7, w >= 4, h >= 2; RAGGED when a pointer is off) gives the CPU chain's bytes in both Gaussian
-    modes, the tiled kernel in EXACT mode too; the FAST tiled kernel (k 9, IMPL_TILE, w < 4) gives the three FAST calls
-    chained, and is prefilled from them."""
+    modes, the tiled kernel in EXACT mode too; the FAST tiled kernel (k 9 and 63, IMPL_TILE, w < 4) gives the three FAST
+    calls chained, and is prefilled from them.  At 63 the halo is 32 pixels on frames of 3 x 3 and 9 x 8."""
     for shape in SHAPES:
         h, w, _ = shape
         x = frames_of(shape)
