@@ -270,11 +270,30 @@ int mi355_gauss_weights_image2d(int k, float sigma, float* out_k2);
  * mi355_hist_gray8_dev and mi355_otsu_thresholds_gray8_dev (device-resident calls, below) expose the two steps. */
 #define MI355_FILTER_EQUALIZE_GRAY8 40 /* 1 byte -> 1 byte */
 #define MI355_FILTER_OTSU_GRAY8 41     /* 1 byte -> 1 byte */
+/* Box mean: cv::blur(src, dst, Size(k, k), Point(-1, -1), BORDER_REPLICATE).  Every channel on its own, alpha included;
+ * the window is k x k, centred, with clamp-to-edge borders (the Gaussian's and the median's clamp); frames are
+ * independent.  With s = the int sum of the k * k clamped taps and d = k * k:
+ *     out = floor((2 s + d) / (2 d))
+ * the integer nearest to s / d (k is odd, so d is odd and a tie cannot occur).  Both of OpenCV's column-sum forms give
+ * exactly this — the 23-bit fixed-point form it uses when k * k <= 256, and cvRound(s * (1.0 / d)) in fp64 otherwise:
+ * both were evaluated on a CPU for every odd k from 3 to 63 and every s from 0 to 255 d, with 0 mismatches against the
+ * formula.  OpenCV is not installed where this library is built and tested, so the formula above is the contract.
+ * k must be odd with 3 <= k <= MI355_MAX_BOX_K, anything else is MI355_ERR_BAD_ARG.  sigma is ignored, no table is
+ * made, and neither the Gaussian mode nor the impl knob (MI355_IMPL_*) applies.  cv::blur's DEFAULT border is
+ * BORDER_REFLECT_101; that border is not offered — pass BORDER_REPLICATE to cv::blur when comparing.
+ * MI355_FILTER_BOX follows the RGBA rules (dword-aligned device pointers; BGR host frames under MI355_INPUT_BGR, as
+ * MEDIAN does), MI355_FILTER_BOX_GRAY8 the single-channel rules (any byte alignment, any width >= 1, UNSUPPORTED under
+ * BGR).  One launch per call, whose cost does not grow with k (running column sums down a band of rows, a prefix sum
+ * along the row); nothing is allocated and nothing is waited for, from the first call on.
+ * The ids are 48 and 49; 42 to 47 stay unassigned and invalid, as callers expect. */
+#define MI355_MAX_BOX_K 63
+#define MI355_FILTER_BOX 48       /* RGBA -> RGBA     */
+#define MI355_FILTER_BOX_GRAY8 49 /* 1 byte -> 1 byte */
 int mi355_filter_batched(mi355_ctx* ctx, int filter, const uint8_t* rgba, uint8_t* out, int w, int h,
                          int nframes, int k, float sigma, uint64_t prof_ns[6]);
 /* bytes per output pixel of a filter (4 or 1), or MI355_ERR_BAD_ARG.  Pure host function. */
 int mi355_filter_out_bpp(int filter);
-/* bytes per input pixel of a filter: 4 for the RGBA filters (ids 0-4, 16, 24-27), 1 for the *_GRAY8 ids, or MI355_ERR_BAD_ARG.
+/* bytes per input pixel of a filter: 4 for the RGBA filters (ids 0-4, 16, 24-27, 48), 1 for the *_GRAY8 ids, or MI355_ERR_BAD_ARG.
  * Pure host function.  Every buffer size of the batched, streamed, pool and group calls is counted in these bytes. */
 int mi355_filter_in_bpp(int filter);
 
@@ -386,6 +405,35 @@ int mi355_resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int
                      int dst_w, int dst_h, int nframes, int interp);
 int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
                          int dst_w, int dst_h, int nframes, int interp, uint64_t prof_ns[6]);
+
+/* ---- local threshold: cv::adaptiveThreshold(src, dst, max_value, ADAPTIVE_THRESH_MEAN_C, type, block, delta) -------
+ * gray8 frames only (the single-channel rules: tightly packed, any byte alignment, any width >= 1).  Entry points of
+ * their own, not filter ids: the parameters do not fit (k, sigma).  The argument order is OpenCV's.
+ *   mean    MI355_FILTER_BOX_GRAY8's value with k = block (OpenCV's own call uses BORDER_REPLICATE there).
+ *   idelta  computed on the host: (int)ceil(delta) for MI355_ADAPTIVE_BINARY, (int)floor(delta) for
+ *           MI355_ADAPTIVE_BINARY_INV, then clamped to [-256, 256] (beyond that the output is constant anyway).
+ *   BINARY      out = (src - mean >  -idelta) ? max_value : 0
+ *   BINARY_INV  out = (src - mean <= -idelta) ? max_value : 0
+ * OpenCV's quirk is kept: with a fractional delta the two types are not complements (ceil for one, floor for the
+ * other) — at delta = 2.5 a pixel with src - mean == -2 is "on" in both.
+ * MI355_ERR_BAD_ARG: a null pointer or context; sizes the filter calls reject; block even, below 3 or above
+ * MI355_MAX_BOX_K; max_value outside 0..255; a type other than the two below; a non-finite delta; overlapping ranges.
+ *   mi355_adaptive_threshold_check        pure host function: MI355_OK or MI355_ERR_BAD_ARG for these values.
+ *   mi355_adaptive_threshold_gray8_dev    the rules of mi355_filter_dev: ONE launch on the context's stream (the mean
+ *                                         frame never exists in memory: the compare is the epilogue of the box
+ *                                         kernel), no synchronisation, no allocation, no table, no scratch — so it can
+ *                                         be captured into a hipGraph from the first call on.
+ *   mi355_adaptive_threshold_gray8_batched  host buffers: H2D, the launch, D2H through the context's pooled buffers;
+ *                                         prof_ns (may be NULL) gets the six timestamps of mi355_filter_batched.
+ *                                         MI355_ERR_UNSUPPORTED under MI355_INPUT_BGR (a gray plane has no BGR form).
+ * Not offered: ADAPTIVE_THRESH_GAUSSIAN_C, RGBA frames, streamed and group forms, row pitch and ROI. */
+#define MI355_ADAPTIVE_BINARY 0     /* cv::THRESH_BINARY     */
+#define MI355_ADAPTIVE_BINARY_INV 1 /* cv::THRESH_BINARY_INV */
+int mi355_adaptive_threshold_check(int w, int h, int nframes, int max_value, int type, int block, double delta);
+int mi355_adaptive_threshold_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes,
+                                       int max_value, int type, int block, double delta);
+int mi355_adaptive_threshold_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
+                                           int max_value, int type, int block, double delta, uint64_t prof_ns[6]);
 
 /* Synthetic frames: px = hash(seed, first_frame + f, y, x), A = 255; mode 1 = smooth
  * gradient + 4-bit noise, mode 2 = flat 64 x 64 patches (constant windows: the content that sends the

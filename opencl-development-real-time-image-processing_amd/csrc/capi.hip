@@ -309,8 +309,9 @@ int ensure_slots(mi355_ctx* ctx, DevBuf (&slots)[mi355_ctx::kSlots], size_t need
 }
 
 // What a filter call's k and sigma must be: ignored; the Gaussian's odd 1 <= k <= MI355_MAX_GAUSS_K with a finite
-// sigma > 0; the median's odd 3 <= k <= MI355_MAX_MEDIAN_K; the morphology's odd 3 <= k <= MI355_MAX_MORPH_K.
-enum class KRule { none, gauss, median, morph };
+// sigma > 0; the median's odd 3 <= k <= MI355_MAX_MEDIAN_K; the morphology's odd 3 <= k <= MI355_MAX_MORPH_K; the box
+// mean's odd 3 <= k <= MI355_MAX_BOX_K.
+enum class KRule { none, gauss, median, morph, box };
 
 struct FilterInfo {
     int id;
@@ -342,6 +343,8 @@ constexpr FilterInfo kFilters[] = {
     {MI355_FILTER_CLOSE_GRAY8, 1, 1, KRule::morph, false, false},
     {MI355_FILTER_EQUALIZE_GRAY8, 1, 1, KRule::none, false, true},
     {MI355_FILTER_OTSU_GRAY8, 1, 1, KRule::none, false, true},
+    {MI355_FILTER_BOX, 4, 4, KRule::box, false, false},
+    {MI355_FILTER_BOX_GRAY8, 1, 1, KRule::box, false, false},
 };
 
 const FilterInfo* filter_info(int filter)
@@ -370,6 +373,7 @@ int check_filter(int filter, int w, int h, int nframes, int k, float sigma, cons
     const bool k_ok = f->k == KRule::gauss    ? valid_k(k) && valid_sigma(sigma)
                       : f->k == KRule::median ? odd_in(k, 3, MI355_MAX_MEDIAN_K)
                       : f->k == KRule::morph  ? odd_in(k, 3, MI355_MAX_MORPH_K)
+                      : f->k == KRule::box    ? odd_in(k, 3, MI355_MAX_BOX_K)
                                               : true;
     if (!k_ok || (f->below_2g && (int64_t)w * (int64_t)h >= (1ll << 31)))
         return MI355_ERR_BAD_ARG;
@@ -488,6 +492,10 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
         if (rc != MI355_OK)
             return rc;
         e = launch_lut_apply(ctx->stream, in, out, static_cast<const uint8_t*>(ctx->d_lut.p), w, h, nframes);
+        break;
+    case MI355_FILTER_BOX:
+    case MI355_FILTER_BOX_GRAY8:
+        e = launch_box(ctx->stream, in, out, w, h, nframes, k, filter == MI355_FILTER_BOX_GRAY8);
         break;
     default:
         return MI355_ERR_BAD_ARG;
@@ -646,6 +654,63 @@ int resize_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int sr
     };
     return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
                            launch);
+}
+
+// The value checks of the adaptive-threshold calls, before any HIP call.
+int check_adaptive(int w, int h, int nframes, int max_value, int type, int block, double delta)
+{
+    if (!valid_sizes(w, h, nframes) || !odd_in(block, 3, MI355_MAX_BOX_K) || max_value < 0 || max_value > 255 ||
+        (type != MI355_ADAPTIVE_BINARY && type != MI355_ADAPTIVE_BINARY_INV) || !std::isfinite(delta))
+        return MI355_ERR_BAD_ARG;
+    return MI355_OK;
+}
+
+// cv::adaptiveThreshold's integer delta: ceil for BINARY, floor for BINARY_INV; beyond +-256 the output is constant
+int adaptive_idelta(int type, double delta)
+{
+    const double d = type == MI355_ADAPTIVE_BINARY ? std::ceil(delta) : std::floor(delta);
+    return d < -256.0 ? -256 : (d > 256.0 ? 256 : (int)d);
+}
+
+int adaptive_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes, int max_value, int type,
+                 int block, double delta)
+{
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    const int rc = check_adaptive(w, h, nframes, max_value, type, block, delta);
+    if (rc != MI355_OK)
+        return rc;
+    const size_t nbytes = (size_t)w * h * nframes;
+    if (overlap(d_in, nbytes, d_out, nbytes))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_adaptive_threshold(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                                           w, h, nframes, block, max_value, type == MI355_ADAPTIVE_BINARY_INV,
+                                           adaptive_idelta(type, delta)));
+    return MI355_OK;
+}
+
+// H2D, one launch, D2H through the pooled buffers
+int adaptive_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes, int max_value, int type,
+                  int block, double delta, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = check_adaptive(w, h, nframes, max_value, type, block, delta);
+    if (rc != MI355_OK)
+        return rc;
+    if (ctx->input_format == MI355_INPUT_BGR)
+        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nbytes = (size_t)w * h * nframes;
+    rc = ensure(ctx, ctx->d_in, nbytes);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, nbytes);
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, ctx->d_in.p, in, nbytes, out, nbytes, prof_ns, [&] {
+        return adaptive_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, max_value, type, block, delta);
+    });
 }
 
 int create_common(int device, hipStream_t stream, bool own, mi355_ctx** out)
@@ -1055,6 +1120,25 @@ MI355_API int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* o
                                    int dst_w, int dst_h, int nframes, int interp, uint64_t prof_ns[6])
 {
     return resize_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, interp, prof_ns);
+}
+
+MI355_API int mi355_adaptive_threshold_check(int w, int h, int nframes, int max_value, int type, int block,
+                                             double delta)
+{
+    return check_adaptive(w, h, nframes, max_value, type, block, delta);
+}
+
+MI355_API int mi355_adaptive_threshold_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h,
+                                                 int nframes, int max_value, int type, int block, double delta)
+{
+    return adaptive_dev(ctx, d_in, d_out, w, h, nframes, max_value, type, block, delta);
+}
+
+MI355_API int mi355_adaptive_threshold_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h,
+                                                     int nframes, int max_value, int type, int block, double delta,
+                                                     uint64_t prof_ns[6])
+{
+    return adaptive_host(ctx, in, out, w, h, nframes, max_value, type, block, delta, prof_ns);
 }
 
 // the argument checks of the two statistics calls: mi355_filter_dev's, with `nout` bytes of 4-byte aligned output

@@ -135,6 +135,16 @@ bool resize_area_factors(int src_w, int src_h, int dst_w, int dst_h, int* nx, in
 hipError_t launch_resize(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w, int src_h,
                          int dst_w, int dst_h, int nframes, int interp);
 
+// cv::blur with BORDER_REPLICATE (box.hip): k x k mean, odd k in 3..MI355_MAX_BOX_K, every channel on its own; gray8 = 1
+// byte per pixel (any byte alignment), else RGBA (dword-aligned).  One register-resident running-sum kernel for every k:
+// no table, no scratch, one launch.
+hipError_t launch_box(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k,
+                      bool gray8);
+// cv::adaptiveThreshold(ADAPTIVE_THRESH_MEAN_C) of gray8 frames, the same kernel with a compare behind the mean:
+// out = (src - mean > -idelta) ? max_value : 0, or with `inverse` (src - mean <= -idelta) ? max_value : 0; one launch
+hipError_t launch_adaptive_threshold(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
+                                     int block, int max_value, bool inverse, int idelta);
+
 // image2d_t-mode semantics of the reference (image2d.hip): filter 0 gray / 2 gauss / 3 sobel
 hipError_t launch_image2d(hipStream_t stream, int filter, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
                           int k, const float* d_table);

@@ -31,6 +31,12 @@ FILTER_ERODE_GRAY8, FILTER_DILATE_GRAY8, FILTER_OPEN_GRAY8, FILTER_CLOSE_GRAY8 =
 MAX_MORPH_K = 17
 # whole-frame statistics (MI355_FILTER_EQUALIZE_GRAY8 / OTSU_GRAY8): ids 40 and 41 (32-39 unassigned), k and sigma ignored
 FILTER_EQUALIZE_GRAY8, FILTER_OTSU_GRAY8 = 40, 41
+# box mean, cv::blur with BORDER_REPLICATE (MI355_FILTER_BOX*): ids 48 and 49 (42-47 unassigned), odd 3 <= k <= MAX_BOX_K,
+# sigma ignored
+FILTER_BOX, FILTER_BOX_GRAY8 = 48, 49
+MAX_BOX_K = 63
+# cv::adaptiveThreshold(ADAPTIVE_THRESH_MEAN_C) types (mi355_adaptive_threshold_*): cv::THRESH_BINARY / THRESH_BINARY_INV
+ADAPTIVE_BINARY, ADAPTIVE_BINARY_INV = 0, 1
 # cv::resize (mi355_resize_*): OpenCV's enum values; AREA only with integer factors 1 .. MAX_AREA_FACTOR
 INTERP_NEAREST, INTERP_LINEAR, INTERP_AREA = 0, 1, 3
 MAX_AREA_FACTOR = 16
@@ -138,6 +144,10 @@ def load_library(path=None):
         "mi355_resize_check": [_ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_resize_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_resize_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _u64p],
+        "mi355_adaptive_threshold_check": [_ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double],
+        "mi355_adaptive_threshold_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double],
+        "mi355_adaptive_threshold_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double,
+                                                   _u64p],
         "mi355_synth_rgba8_dev": [_vp, _vp, _ci, _ci, _ci, _ci, ctypes.c_uint32, _ci],
         "mi355_checksum_dev": [_vp, _vp, ctypes.c_size_t, ctypes.c_uint64, _u64p],
         "mi355_stream_copy_dev": [_vp, _vp, _vp, ctypes.c_size_t],
@@ -226,6 +236,13 @@ def resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes=1, interp=INTERP_LINEA
     these values returns before any device work."""
     return load_library().mi355_resize_check(int(bpp), int(src_w), int(src_h), int(dst_w), int(dst_h), int(nframes),
                                              int(interp))
+
+
+def adaptive_threshold_check(w, h, nframes=1, max_value=255, type=ADAPTIVE_BINARY, block=3, delta=0.0):
+    """mi355_adaptive_threshold_check, a pure host function: the code (0 ok, -1 bad argument) an adaptive-threshold call
+    with these values returns before any device work."""
+    return load_library().mi355_adaptive_threshold_check(int(w), int(h), int(nframes), int(max_value), int(type),
+                                                         int(block), float(delta))
 
 
 def device_count():
@@ -409,6 +426,32 @@ class Context:
         """cv::threshold(THRESH_BINARY | THRESH_OTSU) to 0 / 255 of single-channel frames (MI355_FILTER_OTSU_GRAY8)."""
         return self._host_gray8(FILTER_OTSU_GRAY8, y)
 
+    def box(self, rgba, k, profile=False):
+        """cv::blur(Size(k, k), BORDER_REPLICATE) on every channel of (h, w, 4) / (n, h, w, 4) frames (MI355_FILTER_BOX);
+        odd 3 <= k <= MAX_BOX_K."""
+        return self._host(FILTER_BOX, rgba, k, 0.0, profile=profile)
+
+    def box_gray8(self, y, k):
+        """cv::blur(Size(k, k), BORDER_REPLICATE) of (h, w) / (n, h, w) single-channel frames (MI355_FILTER_BOX_GRAY8)."""
+        return self._host_gray8(FILTER_BOX_GRAY8, y, k)
+
+    def adaptive_threshold_gray8(self, y, max_value, type, block, delta, profile=False):
+        """cv::adaptiveThreshold(y, max_value, ADAPTIVE_THRESH_MEAN_C, type, block, delta) of (h, w) / (n, h, w)
+        single-channel frames (mi355_adaptive_threshold_gray8_batched); type is ADAPTIVE_BINARY or ADAPTIVE_BINARY_INV."""
+        y = np.ascontiguousarray(y, np.uint8)
+        if y.ndim not in (2, 3):
+            raise Mi355Error("adaptive_threshold_gray8", -1, "expected (h, w) or (n, h, w) uint8")
+        frames = y[None] if y.ndim == 2 else y
+        n, h, w = frames.shape
+        out = np.empty((n, h, w), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_adaptive_threshold_gray8_batched(
+            self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, int(max_value), int(type),
+            int(block), float(delta), prof if profile else None)
+        _check("mi355_adaptive_threshold_gray8_batched", rc, self._h)
+        out = out[0] if y.ndim == 2 else out
+        return (out, list(prof)) if profile else out
+
     # -- changing the frame size (mi355_resize_batched) ---------------------------------------------
     def _resize_host(self, frames, bpp, dst_w, dst_h, interp, profile):
         n, h, w = frames.shape[:3]
@@ -542,6 +585,14 @@ class Context:
         rc = self._lib.mi355_resize_dev(self._h, _vp(int(d_in)), _vp(int(d_out)), int(bpp), int(sw), int(sh), int(dw),
                                         int(dh), int(nframes), int(interp))
         _check("mi355_resize_dev", rc, self._h)
+
+    def adaptive_threshold_gray8_dev(self, d_in, d_out, w, h, nframes, max_value, type, block, delta):
+        """mi355_adaptive_threshold_gray8_dev: nframes gray8 frames at d_in thresholded against their block x block mean
+        into d_out; one launch, no synchronisation, no allocation."""
+        rc = self._lib.mi355_adaptive_threshold_gray8_dev(self._h, _vp(int(d_in)), _vp(int(d_out)), int(w), int(h),
+                                                          int(nframes), int(max_value), int(type), int(block),
+                                                          float(delta))
+        _check("mi355_adaptive_threshold_gray8_dev", rc, self._h)
 
     def hist_gray8_dev(self, d_in, d_hist, w, h, nframes):
         """mi355_hist_gray8_dev: nframes x 256 uint32 counts to d_hist (overwritten), no synchronisation."""
