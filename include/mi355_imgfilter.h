@@ -406,6 +406,81 @@ int mi355_resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int
 int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
                          int dst_w, int dst_h, int nframes, int interp, uint64_t prof_ns[6]);
 
+/* ---- rotating, shifting and deskewing frames: cv::warpAffine of 8-bit frames ---------------------
+ * nframes tightly packed, independent frames of src_w x src_h become nframes frames of dst_w x dst_h, all through the
+ * same 2 x 3 matrix m = {m0, m1, m2, m3, m4, m5} (row-major, as cv::Mat(2, 3, CV_64F)).  bpp is 4 (RGBA, every channel
+ * warped on its own, alpha included; dword-aligned device pointers) or 1 (gray8; any byte alignment, any width >= 1).
+ * Entry points of their own, not filter ids.  flags is MI355_INTERP_NEAREST or MI355_INTERP_LINEAR, optionally or-ed
+ * with MI355_WARP_INVERSE_MAP; anything else is MI355_ERR_BAD_ARG, MI355_INTERP_AREA included (OpenCV silently turns
+ * AREA into LINEAR; this library does not).  border_value holds the four bytes of a border pixel in memory order: R in
+ * bits 0-7, then G, B and A; gray8 uses bits 0-7 and ignores the rest.  It is used only under MI355_BORDER_CONSTANT.
+ * OpenCV is not installed where this library is built and tested, so THE ARITHMETIC BELOW IS THE CONTRACT.  It is the
+ * classic fixed-point path of cv::warpAffine (WarpAffineInvoker followed by remapNearest / remapBilinear), restated
+ * from OpenCV's source from memory — not its IPP or OpenCL paths, and not the float kernels newer OpenCV releases use.
+ * Nobody has compared it with an OpenCV build here.
+ *   matrix    mi355_warp_affine_matrix, a pure host function, fp64, no fused multiply-add (-ffp-contract=off):
+ *               with MI355_WARP_INVERSE_MAP: inv = m.  Otherwise OpenCV's inversion, operation by operation:
+ *                 D = m0*m4 - m1*m3;  D = (D != 0) ? 1.0/D : 0.0
+ *                 A11 = m4*D;  A22 = m0*D
+ *                 i0 = A11;  i1 = m1*(-D);  i3 = m3*(-D);  i4 = A22
+ *                 i2 = -i0*m2 - i1*m5;  i5 = -i3*m2 - i4*m5
+ *               A singular matrix gives the all-zero map, as in OpenCV: every output pixel samples source (0, 0).
+ *   coordinates  per output pixel (x, y), in int; rint is round-half-even (cvRound); >> is an arithmetic shift:
+ *                 adelta(x) = rint((i0 * x) * 1024.0)         bdelta(x) = rint((i3 * x) * 1024.0)
+ *                 X0(y) = rint((i1 * y + i2) * 1024.0) + rd   Y0(y) = rint((i4 * y + i5) * 1024.0) + rd
+ *                 NEAREST: rd = 512;  sx = (X0 + adelta) >> 10;  sy = (Y0 + bdelta) >> 10
+ *                 LINEAR:  rd = 16;   X = (X0 + adelta) >> 5;  Y likewise
+ *                          sx = X >> 5;  fx = X & 31;  sy = Y >> 5;  fy = Y & 31
+ *               (so NEAREST rounds to the nearest source pixel and LINEAR works on a grid of 1/32 pixel.)
+ *   sampling  per channel.  tap(u, v) = src[v][u] inside the frame; outside it is the border byte under
+ *             MI355_BORDER_CONSTANT and src[clamp(v)][clamp(u)] under MI355_BORDER_REPLICATE.
+ *               NEAREST: out = tap(sx, sy)
+ *               LINEAR:  out = ((32-fx)*(32-fy)*tap(sx, sy)   + fx*(32-fy)*tap(sx+1, sy)
+ *                             + (32-fx)*fy*tap(sx, sy+1)     + fx*fy*tap(sx+1, sy+1) + 512) >> 10
+ *             This equals OpenCV's 15-bit weight table followed by (sum + 16384) >> 15: the table entry is
+ *             32 * (32-fx or fx) * (32-fy or fy) exactly and its rows sum to 32768 with no correction step (all 1024
+ *             entries checked in fp32).  The result always lies in 0..255.  Frames are independent: a tap never reads a
+ *             neighbouring frame.
+ *   limits    MI355_ERR_BAD_ARG: a null pointer or context; bpp other than 1 or 4; bad flags or border mode; a size or
+ *             frame count <= 0 (or more than 6e10 pixels, or 2^31 tiles of work, in a call); a non-finite matrix entry;
+ *             for bpp 4 a device pointer that is not dword-aligned; input and output ranges that overlap, each counted
+ *             with its own shape.
+ *             MI355_ERR_UNSUPPORTED: a width or height above MI355_MAX_WARP_SIZE (below it OpenCV's saturation of sx,
+ *             sy to short cannot be observed, so the formula omits it); a matrix for which
+ *             |i0|*(dst_w-1) + |i1|*(dst_h-1) + |i2| >= 2^20, or the same sum for i3, i4, i5 (below that no int sum
+ *             above can overflow, and OpenCV's int saturation cannot be observed either).
+ *   mi355_rotation_matrix      cv::getRotationMatrix2D, a pure host function:
+ *                                a = cos(angle_deg*pi/180)*scale;  b = sin(angle_deg*pi/180)*scale
+ *                                m = {a, b, (1-a)*cx - b*cy, -b, a, b*cx + (1-a)*cy}
+ *                              MI355_ERR_BAD_ARG for a null m, a non-finite input and scale == 0.
+ *   mi355_warp_affine_matrix   the inverse map above; MI355_ERR_BAD_ARG for a null pointer, bad flags or a non-finite
+ *                              entry of m.
+ *   mi355_warp_affine_check    pure host function: MI355_OK, MI355_ERR_BAD_ARG or MI355_ERR_UNSUPPORTED for these
+ *                              values, before any device work.
+ *   mi355_warp_affine_dev      the rules of mi355_resize_dev: enqueues one launch on the context's stream and returns
+ *                              without synchronising.  No allocation, table or scratch: the six doubles and the sizes
+ *                              go by value, so it can be captured into a hipGraph from the first call on.
+ *   mi355_warp_affine_batched  host buffers: H2D, one launch, D2H through the context's pooled buffers, each side sized
+ *                              by its own shape; prof_ns (may be NULL) gets the six timestamps of mi355_filter_batched.
+ *                              Under MI355_INPUT_BGR bpp 4 takes 3-byte BGR frames (the expansion counts as kernel
+ *                              time) and bpp 1 is MI355_ERR_UNSUPPORTED.
+ * Not offered: warpPerspective, remap, cubic and Lanczos, BORDER_TRANSPARENT / REFLECT* / WRAP, streamed and group
+ * forms, mi355_pool_alloc, row pitch and ROI, and one matrix per frame (a stabiliser calls once per frame). */
+#define MI355_WARP_INVERSE_MAP 16 /* cv::WARP_INVERSE_MAP, or-ed into flags */
+#define MI355_BORDER_CONSTANT 0   /* cv::BORDER_CONSTANT  */
+#define MI355_BORDER_REPLICATE 1  /* cv::BORDER_REPLICATE */
+#define MI355_MAX_WARP_SIZE 32766 /* largest width / height of either shape */
+int mi355_rotation_matrix(double cx, double cy, double angle_deg, double scale, double m[6]);
+int mi355_warp_affine_matrix(const double m[6], int flags, double inv[6]);
+int mi355_warp_affine_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, const double m[6],
+                            int flags, int border_mode);
+int mi355_warp_affine_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w,
+                          int dst_h, int nframes, const double m[6], int flags, int border_mode,
+                          uint32_t border_value);
+int mi355_warp_affine_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
+                              int dst_w, int dst_h, int nframes, const double m[6], int flags, int border_mode,
+                              uint32_t border_value, uint64_t prof_ns[6]);
+
 /* ---- local threshold: cv::adaptiveThreshold(src, dst, max_value, ADAPTIVE_THRESH_MEAN_C, type, block, delta) -------
  * gray8 frames only (the single-channel rules: tightly packed, any byte alignment, any width >= 1).  Entry points of
  * their own, not filter ids: the parameters do not fit (k, sigma).  The argument order is OpenCV's.

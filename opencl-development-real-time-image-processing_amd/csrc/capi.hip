@@ -656,6 +656,118 @@ int resize_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int sr
                            launch);
 }
 
+// cv::warpAffine's inverse map: m itself under MI355_WARP_INVERSE_MAP, else OpenCV's inversion, operation by operation
+// (fp64, nothing fused: the library is built with -ffp-contract=off).  A singular matrix gives the all-zero map.
+void warp_inverse(const double m[6], int flags, double inv[6])
+{
+    if (flags & MI355_WARP_INVERSE_MAP) {
+        for (int i = 0; i < 6; i++)
+            inv[i] = m[i];
+        return;
+    }
+    double D = m[0] * m[4] - m[1] * m[3];
+    D = (D != 0.0) ? 1.0 / D : 0.0;
+    const double A11 = m[4] * D, A22 = m[0] * D;
+    inv[0] = A11;
+    inv[1] = m[1] * (-D);
+    inv[3] = m[3] * (-D);
+    inv[4] = A22;
+    inv[2] = -inv[0] * m[2] - inv[1] * m[5];
+    inv[5] = -inv[3] * m[2] - inv[4] * m[5];
+}
+
+bool warp_flags_ok(int flags)
+{
+    const int interp = flags & ~MI355_WARP_INVERSE_MAP;
+    return interp == MI355_INTERP_NEAREST || interp == MI355_INTERP_LINEAR;
+}
+
+// The value checks of the warp calls, before any HIP call: bytes per pixel, flags, border mode, both shapes, the matrix;
+// then the sizes and the inverse map the fixed-point arithmetic takes.  inv (may be null) gets the inverse map.
+int check_warp(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, const double* m, int flags,
+               int border_mode, double* inv)
+{
+    if (!m || (bpp != 1 && bpp != 4) || !warp_flags_ok(flags) ||
+        (border_mode != MI355_BORDER_CONSTANT && border_mode != MI355_BORDER_REPLICATE) || src_w <= 0 || src_h <= 0 ||
+        dst_w <= 0 || dst_h <= 0 || nframes <= 0)
+        return MI355_ERR_BAD_ARG;
+    for (int i = 0; i < 6; i++)
+        if (!std::isfinite(m[i]))
+            return MI355_ERR_BAD_ARG;
+    if (src_w > MI355_MAX_WARP_SIZE || src_h > MI355_MAX_WARP_SIZE || dst_w > MI355_MAX_WARP_SIZE ||
+        dst_h > MI355_MAX_WARP_SIZE)
+        return MI355_ERR_UNSUPPORTED;
+    double i[6];
+    warp_inverse(m, flags, i);
+    if (!valid_sizes(src_w, src_h, nframes) || !valid_sizes(dst_w, dst_h, nframes) ||
+        warp_work_items(i, dst_w, dst_h, nframes) > 0x7FFFFFF0ull)
+        return MI355_ERR_BAD_ARG;
+    const double limit = 1048576.0;  // 2^20: below it no int sum of the coordinate arithmetic overflows
+    const double rx = std::fabs(i[0]) * (double)(dst_w - 1) + std::fabs(i[1]) * (double)(dst_h - 1) + std::fabs(i[2]);
+    const double ry = std::fabs(i[3]) * (double)(dst_w - 1) + std::fabs(i[4]) * (double)(dst_h - 1) + std::fabs(i[5]);
+    if (!(rx < limit) || !(ry < limit))  // an inverse that overflowed to inf or nan lands here too
+        return MI355_ERR_UNSUPPORTED;
+    if (inv)
+        for (int k = 0; k < 6; k++)
+            inv[k] = i[k];
+    return MI355_OK;
+}
+
+int warp_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+             int nframes, const double* m, int flags, int border_mode, uint32_t border_value)
+{
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    double inv[6];
+    const int rc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv);
+    if (rc != MI355_OK)
+        return rc;
+    // each side counted with its own shape; the kernel reads source pixels long after other waves stored theirs
+    const size_t in_bytes = (size_t)src_w * src_h * nframes * (size_t)bpp;
+    const size_t out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
+    if ((bpp == 4 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) ||
+        overlap(d_in, in_bytes, d_out, out_bytes))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_warp_affine(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp,
+                                    src_w, src_h, dst_w, dst_h, nframes, inv, flags & ~MI355_WARP_INVERSE_MAP, border_mode,
+                                    border_value));
+    return MI355_OK;
+}
+
+// H2D, one launch, D2H through the pooled buffers, each side sized by its own shape
+int warp_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+              int nframes, const double* m, int flags, int border_mode, uint32_t border_value, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
+    if (bgr && bpp == 1)
+        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t in_px = (size_t)src_w * src_h * nframes;
+    const size_t in_bytes = in_px * (size_t)bpp, out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
+    rc = ensure(ctx, ctx->d_in, in_bytes);
+    if (rc == MI355_OK && bgr)
+        rc = ensure(ctx, ctx->d_raw, in_px * 3);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, out_bytes);
+    if (rc != MI355_OK)
+        return rc;
+    auto launch = [&] {
+        if (bgr)  // the BGR2RGBA expansion counts as kernel time
+            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
+                                            static_cast<uint8_t*>(ctx->d_in.p), in_px));
+        return warp_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode,
+                        border_value);
+    };
+    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
+                           launch);
+}
+
 // The value checks of the adaptive-threshold calls, before any HIP call.
 int check_adaptive(int w, int h, int nframes, int max_value, int type, int block, double delta)
 {
@@ -1120,6 +1232,53 @@ MI355_API int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* o
                                    int dst_w, int dst_h, int nframes, int interp, uint64_t prof_ns[6])
 {
     return resize_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, interp, prof_ns);
+}
+
+MI355_API int mi355_rotation_matrix(double cx, double cy, double angle_deg, double scale, double m[6])
+{
+    if (!m || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(angle_deg) || !std::isfinite(scale) ||
+        scale == 0.0)
+        return MI355_ERR_BAD_ARG;
+    const double rad = angle_deg * 3.14159265358979323846 / 180.0;
+    const double a = std::cos(rad) * scale, b = std::sin(rad) * scale;
+    m[0] = a;
+    m[1] = b;
+    m[2] = (1.0 - a) * cx - b * cy;
+    m[3] = -b;
+    m[4] = a;
+    m[5] = b * cx + (1.0 - a) * cy;
+    return MI355_OK;
+}
+
+MI355_API int mi355_warp_affine_matrix(const double m[6], int flags, double inv[6])
+{
+    if (!m || !inv || !warp_flags_ok(flags))
+        return MI355_ERR_BAD_ARG;
+    for (int i = 0; i < 6; i++)
+        if (!std::isfinite(m[i]))
+            return MI355_ERR_BAD_ARG;
+    warp_inverse(m, flags, inv);
+    return MI355_OK;
+}
+
+MI355_API int mi355_warp_affine_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes,
+                                      const double m[6], int flags, int border_mode)
+{
+    return check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
+}
+
+MI355_API int mi355_warp_affine_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h,
+                                    int dst_w, int dst_h, int nframes, const double m[6], int flags, int border_mode,
+                                    uint32_t border_value)
+{
+    return warp_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, border_value);
+}
+
+MI355_API int mi355_warp_affine_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
+                                        int dst_w, int dst_h, int nframes, const double m[6], int flags, int border_mode,
+                                        uint32_t border_value, uint64_t prof_ns[6])
+{
+    return warp_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, border_value, prof_ns);
 }
 
 MI355_API int mi355_adaptive_threshold_check(int w, int h, int nframes, int max_value, int type, int block,

@@ -135,6 +135,26 @@ bool resize_area_factors(int src_w, int src_h, int dst_w, int dst_h, int* nx, in
 hipError_t launch_resize(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w, int src_h,
                          int dst_w, int dst_h, int nframes, int interp);
 
+// cv::warpAffine of tightly packed 8-bit frames (warp.hip): bpp 4 (RGBA, dword-aligned) or 1 (gray8, any byte alignment);
+// interp 0 nearest, 1 linear (10-bit fixed-point coordinates, 1/32-pixel weights); border_mode 0 constant (border_value:
+// the pixel's four bytes in memory order, gray8 its low byte), 1 replicate.  inv maps an output pixel to its source
+// position (the caller inverts; the bound of the header's "Limits" holds).  The six doubles and the sizes go to the kernel
+// by value: no table, no allocation, one launch.  A wave owns a tile of output pixels, 4 per lane: the wide tile (64 x 16)
+// while a 64-pixel output row crosses at most kWarpWideMaxRows source rows (|inv[3]| * 64: identity, shifts, scales, a
+// deskew by a degree or two), the square tile (32 x 32) for every steeper map.  Both shapes and the rule are measured
+// choices (profiles/warp_rate.txt).  warp_work_items is the number of tiles (a launch takes fewer than 2^31).
+constexpr int kWarpMaxSize = 32766;
+constexpr int kWarpWideLanesLog2 = 4;    // 16 lanes of 4 pixels side by side
+constexpr int kWarpWideH = 16;
+constexpr int kWarpSquareLanesLog2 = 3;  // 8 lanes of 4 pixels side by side
+constexpr int kWarpSquareH = 32;
+constexpr double kWarpWideMaxRows = 3.0;
+bool warp_tile_is_wide(const double inv[6]);
+uint64_t warp_work_items(const double inv[6], int dst_w, int dst_h, int nframes);
+hipError_t launch_warp_affine(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w, int src_h,
+                              int dst_w, int dst_h, int nframes, const double inv[6], int interp, int border_mode,
+                              uint32_t border_value);
+
 // cv::blur with BORDER_REPLICATE (box.hip): k x k mean, odd k in 3..MI355_MAX_BOX_K, every channel on its own; gray8 = 1
 // byte per pixel (any byte alignment), else RGBA (dword-aligned).  One register-resident running-sum kernel for every k:
 // no table, no scratch, one launch.

@@ -1,0 +1,314 @@
+// warp.hip — cv::warpAffine of 8-bit frames (include/mi355_imgfilter.h, "Rotating, shifting and deskewing frames"):
+// NEAREST and LINEAR (OpenCV's classic fixed-point path: 10 fractional bits per coordinate, a 1/32-pixel weight grid),
+// BORDER_CONSTANT and BORDER_REPLICATE, RGBA (every channel on its own) and gray8.
+//
+// One kernel template over <bytes per pixel, interpolation, border mode>.  A work item is one wave owning a 2-D tile of
+// output pixels: a lane owns kWarpPx = 4 adjacent output columns (16 bytes per RGBA store, one dword per gray8 store where
+// the address allows it, byte stores at ragged ends and odd alignments), 2^lx_log2 lanes sit side by side and the
+// 64 >> lx_log2 lane rows walk the tile top to bottom, so the source lines of one pass are the lines the pass before
+// touched.  The host picks one of two tile shapes per launch from the map's slant (launch_warp_affine).  Tiles are ordered
+// row-major inside a frame and blocks go through xcd_remap, so the tiles of one XCD are
+// neighbours and share source lines in its L2.  The inverse map (six doubles) and the sizes come by value; per lane:
+//   adelta / bdelta  of its four columns once, in registers;
+//   X0(y) / Y0(y)    once per row it walks;
+// in the fp64 and int operations the header states.  Nothing is read from a table.
+// Whether every tap of a tile lies inside the frame is decided once per tile from the tile's four corners: adelta and X0
+// are each monotone (rint of a monotone function), so the extremes of X0(y) + adelta(x) over the tile are corner values
+// and the test is exact.  Interior tiles run with no per-tap test (RGBA LINEAR: the two horizontally adjacent taps of a
+// source row as one 8-byte load); all other tiles clamp every index into the frame and, under BORDER_CONSTANT, replace
+// the taps that lay outside.  Lanes past the right end repeat the last column and store nothing.  No access leaves a
+// frame.
+#include <cmath>
+#include <cstdio>
+
+#include "kernels.hpp"
+#include "slide_common.hpp"
+
+namespace mi355 {
+
+namespace {
+
+constexpr int kWarpPx = 4;     // output columns per lane
+constexpr int kWarpWaves = 4;  // waves (tiles) per block
+
+constexpr int kNearest = 0, kLinear = 1;     // MI355_INTERP_*
+constexpr int kConstant = 0, kReplicate = 1;  // MI355_BORDER_*
+
+struct WarpArgs {
+    const uint8_t* in;
+    uint8_t* out;
+    int sw, sh, dw, dh;
+    int lx_log2;  // lanes side by side in a tile: tile width = kWarpPx << lx_log2
+    int tile_h;   // output rows per tile, a multiple of 64 >> lx_log2
+    int tiles_x, tiles_y;
+    uint32_t nwork;
+    uint32_t border;  // RGBA: the border pixel; gray8: its byte
+    double i0, i1, i2, i3, i4, i5;
+};
+
+// rint(v * 1024.0) as int: cvRound of a coordinate in 10-bit fixed point (|v| < 2^20, so it fits)
+__device__ __forceinline__ int fix10(double v)
+{
+    return (int)__builtin_rint(v * 1024.0);
+}
+
+// four output pixels of a lane (RGBA: dwords; gray8: byte values) to columns x0 .. x0 + 3 of the row at `rowp`
+template <int BPP>
+__device__ __forceinline__ void warp_store(global_ptr<uint8_t> rowp, int x0, int dw, const uint32_t (&px)[kWarpPx])
+{
+    if constexpr (BPP == 4) {
+        if (x0 + kWarpPx <= dw) {
+            gstore_a4<u32x4>(rowp + (uint32_t)x0 * 4u, u32x4{px[0], px[1], px[2], px[3]});
+        } else {
+#pragma unroll
+            for (int j = 0; j < kWarpPx; j++)
+                if (x0 + j < dw)
+                    gstore_a4<uint32_t>(rowp + (uint32_t)(x0 + j) * 4u, px[j]);
+        }
+    } else {
+        global_ptr<uint8_t> p = rowp + (uint32_t)x0;
+        if (x0 + kWarpPx <= dw && (reinterpret_cast<uint64_t>(p) & 3u) == 0) {
+            gstore_a4<uint32_t>(p, px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24));
+        } else {
+#pragma unroll
+            for (int j = 0; j < kWarpPx; j++)
+                if (x0 + j < dw)
+                    p[j] = (uint8_t)px[j];
+        }
+    }
+}
+
+template <int BPP>
+__device__ __forceinline__ uint32_t load_px(global_ptr<const uint8_t> src, uint32_t pixel)
+{
+    if constexpr (BPP == 4)
+        return gload<uint32_t>(src + pixel * 4u);
+    else
+        return gload<uint8_t>(src + pixel);
+}
+
+// (wx0 p00 + wx1 p01) wy0 + (wx0 p10 + wx1 p11) wy1 + 512 >> 10 per channel: the four products of the header's sum,
+// regrouped (integers, nothing is rounded in between).  RGBA rows are blended as (R, B) and (G, A) u16 pairs:
+// 32 * 255 < 65536.
+template <int BPP>
+__device__ __forceinline__ uint32_t blend(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, uint32_t fx,
+                                          uint32_t fy)
+{
+    const uint32_t wx0 = 32u - fx, wx1 = fx, wy0 = 32u - fy, wy1 = fy;
+    if constexpr (BPP == 4) {
+        const uint32_t m = 0x00FF00FFu;
+        const uint32_t h0rb = (p00 & m) * wx0 + (p01 & m) * wx1, h0ga = ((p00 >> 8) & m) * wx0 + ((p01 >> 8) & m) * wx1;
+        const uint32_t h1rb = (p10 & m) * wx0 + (p11 & m) * wx1, h1ga = ((p10 >> 8) & m) * wx0 + ((p11 >> 8) & m) * wx1;
+        const uint32_t r = ((h0rb & 0xFFFFu) * wy0 + (h1rb & 0xFFFFu) * wy1 + 512u) >> 10;
+        const uint32_t b = ((h0rb >> 16) * wy0 + (h1rb >> 16) * wy1 + 512u) >> 10;
+        const uint32_t g = ((h0ga & 0xFFFFu) * wy0 + (h1ga & 0xFFFFu) * wy1 + 512u) >> 10;
+        const uint32_t al = ((h0ga >> 16) * wy0 + (h1ga >> 16) * wy1 + 512u) >> 10;
+        return r | (g << 8) | (b << 16) | (al << 24);
+    } else {
+        return ((p00 * wx0 + p01 * wx1) * wy0 + (p10 * wx0 + p11 * wx1) * wy1 + 512u) >> 10;
+    }
+}
+
+// one output pixel from its fixed-point source position (X, Y), rd already added
+template <int BPP, int INTERP, int BORDER, bool INTERIOR>
+__device__ __forceinline__ uint32_t sample(global_ptr<const uint8_t> src, const WarpArgs& a, int X, int Y)
+{
+    const int sx = X >> 10, sy = Y >> 10;
+    if constexpr (INTERP == kNearest) {
+        if constexpr (INTERIOR) {
+            return load_px<BPP>(src, (uint32_t)sy * (uint32_t)a.sw + (uint32_t)sx);
+        } else {
+            const bool in = (unsigned)sx < (unsigned)a.sw && (unsigned)sy < (unsigned)a.sh;
+            const uint32_t v = load_px<BPP>(src, (uint32_t)clampi(sy, 0, a.sh - 1) * (uint32_t)a.sw +
+                                                     (uint32_t)clampi(sx, 0, a.sw - 1));
+            return (BORDER == kConstant && !in) ? a.border : v;
+        }
+    } else {
+        const uint32_t fx = (uint32_t)(X >> 5) & 31u, fy = (uint32_t)(Y >> 5) & 31u;
+        uint32_t p00, p01, p10, p11;
+        if constexpr (INTERIOR) {
+            const uint32_t at = (uint32_t)sy * (uint32_t)a.sw + (uint32_t)sx;
+            if constexpr (BPP == 4) {
+                const u32x2 r0 = gload_a4<u32x2>(src + at * 4u);
+                const u32x2 r1 = gload_a4<u32x2>(src + (at + (uint32_t)a.sw) * 4u);
+                p00 = r0.x;
+                p01 = r0.y;
+                p10 = r1.x;
+                p11 = r1.y;
+            } else {
+                p00 = load_px<1>(src, at);
+                p01 = load_px<1>(src, at + 1u);
+                p10 = load_px<1>(src, at + (uint32_t)a.sw);
+                p11 = load_px<1>(src, at + (uint32_t)a.sw + 1u);
+            }
+        } else {
+            const bool x0in = (unsigned)sx < (unsigned)a.sw, x1in = (unsigned)(sx + 1) < (unsigned)a.sw;
+            const bool y0in = (unsigned)sy < (unsigned)a.sh, y1in = (unsigned)(sy + 1) < (unsigned)a.sh;
+            const uint32_t u0 = (uint32_t)clampi(sx, 0, a.sw - 1), u1 = (uint32_t)clampi(sx + 1, 0, a.sw - 1);
+            const uint32_t v0 = (uint32_t)clampi(sy, 0, a.sh - 1) * (uint32_t)a.sw;
+            const uint32_t v1 = (uint32_t)clampi(sy + 1, 0, a.sh - 1) * (uint32_t)a.sw;
+            p00 = load_px<BPP>(src, v0 + u0);
+            p01 = load_px<BPP>(src, v0 + u1);
+            p10 = load_px<BPP>(src, v1 + u0);
+            p11 = load_px<BPP>(src, v1 + u1);
+            if constexpr (BORDER == kConstant) {
+                p00 = (x0in && y0in) ? p00 : a.border;
+                p01 = (x1in && y0in) ? p01 : a.border;
+                p10 = (x0in && y1in) ? p10 : a.border;
+                p11 = (x1in && y1in) ? p11 : a.border;
+            }
+        }
+        return blend<BPP>(p00, p01, p10, p11, fx, fy);
+    }
+}
+
+// the lane's rows of the tile, top to bottom
+template <int BPP, int INTERP, int BORDER, bool INTERIOR>
+__device__ __forceinline__ void walk_rows(const WarpArgs& a, global_ptr<const uint8_t> src, global_ptr<uint8_t> dst,
+                                          int x0, int y_first, int y_end, int y_step, const int (&adelta)[kWarpPx],
+                                          const int (&bdelta)[kWarpPx])
+{
+    constexpr int rd = INTERP == kLinear ? 16 : 512;
+    for (int y = y_first; y < y_end; y += y_step) {
+        const int X0 = fix10(a.i1 * (double)y + a.i2) + rd;
+        const int Y0 = fix10(a.i4 * (double)y + a.i5) + rd;
+        uint32_t px[kWarpPx];
+#pragma unroll
+        for (int j = 0; j < kWarpPx; j++)
+            px[j] = sample<BPP, INTERP, BORDER, INTERIOR>(src, a, X0 + adelta[j], Y0 + bdelta[j]);
+        warp_store<BPP>(dst + (uint32_t)y * (uint32_t)a.dw * (uint32_t)BPP, x0, a.dw, px);
+    }
+}
+
+template <int BPP, int INTERP, int BORDER>
+__global__ __launch_bounds__(kWarpWaves* kWave) void warp_kernel(const WarpArgs a)
+{
+    const uint32_t block = xcd_remap(blockIdx.x, gridDim.x);
+    const uint32_t work = __builtin_amdgcn_readfirstlane(block * kWarpWaves + (uint32_t)(threadIdx.x >> 6));
+    if (work >= a.nwork)
+        return;
+    const int lane = threadIdx.x & 63;
+    const int tx = (int)(work % (uint32_t)a.tiles_x);
+    const uint32_t t = work / (uint32_t)a.tiles_x;
+    const int ty = (int)(t % (uint32_t)a.tiles_y);
+    const size_t frame = t / (uint32_t)a.tiles_y;
+    const int tile_w = kWarpPx << a.lx_log2;
+    const int tx0 = tx * tile_w, tx1 = min(tx0 + tile_w, a.dw) - 1;           // first and last column of the tile
+    const int ty0 = ty * a.tile_h, ty_end = min(ty0 + a.tile_h, a.dh);         // first row and one past the last
+    const int x0 = tx0 + (lane & ((1 << a.lx_log2) - 1)) * kWarpPx;
+    const global_ptr<const uint8_t> src = uniform_ptr(a.in + frame * ((size_t)a.sw * a.sh * BPP));
+    const global_ptr<uint8_t> dst = uniform_ptr(a.out + frame * ((size_t)a.dw * a.dh * BPP));
+
+    int adelta[kWarpPx], bdelta[kWarpPx];
+#pragma unroll
+    for (int j = 0; j < kWarpPx; j++) {
+        const double x = (double)min(x0 + j, a.dw - 1);
+        adelta[j] = fix10(a.i0 * x);
+        bdelta[j] = fix10(a.i3 * x);
+    }
+
+    // every tap of the tile inside the frame?  The extremes of X0(y) + adelta(x) over the tile are corner values.
+    constexpr int rd = INTERP == kLinear ? 16 : 512;
+    constexpr int reach = INTERP == kLinear ? 1 : 0;
+    const int ax0 = fix10(a.i0 * (double)tx0), ax1 = fix10(a.i0 * (double)tx1);
+    const int bx0 = fix10(a.i3 * (double)tx0), bx1 = fix10(a.i3 * (double)tx1);
+    const int Xa = fix10(a.i1 * (double)ty0 + a.i2) + rd, Xb = fix10(a.i1 * (double)(ty_end - 1) + a.i2) + rd;
+    const int Ya = fix10(a.i4 * (double)ty0 + a.i5) + rd, Yb = fix10(a.i4 * (double)(ty_end - 1) + a.i5) + rd;
+    const int sx_min = (min(Xa, Xb) + min(ax0, ax1)) >> 10, sx_max = ((max(Xa, Xb) + max(ax0, ax1)) >> 10) + reach;
+    const int sy_min = (min(Ya, Yb) + min(bx0, bx1)) >> 10, sy_max = ((max(Ya, Yb) + max(bx0, bx1)) >> 10) + reach;
+    const bool interior =
+        __builtin_amdgcn_readfirstlane((int)(sx_min >= 0 && sx_max <= a.sw - 1 && sy_min >= 0 && sy_max <= a.sh - 1)) != 0;
+
+    const int y_first = ty0 + (lane >> a.lx_log2), y_step = kWave >> a.lx_log2;
+    if (interior)
+        walk_rows<BPP, INTERP, BORDER, true>(a, src, dst, x0, y_first, ty_end, y_step, adelta, bdelta);
+    else
+        walk_rows<BPP, INTERP, BORDER, false>(a, src, dst, x0, y_first, ty_end, y_step, adelta, bdelta);
+}
+
+template <int BPP, int INTERP, int BORDER>
+hipError_t launch_one(hipStream_t stream, const WarpArgs& a)
+{
+    const uint32_t nblocks = (a.nwork + kWarpWaves - 1) / kWarpWaves;
+    hipLaunchKernelGGL((warp_kernel<BPP, INTERP, BORDER>), dim3(nblocks), dim3(kWarpWaves * kWave), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <int BPP>
+hipError_t launch_bpp(hipStream_t stream, const WarpArgs& a, int interp, int border_mode)
+{
+    if (interp == kNearest)
+        return border_mode == kConstant ? launch_one<BPP, kNearest, kConstant>(stream, a)
+                                        : launch_one<BPP, kNearest, kReplicate>(stream, a);
+    return border_mode == kConstant ? launch_one<BPP, kLinear, kConstant>(stream, a)
+                                    : launch_one<BPP, kLinear, kReplicate>(stream, a);
+}
+
+// The tile of a launch (kernels.hpp; both shapes and the rule between them come from the A/B of tools/warp_rate.py): the
+// wide tile while an output row stays within a few source rows, the square tile for every steeper map.  The tune build
+// takes MI355_TUNE_WARP_TILE=<lanes across, log2>x<rows> for that A/B.
+void tile_shape(const double inv[6], int* lx_log2, int* tile_h)
+{
+    const bool wide = warp_tile_is_wide(inv);
+    *lx_log2 = wide ? kWarpWideLanesLog2 : kWarpSquareLanesLog2;
+    *tile_h = wide ? kWarpWideH : kWarpSquareH;
+    if (const char* e = tune_env("MI355_TUNE_WARP_TILE")) {
+        int l = 0, h = 0;
+        if (sscanf(e, "%dx%d", &l, &h) == 2 && l >= 0 && l <= 6 && h >= (kWave >> l) && h <= 4096 && h % (kWave >> l) == 0) {
+            *lx_log2 = l;
+            *tile_h = h;
+        }
+    }
+}
+
+}  // namespace
+
+bool warp_tile_is_wide(const double inv[6])
+{
+    return std::fabs(inv[3]) * (double)(kWarpPx << kWarpWideLanesLog2) <= kWarpWideMaxRows;
+}
+
+uint64_t warp_work_items(const double inv[6], int dst_w, int dst_h, int nframes)
+{
+    int lx_log2 = 0, tile_h = 0;
+    tile_shape(inv, &lx_log2, &tile_h);
+    const int tile_w = kWarpPx << lx_log2;
+    return (uint64_t)((dst_w + tile_w - 1) / tile_w) * (uint64_t)((dst_h + tile_h - 1) / tile_h) * (uint64_t)nframes;
+}
+
+hipError_t launch_warp_affine(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w, int src_h,
+                              int dst_w, int dst_h, int nframes, const double inv[6], int interp, int border_mode,
+                              uint32_t border_value)
+{
+    if ((bpp != 1 && bpp != 4) || (interp != kNearest && interp != kLinear) ||
+        (border_mode != kConstant && border_mode != kReplicate))
+        return hipErrorInvalidValue;
+    // pixel indices inside a frame are 32-bit, times 4 bytes
+    if (src_w > kWarpMaxSize || src_h > kWarpMaxSize || dst_w > kWarpMaxSize || dst_h > kWarpMaxSize)
+        return hipErrorInvalidValue;
+    const uint64_t nwork = warp_work_items(inv, dst_w, dst_h, nframes);
+    if (nwork == 0 || nwork > 0x7FFFFFF0ull)
+        return hipErrorInvalidValue;
+    WarpArgs a{};
+    a.in = d_in;
+    a.out = d_out;
+    a.sw = src_w;
+    a.sh = src_h;
+    a.dw = dst_w;
+    a.dh = dst_h;
+    tile_shape(inv, &a.lx_log2, &a.tile_h);
+    const int tile_w = kWarpPx << a.lx_log2;
+    a.tiles_x = (dst_w + tile_w - 1) / tile_w;
+    a.tiles_y = (dst_h + a.tile_h - 1) / a.tile_h;
+    a.nwork = (uint32_t)nwork;
+    a.border = bpp == 4 ? border_value : (border_value & 0xFFu);
+    a.i0 = inv[0];
+    a.i1 = inv[1];
+    a.i2 = inv[2];
+    a.i3 = inv[3];
+    a.i4 = inv[4];
+    a.i5 = inv[5];
+    return bpp == 4 ? launch_bpp<4>(stream, a, interp, border_mode) : launch_bpp<1>(stream, a, interp, border_mode);
+}
+
+}  // namespace mi355

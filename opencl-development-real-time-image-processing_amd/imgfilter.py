@@ -40,6 +40,10 @@ ADAPTIVE_BINARY, ADAPTIVE_BINARY_INV = 0, 1
 # cv::resize (mi355_resize_*): OpenCV's enum values; AREA only with integer factors 1 .. MAX_AREA_FACTOR
 INTERP_NEAREST, INTERP_LINEAR, INTERP_AREA = 0, 1, 3
 MAX_AREA_FACTOR = 16
+# cv::warpAffine (mi355_warp_affine_*): flags = INTERP_NEAREST or INTERP_LINEAR, optionally | WARP_INVERSE_MAP
+WARP_INVERSE_MAP = 16
+BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
+MAX_WARP_SIZE = 32766
 GAUSS_FAST, GAUSS_EXACT = 0, 1
 INPUT_RGBA, INPUT_BGR = 0, 1
 IMPL_AUTO, IMPL_TILE, IMPL_MFMA, IMPL_VALU = 0, 1, 2, 3
@@ -65,6 +69,8 @@ _f32p = ctypes.POINTER(ctypes.c_float)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 _ci = ctypes.c_int
+_cd = ctypes.c_double
+_f64p = ctypes.POINTER(ctypes.c_double)
 
 
 class Mi355Error(RuntimeError):
@@ -144,6 +150,12 @@ def load_library(path=None):
         "mi355_resize_check": [_ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_resize_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_resize_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _u64p],
+        "mi355_rotation_matrix": [_cd, _cd, _cd, _cd, _f64p],
+        "mi355_warp_affine_matrix": [_f64p, _ci, _f64p],
+        "mi355_warp_affine_check": [_ci, _ci, _ci, _ci, _ci, _ci, _f64p, _ci, _ci],
+        "mi355_warp_affine_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _f64p, _ci, _ci, ctypes.c_uint32],
+        "mi355_warp_affine_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _f64p, _ci, _ci, ctypes.c_uint32,
+                                      _u64p],
         "mi355_adaptive_threshold_check": [_ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double],
         "mi355_adaptive_threshold_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double],
         "mi355_adaptive_threshold_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double,
@@ -236,6 +248,40 @@ def resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes=1, interp=INTERP_LINEA
     these values returns before any device work."""
     return load_library().mi355_resize_check(int(bpp), int(src_w), int(src_h), int(dst_w), int(dst_h), int(nframes),
                                              int(interp))
+
+
+def _matrix(m):
+    """Six doubles for the C calls from any 2 x 3 or flat sequence (None stays a null pointer)."""
+    if m is None:
+        return None
+    v = np.asarray(m, np.float64).ravel()
+    if v.size != 6:
+        raise Mi355Error("warp_affine", -1, "expected a 2 x 3 matrix")
+    return (ctypes.c_double * 6)(*v.tolist())
+
+
+def rotation_matrix(cx, cy, angle_deg, scale=1.0):
+    """mi355_rotation_matrix, cv::getRotationMatrix2D: the (2, 3) float64 matrix of a rotation by angle_deg
+    (counter-clockwise, the origin at the top-left corner) about (cx, cy) with an isotropic scale."""
+    m = (ctypes.c_double * 6)()
+    _check("mi355_rotation_matrix", load_library().mi355_rotation_matrix(float(cx), float(cy), float(angle_deg),
+                                                                         float(scale), m))
+    return np.array(list(m), np.float64).reshape(2, 3)
+
+
+def warp_affine_matrix(m, flags=INTERP_LINEAR):
+    """mi355_warp_affine_matrix: the (2, 3) float64 map from an output pixel to its source position that a warp call
+    with (m, flags) uses: m itself under WARP_INVERSE_MAP, else OpenCV's inversion."""
+    inv = (ctypes.c_double * 6)()
+    _check("mi355_warp_affine_matrix", load_library().mi355_warp_affine_matrix(_matrix(m), int(flags), inv))
+    return np.array(list(inv), np.float64).reshape(2, 3)
+
+
+def warp_affine_check(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT):
+    """mi355_warp_affine_check, a pure host function: the code (0 ok, -1 bad argument, -4 unsupported) a warp call with
+    these values returns before any device work."""
+    return load_library().mi355_warp_affine_check(int(bpp), int(src_w), int(src_h), int(dst_w), int(dst_h),
+                                                  int(nframes), _matrix(m), int(flags), int(border_mode))
 
 
 def adaptive_threshold_check(w, h, nframes=1, max_value=255, type=ADAPTIVE_BINARY, block=3, delta=0.0):
@@ -485,6 +531,44 @@ class Context:
         out, _ = self._resize_host(y[None] if y.ndim == 2 else y, 1, dst_w, dst_h, interp, False)
         return out[0] if y.ndim == 2 else out
 
+    # -- rotating, shifting and deskewing frames (mi355_warp_affine_batched) ---------------------------
+    def _warp_host(self, frames, bpp, m, dst_w, dst_h, flags, border_mode, border_value, profile):
+        n, h, w = frames.shape[:3]
+        out = np.empty((n, int(dst_h), int(dst_w), 4) if bpp == 4 else (n, int(dst_h), int(dst_w)), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_warp_affine_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), bpp, w,
+                                                 h, int(dst_w), int(dst_h), n, _matrix(m), int(flags), int(border_mode),
+                                                 int(border_value) & 0xFFFFFFFF, prof if profile else None)
+        _check("mi355_warp_affine_batched", rc, self._h)
+        return out, list(prof)
+
+    def warp_affine(self, rgba, m, dst_w, dst_h, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT, border_value=0,
+                    profile=False):
+        """cv::warpAffine of (h, w, 4) / (n, h, w, 4) frames through the 2 x 3 matrix m to (dst_h, dst_w), every channel
+        on its own; flags is INTERP_NEAREST or INTERP_LINEAR, optionally | WARP_INVERSE_MAP; border_value is
+        R | G << 8 | B << 16 | A << 24, used under BORDER_CONSTANT.  Under INPUT_BGR the frames have 3 channels and the
+        result is RGBA."""
+        rgba = np.ascontiguousarray(rgba, np.uint8)
+        if rgba.ndim not in (3, 4):
+            raise Mi355Error("warp_affine", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
+        frames = rgba[None] if rgba.ndim == 3 else rgba
+        if frames.shape[3] != getattr(self, "_in_ch", 4):
+            raise Mi355Error("warp_affine", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
+        out, prof = self._warp_host(frames, 4, m, dst_w, dst_h, flags, border_mode, border_value, profile)
+        if rgba.ndim == 3:
+            out = out[0]
+        return (out, prof) if profile else out
+
+    def warp_affine_gray8(self, y, m, dst_w, dst_h, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT, border_value=0):
+        """cv::warpAffine of (h, w) / (n, h, w) single-channel frames to (dst_h, dst_w); border_value's low byte is the
+        border under BORDER_CONSTANT."""
+        y = np.ascontiguousarray(y, np.uint8)
+        if y.ndim not in (2, 3):
+            raise Mi355Error("warp_affine_gray8", -1, "expected (h, w) or (n, h, w) uint8")
+        out, _ = self._warp_host(y[None] if y.ndim == 2 else y, 1, m, dst_w, dst_h, flags, border_mode, border_value,
+                                 False)
+        return out[0] if y.ndim == 2 else out
+
     def _stats_gray8(self, fn, y, per_frame, dtype):
         y = np.ascontiguousarray(y, np.uint8)
         if y.ndim not in (2, 3):
@@ -585,6 +669,15 @@ class Context:
         rc = self._lib.mi355_resize_dev(self._h, _vp(int(d_in)), _vp(int(d_out)), int(bpp), int(sw), int(sh), int(dw),
                                         int(dh), int(nframes), int(interp))
         _check("mi355_resize_dev", rc, self._h)
+
+    def warp_affine_dev(self, d_in, d_out, bpp, sw, sh, dw, dh, nframes, m, flags=INTERP_LINEAR,
+                        border_mode=BORDER_CONSTANT, border_value=0):
+        """mi355_warp_affine_dev: nframes frames of sw x sh at d_in through m to dw x dh at d_out, bpp 4 (RGBA) or 1
+        (gray8); one launch, no synchronisation, no allocation."""
+        rc = self._lib.mi355_warp_affine_dev(self._h, _vp(int(d_in)), _vp(int(d_out)), int(bpp), int(sw), int(sh),
+                                             int(dw), int(dh), int(nframes), _matrix(m), int(flags), int(border_mode),
+                                             int(border_value) & 0xFFFFFFFF)
+        _check("mi355_warp_affine_dev", rc, self._h)
 
     def adaptive_threshold_gray8_dev(self, d_in, d_out, w, h, nframes, max_value, type, block, delta):
         """mi355_adaptive_threshold_gray8_dev: nframes gray8 frames at d_in thresholded against their block x block mean
