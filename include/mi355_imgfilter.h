@@ -464,8 +464,9 @@ int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bp
  *                              by its own shape; prof_ns (may be NULL) gets the six timestamps of mi355_filter_batched.
  *                              Under MI355_INPUT_BGR bpp 4 takes 3-byte BGR frames (the expansion counts as kernel
  *                              time) and bpp 1 is MI355_ERR_UNSUPPORTED.
- * Not offered: warpPerspective, remap, cubic and Lanczos, BORDER_TRANSPARENT / REFLECT* / WRAP, streamed and group
- * forms, mi355_pool_alloc, row pitch and ROI, and one matrix per frame (a stabiliser calls once per frame). */
+ * Not offered: cubic and Lanczos, BORDER_TRANSPARENT / REFLECT* / WRAP, streamed and group forms, mi355_pool_alloc, row
+ * pitch and ROI, and one matrix per frame (a stabiliser calls once per frame).  warpPerspective and remap have their own
+ * section below. */
 #define MI355_WARP_INVERSE_MAP 16 /* cv::WARP_INVERSE_MAP, or-ed into flags */
 #define MI355_BORDER_CONSTANT 0   /* cv::BORDER_CONSTANT  */
 #define MI355_BORDER_REPLICATE 1  /* cv::BORDER_REPLICATE */
@@ -480,6 +481,84 @@ int mi355_warp_affine_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp
 int mi355_warp_affine_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
                               int dst_w, int dst_h, int nframes, const double m[6], int flags, int border_mode,
                               uint32_t border_value, uint64_t prof_ns[6]);
+
+/* ---- undistorting and rectifying frames: cv::remap and cv::warpPerspective of 8-bit frames -------
+ * The frame rules are those of mi355_warp_affine_*: nframes tightly packed, independent frames of src_w x src_h become
+ * nframes frames of dst_w x dst_h; bpp 4 (RGBA, every channel on its own, dword-aligned device pointers) or 1 (gray8, any
+ * byte alignment, any width >= 1); border_mode MI355_BORDER_CONSTANT or MI355_BORDER_REPLICATE with border_value as
+ * there; sizes up to MI355_MAX_WARP_SIZE.  interp is MI355_INTERP_NEAREST or MI355_INTERP_LINEAR only.
+ * OpenCV is not installed where this library is built and tested, so THE ARITHMETIC BELOW IS THE CONTRACT.  It restates
+ * OpenCV's classic fixed-point path (cv::remap on CV_16SC2 + CV_16UC1 maps, cv::convertMaps for float maps,
+ * WarpPerspectiveInvoker followed by remapNearest / remapBilinear) from memory.  Nobody has compared it with an OpenCV
+ * build here.
+ *   maps      mi355_remap_*: ONE map of dst_w x dst_h entries, row-major and tightly packed, serves all nframes frames.
+ *               MI355_MAP_FIXED  map1: int16 (sx, sy) pairs, dword-aligned; map2: uint16 fy*32+fx, 2-byte aligned; map2
+ *                                may be NULL with MI355_INTERP_NEAREST, which does not read it.
+ *               MI355_MAP_FLOAT  map1: the float x plane, map2: the float y plane, both dword-aligned.
+ *             Any other NULL and any misalignment is MI355_ERR_BAD_ARG, and so is an output range that overlaps the
+ *             input or either map.
+ *   remap coordinates  per output pixel i = y * dst_w + x; clamp16(v) = min(max(v, -32768), 32767):
+ *               FIXED:  sx = map1[2i];  sy = map1[2i+1];  LINEAR adds a = map2[i] & 1023;  fx = a & 31;  fy = a >> 5
+ *               FLOAT:  tx = map_x[i] * S in fp32, S = 32.0f for LINEAR and 1.0f for NEAREST (exact short of overflow)
+ *                       X = (int)rint(tx), round half even; a NaN tx gives INT_MIN; tx <= -2^31 gives INT_MIN and
+ *                       tx >= 2^31 gives INT_MAX.  Y likewise from map_y.
+ *                       NEAREST: sx = clamp16(X);  sy = clamp16(Y)
+ *                       LINEAR:  sx = clamp16(X >> 5);  fx = X & 31;  sy = clamp16(Y >> 5);  fy = Y & 31
+ *             (cv::convertMaps followed by FIXED gives what FLOAT gives.  With sizes <= MI355_MAX_WARP_SIZE the clamp to
+ *             short cannot be observed: a saturated index lies outside the frame either way.)
+ *   perspective matrix  mi355_perspective_matrix, a pure host function, fp64, no fused multiply-add; m is row-major, as
+ *             cv::Mat(3, 3, CV_64F).  With MI355_WARP_INVERSE_MAP: inv = m.  Otherwise the adjugate times 1 / det:
+ *               det = m0*(m4*m8 - m5*m7) - m1*(m3*m8 - m5*m6) + m2*(m3*m7 - m4*m6);  d = (det != 0) ? 1.0/det : 0.0
+ *               inv0 = (m4*m8 - m5*m7)*d;  inv1 = (m2*m7 - m1*m8)*d;  inv2 = (m1*m5 - m2*m4)*d
+ *               inv3 = (m5*m6 - m3*m8)*d;  inv4 = (m0*m8 - m2*m6)*d;  inv5 = (m2*m3 - m0*m5)*d
+ *               inv6 = (m3*m7 - m4*m6)*d;  inv7 = (m1*m6 - m0*m7)*d;  inv8 = (m0*m4 - m1*m3)*d
+ *             A singular matrix gives the all-zero map: w == 0 everywhere and every pixel samples source (0, 0), like
+ *             the affine call.  No range limit is needed: the clamp below is part of the formula.
+ *   perspective coordinates  per output pixel (x, y) from inv = h0 .. h8, all fp64, IEEE division, nothing fused; the
+ *             round brackets fix the order of operations:
+ *               w  = (h6*x) + (h7*y + h8);  s = (w != 0) ? S / w : 0      S = 32.0 for LINEAR, 1.0 for NEAREST
+ *               tX = ((h0*x) + (h1*y + h2)) * s;  tY = ((h3*x) + (h4*y + h5)) * s
+ *               fX = !(tX < 2147483647.0) ? 2147483647.0 : tX;  fX = fX < -2147483648.0 ? -2147483648.0 : fX
+ *               X  = (int)rint(fX);  Y likewise        (a NaN gives INT_MAX, as OpenCV's min / max order does)
+ *             then sx, fx, sy, fy from X and Y exactly as under FLOAT above.
+ *             One known difference: OpenCV evaluates X0 + M[0]*x1 per 32-column block from the block's first column,
+ *             which can differ from the formula above in the last bit of a double.  That cannot change a pixel unless a
+ *             coordinate lies within about 1e-12 of a rounding boundary.
+ *   sampling  tap(), NEAREST, the LINEAR sum (... + 512) >> 10 and both border rules are those of the warpAffine
+ *             section above, applied to (sx, sy, fx, fy).
+ *   limits    MI355_ERR_BAD_ARG: a null pointer or context (but see map2); bpp other than 1 or 4; an unknown map_kind,
+ *             interp (remap: anything but NEAREST and LINEAR; perspective: bad flags) or border mode; a size or frame
+ *             count <= 0 (or more than 6e10 pixels, or 2^31 tiles of work, in a call); a non-finite matrix entry; the
+ *             alignment and overlap rules above.  MI355_ERR_UNSUPPORTED: a width or height above MI355_MAX_WARP_SIZE.
+ *   mi355_remap_check, mi355_warp_perspective_check   pure host functions: the code a call with these values returns
+ *             before any device work.
+ *   mi355_remap_dev, mi355_warp_perspective_dev   the rules of mi355_warp_affine_dev: one launch on the context's
+ *             stream, no synchronisation, no allocation, table or scratch (the nine doubles go by value; the maps are the
+ *             caller's), so the first call a fresh context makes can be the captured one.
+ *   mi355_remap_batched, mi355_warp_perspective_batched   host buffers through the context's pooled buffers; the maps
+ *             (host pointers here) are uploaded on every call and count as H2D time; prof_ns (may be NULL) gets the six
+ *             timestamps of mi355_filter_batched.  MI355_INPUT_BGR behaves as in mi355_warp_affine_batched.
+ * Not offered: building undistortion maps (initUndistortRectifyMap), convertMaps as an entry point, cubic and Lanczos,
+ * other border modes, one map or one matrix per frame, group and streamed forms, row pitch and ROI. */
+#define MI355_MAP_FIXED 0 /* map1: int16 (sx, sy) pairs, map2: uint16 fy*32+fx  (CV_16SC2 + CV_16UC1, cv::convertMaps) */
+#define MI355_MAP_FLOAT 1 /* map1: float x plane, map2: float y plane           (CV_32FC1 + CV_32FC1) */
+int mi355_remap_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int map_kind, int interp,
+                      int border_mode);
+int mi355_remap_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+                    int nframes, const void* d_map1, const void* d_map2, int map_kind, int interp, int border_mode,
+                    uint32_t border_value);
+int mi355_remap_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w,
+                        int dst_h, int nframes, const void* map1, const void* map2, int map_kind, int interp,
+                        int border_mode, uint32_t border_value, uint64_t prof_ns[6]);
+int mi355_perspective_matrix(const double m[9], int flags, double inv[9]);
+int mi355_warp_perspective_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, const double m[9],
+                                 int flags, int border_mode);
+int mi355_warp_perspective_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w,
+                               int dst_h, int nframes, const double m[9], int flags, int border_mode,
+                               uint32_t border_value);
+int mi355_warp_perspective_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
+                                   int dst_w, int dst_h, int nframes, const double m[9], int flags, int border_mode,
+                                   uint32_t border_value, uint64_t prof_ns[6]);
 
 /* ---- local threshold: cv::adaptiveThreshold(src, dst, max_value, ADAPTIVE_THRESH_MEAN_C, type, block, delta) -------
  * gray8 frames only (the single-channel rules: tightly packed, any byte alignment, any width >= 1).  Entry points of

@@ -54,6 +54,7 @@ struct mi355_ctx {
     DevBuf d_flags = {};  // per-work-item flags of the two-kernel Gaussian (gauss_wide.hip)
     DevBuf d_hist = {};   // per-frame 256-bin histograms of EQUALIZE_GRAY8 / OTSU_GRAY8 (hist.hip)
     DevBuf d_lut = {};    // their per-frame 256-byte tables
+    DevBuf d_map1 = {}, d_map2 = {};  // the maps of mi355_remap_batched
     unsigned long long* d_acc = nullptr;
     float* d_img_table = nullptr;  // image2d-mode Gaussian table (k*k floats, MI355_MAX_GAUSS_K^2 capacity)
     // streamed path: copy streams, per-slot events and device slots (created on first use)
@@ -527,15 +528,19 @@ int fill_prof(mi355_ctx* ctx, uint64_t host0, uint64_t prof_ns[6])
 // Four events on the in-order stream give the six timestamps: write-end IS kernel-start and kernel-end IS read-start
 // (round 2 recorded six events and made five elapsed-time queries per call; at 75 x 75 the API calls around the three
 // operations were a third of the call).  No events at all when the caller wants no timestamps.
-template <class Launch>
+// `upload` enqueues whatever else the call sends to the device (the maps of a remap); it counts as H2D time.
+template <class Upload, class Launch>
 int timed_roundtrip(mi355_ctx* ctx, void* d_dst, const void* in, size_t in_bytes, uint8_t* out, size_t out_bytes,
-                    uint64_t prof_ns[6], Launch launch)
+                    uint64_t prof_ns[6], Upload upload, Launch launch)
 {
     hipStream_t s = ctx->stream;
     const uint64_t host0 = now_ns();
     if (prof_ns)
         HIP_TRY(ctx, hipEventRecord(ctx->ev[0], s));
     HIP_TRY(ctx, hipMemcpyAsync(d_dst, in, in_bytes, hipMemcpyHostToDevice, s));
+    const int urc = upload();
+    if (urc != MI355_OK)
+        return urc;
     if (prof_ns)
         HIP_TRY(ctx, hipEventRecord(ctx->ev[1], s));
     const int rc = launch();
@@ -550,6 +555,13 @@ int timed_roundtrip(mi355_ctx* ctx, void* d_dst, const void* in, size_t in_bytes
     if (prof_ns)
         return fill_prof(ctx, host0, prof_ns);
     return MI355_OK;
+}
+
+template <class Launch>
+int timed_roundtrip(mi355_ctx* ctx, void* d_dst, const void* in, size_t in_bytes, uint8_t* out, size_t out_bytes,
+                    uint64_t prof_ns[6], Launch launch)
+{
+    return timed_roundtrip(ctx, d_dst, in, in_bytes, out, out_bytes, prof_ns, [] { return (int)MI355_OK; }, launch);
 }
 
 // H2D, kernel, D2H through the context's pooled buffers
@@ -768,6 +780,214 @@ int warp_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_
                            launch);
 }
 
+// The argument errors every geometric call with two shapes shares
+bool bad_shapes(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int border_mode)
+{
+    return (bpp != 1 && bpp != 4) || (border_mode != MI355_BORDER_CONSTANT && border_mode != MI355_BORDER_REPLICATE) ||
+           src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0 || nframes <= 0;
+}
+
+// ... and, in the order of check_warp, the size limit and then the amount of work of remap.hip's launches
+int check_two_shapes(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int border_mode)
+{
+    if (bad_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode))
+        return MI355_ERR_BAD_ARG;
+    if (src_w > MI355_MAX_WARP_SIZE || src_h > MI355_MAX_WARP_SIZE || dst_w > MI355_MAX_WARP_SIZE ||
+        dst_h > MI355_MAX_WARP_SIZE)
+        return MI355_ERR_UNSUPPORTED;
+    if (!valid_sizes(src_w, src_h, nframes) || !valid_sizes(dst_w, dst_h, nframes) ||
+        remap_work_items(dst_w, dst_h, nframes) > 0x7FFFFFF0ull)
+        return MI355_ERR_BAD_ARG;
+    return MI355_OK;
+}
+
+// The value checks of the remap calls, before any HIP call.
+int check_remap(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int map_kind, int interp,
+                int border_mode)
+{
+    if ((map_kind != MI355_MAP_FIXED && map_kind != MI355_MAP_FLOAT) ||
+        (interp != MI355_INTERP_NEAREST && interp != MI355_INTERP_LINEAR))
+        return MI355_ERR_BAD_ARG;
+    return check_two_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode);
+}
+
+// bytes of the two maps of a remap call; map2 of FIXED + NEAREST is not read
+void map_bytes(int dst_w, int dst_h, int map_kind, size_t* n1, size_t* n2)
+{
+    const size_t entries = (size_t)dst_w * dst_h;
+    *n1 = entries * 4;
+    *n2 = entries * (map_kind == MI355_MAP_FIXED ? 2 : 4);
+}
+
+int remap_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+              int nframes, const void* d_map1, const void* d_map2, int map_kind, int interp, int border_mode,
+              uint32_t border_value)
+{
+    if (!ctx || !d_in || !d_out || !d_map1)
+        return MI355_ERR_BAD_ARG;
+    const int rc = check_remap(bpp, src_w, src_h, dst_w, dst_h, nframes, map_kind, interp, border_mode);
+    if (rc != MI355_OK)
+        return rc;
+    if (!d_map2 && !(map_kind == MI355_MAP_FIXED && interp == MI355_INTERP_NEAREST))
+        return MI355_ERR_BAD_ARG;
+    const size_t in_bytes = (size_t)src_w * src_h * nframes * (size_t)bpp;
+    const size_t out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
+    size_t n1 = 0, n2 = 0;
+    map_bytes(dst_w, dst_h, map_kind, &n1, &n2);
+    const uintptr_t align2 = map_kind == MI355_MAP_FIXED ? 1u : 3u;
+    if ((bpp == 4 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) ||
+        (reinterpret_cast<uintptr_t>(d_map1) & 3u) || (reinterpret_cast<uintptr_t>(d_map2) & align2) ||
+        overlap(d_in, in_bytes, d_out, out_bytes) || overlap(d_map1, n1, d_out, out_bytes) ||
+        (d_map2 && overlap(d_map2, n2, d_out, out_bytes)))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_remap(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp, src_w,
+                              src_h, dst_w, dst_h, nframes, d_map1, d_map2, map_kind, interp, border_mode, border_value));
+    return MI355_OK;
+}
+
+// H2D of the frames and of the maps, one launch, D2H through the pooled buffers, each side sized by its own shape
+int remap_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+               int nframes, const void* map1, const void* map2, int map_kind, int interp, int border_mode,
+               uint32_t border_value, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out || !map1)
+        return MI355_ERR_BAD_ARG;
+    int rc = check_remap(bpp, src_w, src_h, dst_w, dst_h, nframes, map_kind, interp, border_mode);
+    if (rc != MI355_OK)
+        return rc;
+    if (!map2 && !(map_kind == MI355_MAP_FIXED && interp == MI355_INTERP_NEAREST))
+        return MI355_ERR_BAD_ARG;
+    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
+    if (bgr && bpp == 1)
+        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t in_px = (size_t)src_w * src_h * nframes;
+    const size_t in_bytes = in_px * (size_t)bpp, out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
+    size_t n1 = 0, n2 = 0;
+    map_bytes(dst_w, dst_h, map_kind, &n1, &n2);
+    rc = ensure(ctx, ctx->d_in, in_bytes);
+    if (rc == MI355_OK && bgr)
+        rc = ensure(ctx, ctx->d_raw, in_px * 3);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, out_bytes);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_map1, n1);
+    if (rc == MI355_OK && map2)
+        rc = ensure(ctx, ctx->d_map2, n2);
+    if (rc != MI355_OK)
+        return rc;
+    auto upload = [&] {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map1.p, map1, n1, hipMemcpyHostToDevice, ctx->stream));
+        if (map2)
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map2.p, map2, n2, hipMemcpyHostToDevice, ctx->stream));
+        return (int)MI355_OK;
+    };
+    auto launch = [&] {
+        if (bgr)  // the BGR2RGBA expansion counts as kernel time
+            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
+                                            static_cast<uint8_t*>(ctx->d_in.p), in_px));
+        return remap_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, ctx->d_map1.p,
+                         map2 ? ctx->d_map2.p : nullptr, map_kind, interp, border_mode, border_value);
+    };
+    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
+                           upload, launch);
+}
+
+// cv::warpPerspective's inverse map: m itself under MI355_WARP_INVERSE_MAP, else the adjugate times 1 / det, operation
+// by operation (fp64, nothing fused).  A singular matrix gives the all-zero map.
+void perspective_inverse(const double m[9], int flags, double inv[9])
+{
+    if (flags & MI355_WARP_INVERSE_MAP) {
+        for (int i = 0; i < 9; i++)
+            inv[i] = m[i];
+        return;
+    }
+    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) +
+                       m[2] * (m[3] * m[7] - m[4] * m[6]);
+    const double d = (det != 0.0) ? 1.0 / det : 0.0;
+    inv[0] = (m[4] * m[8] - m[5] * m[7]) * d;
+    inv[1] = (m[2] * m[7] - m[1] * m[8]) * d;
+    inv[2] = (m[1] * m[5] - m[2] * m[4]) * d;
+    inv[3] = (m[5] * m[6] - m[3] * m[8]) * d;
+    inv[4] = (m[0] * m[8] - m[2] * m[6]) * d;
+    inv[5] = (m[2] * m[3] - m[0] * m[5]) * d;
+    inv[6] = (m[3] * m[7] - m[4] * m[6]) * d;
+    inv[7] = (m[1] * m[6] - m[0] * m[7]) * d;
+    inv[8] = (m[0] * m[4] - m[1] * m[3]) * d;
+}
+
+// The value checks of the perspective calls, before any HIP call.  inv (may be null) gets the inverse map.
+int check_perspective(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, const double* m, int flags,
+                      int border_mode, double* inv)
+{
+    // a non-finite entry is an argument error even where the size limit would answer UNSUPPORTED (check_warp's order)
+    if (!m || !warp_flags_ok(flags) || bad_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode))
+        return MI355_ERR_BAD_ARG;
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(m[i]))
+            return MI355_ERR_BAD_ARG;
+    const int rc = check_two_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode);
+    if (rc == MI355_OK && inv)
+        perspective_inverse(m, flags, inv);
+    return rc;
+}
+
+int perspective_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+                    int nframes, const double* m, int flags, int border_mode, uint32_t border_value)
+{
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    double inv[9];
+    const int rc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv);
+    if (rc != MI355_OK)
+        return rc;
+    const size_t in_bytes = (size_t)src_w * src_h * nframes * (size_t)bpp;
+    const size_t out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
+    if ((bpp == 4 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) ||
+        overlap(d_in, in_bytes, d_out, out_bytes))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_warp_perspective(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                                         bpp, src_w, src_h, dst_w, dst_h, nframes, inv, flags & ~MI355_WARP_INVERSE_MAP,
+                                         border_mode, border_value));
+    return MI355_OK;
+}
+
+// H2D, one launch, D2H through the pooled buffers, each side sized by its own shape
+int perspective_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w,
+                     int dst_h, int nframes, const double* m, int flags, int border_mode, uint32_t border_value,
+                     uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
+    if (bgr && bpp == 1)
+        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t in_px = (size_t)src_w * src_h * nframes;
+    const size_t in_bytes = in_px * (size_t)bpp, out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
+    rc = ensure(ctx, ctx->d_in, in_bytes);
+    if (rc == MI355_OK && bgr)
+        rc = ensure(ctx, ctx->d_raw, in_px * 3);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, out_bytes);
+    if (rc != MI355_OK)
+        return rc;
+    auto launch = [&] {
+        if (bgr)  // the BGR2RGBA expansion counts as kernel time
+            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
+                                            static_cast<uint8_t*>(ctx->d_in.p), in_px));
+        return perspective_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags,
+                               border_mode, border_value);
+    };
+    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
+                           launch);
+}
+
 // The value checks of the adaptive-threshold calls, before any HIP call.
 int check_adaptive(int w, int h, int nframes, int max_value, int type, int block, double delta)
 {
@@ -900,7 +1120,7 @@ MI355_API int mi355_ctx_destroy(mi355_ctx* ctx)
     for (void* p : ctx->pinned)
         (void)hipHostFree(p);
     for (void* p : {(void*)ctx->d_acc, (void*)ctx->d_img_table, ctx->d_in.p, ctx->d_out.p, ctx->d_raw.p, ctx->d_flags.p,
-                    ctx->d_hist.p, ctx->d_lut.p})
+                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_map1.p, ctx->d_map2.p})
         if (p)
             (void)hipFree(p);
     for (int i = 0; i < mi355_ctx::kSlots; i++) {
@@ -1279,6 +1499,61 @@ MI355_API int mi355_warp_affine_batched(mi355_ctx* ctx, const uint8_t* in, uint8
                                         uint32_t border_value, uint64_t prof_ns[6])
 {
     return warp_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, border_value, prof_ns);
+}
+
+MI355_API int mi355_remap_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int map_kind,
+                                int interp, int border_mode)
+{
+    return check_remap(bpp, src_w, src_h, dst_w, dst_h, nframes, map_kind, interp, border_mode);
+}
+
+MI355_API int mi355_remap_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w,
+                              int dst_h, int nframes, const void* d_map1, const void* d_map2, int map_kind, int interp,
+                              int border_mode, uint32_t border_value)
+{
+    return remap_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes, d_map1, d_map2, map_kind, interp,
+                     border_mode, border_value);
+}
+
+MI355_API int mi355_remap_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
+                                  int dst_w, int dst_h, int nframes, const void* map1, const void* map2, int map_kind,
+                                  int interp, int border_mode, uint32_t border_value, uint64_t prof_ns[6])
+{
+    return remap_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, map1, map2, map_kind, interp, border_mode,
+                      border_value, prof_ns);
+}
+
+MI355_API int mi355_perspective_matrix(const double m[9], int flags, double inv[9])
+{
+    if (!m || !inv || !warp_flags_ok(flags))
+        return MI355_ERR_BAD_ARG;
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(m[i]))
+            return MI355_ERR_BAD_ARG;
+    perspective_inverse(m, flags, inv);
+    return MI355_OK;
+}
+
+MI355_API int mi355_warp_perspective_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes,
+                                           const double m[9], int flags, int border_mode)
+{
+    return check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
+}
+
+MI355_API int mi355_warp_perspective_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h,
+                                         int dst_w, int dst_h, int nframes, const double m[9], int flags,
+                                         int border_mode, uint32_t border_value)
+{
+    return perspective_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode,
+                           border_value);
+}
+
+MI355_API int mi355_warp_perspective_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w,
+                                             int src_h, int dst_w, int dst_h, int nframes, const double m[9], int flags,
+                                             int border_mode, uint32_t border_value, uint64_t prof_ns[6])
+{
+    return perspective_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, border_value,
+                            prof_ns);
 }
 
 MI355_API int mi355_adaptive_threshold_check(int w, int h, int nframes, int max_value, int type, int block,

@@ -155,6 +155,28 @@ hipError_t launch_warp_affine(hipStream_t stream, const uint8_t* d_in, uint8_t* 
                               int dst_w, int dst_h, int nframes, const double inv[6], int interp, int border_mode,
                               uint32_t border_value);
 
+// cv::remap and cv::warpPerspective of tightly packed 8-bit frames (remap.hip), with the frame, interp and border rules
+// of launch_warp_affine.  launch_remap: one map of dst_w x dst_h entries for all frames; map_kind 0 (FIXED) takes int16
+// (sx, sy) pairs at d_map1 (dword-aligned) and uint16 fy*32+fx at d_map2 (2-byte aligned; may be null for NEAREST),
+// map_kind 1 (FLOAT) takes the x plane and the y plane (both dword-aligned).  launch_warp_perspective: inv maps an
+// output pixel to its source position (the caller inverts); the nine doubles go to the kernel by value.  No table, no
+// allocation, one launch each.  A wave owns a tile of output pixels, 4 per lane, across kRemapFrames consecutive frames
+// (the map entry or the division is paid once per chunk), and votes per row pass whether it needs border tests.  The
+// tile (32 x 32, warp.hip's square tile) and kRemapFrames are measured choices (profiles/remap_rate.txt): 4 frames are
+// the best candidate or within 2.5 % of it for every map and save up to 38 % on a keystone, at up to 7 % on a homography
+// that is a steep turn; the square tile beats the wide one on RGBA and on every turned map.
+// remap_work_items is the number of work items of a launch (a launch takes fewer than 2^31).
+constexpr int kRemapLanesLog2 = 3;  // 8 lanes of 4 pixels side by side
+constexpr int kRemapTileH = 32;
+constexpr int kRemapFrames = 4;  // frames per work item
+uint64_t remap_work_items(int dst_w, int dst_h, int nframes);
+hipError_t launch_remap(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w, int src_h,
+                        int dst_w, int dst_h, int nframes, const void* d_map1, const void* d_map2, int map_kind,
+                        int interp, int border_mode, uint32_t border_value);
+hipError_t launch_warp_perspective(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w,
+                                   int src_h, int dst_w, int dst_h, int nframes, const double inv[9], int interp,
+                                   int border_mode, uint32_t border_value);
+
 // cv::blur with BORDER_REPLICATE (box.hip): k x k mean, odd k in 3..MI355_MAX_BOX_K, every channel on its own; gray8 = 1
 // byte per pixel (any byte alignment), else RGBA (dword-aligned).  One register-resident running-sum kernel for every k:
 // no table, no scratch, one launch.

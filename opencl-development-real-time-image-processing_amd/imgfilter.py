@@ -44,6 +44,8 @@ MAX_AREA_FACTOR = 16
 WARP_INVERSE_MAP = 16
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
 MAX_WARP_SIZE = 32766
+# cv::remap (mi355_remap_*): FIXED = int16 (sx, sy) pairs + uint16 fy*32+fx (cv::convertMaps), FLOAT = float x and y planes
+MAP_FIXED, MAP_FLOAT = 0, 1
 GAUSS_FAST, GAUSS_EXACT = 0, 1
 INPUT_RGBA, INPUT_BGR = 0, 1
 IMPL_AUTO, IMPL_TILE, IMPL_MFMA, IMPL_VALU = 0, 1, 2, 3
@@ -156,6 +158,15 @@ def load_library(path=None):
         "mi355_warp_affine_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _f64p, _ci, _ci, ctypes.c_uint32],
         "mi355_warp_affine_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _f64p, _ci, _ci, ctypes.c_uint32,
                                       _u64p],
+        "mi355_remap_check": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_remap_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, ctypes.c_uint32],
+        "mi355_remap_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, ctypes.c_uint32,
+                                _u64p],
+        "mi355_perspective_matrix": [_f64p, _ci, _f64p],
+        "mi355_warp_perspective_check": [_ci, _ci, _ci, _ci, _ci, _ci, _f64p, _ci, _ci],
+        "mi355_warp_perspective_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _f64p, _ci, _ci, ctypes.c_uint32],
+        "mi355_warp_perspective_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _f64p, _ci, _ci,
+                                           ctypes.c_uint32, _u64p],
         "mi355_adaptive_threshold_check": [_ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double],
         "mi355_adaptive_threshold_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double],
         "mi355_adaptive_threshold_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double,
@@ -282,6 +293,52 @@ def warp_affine_check(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags=INTERP_
     these values returns before any device work."""
     return load_library().mi355_warp_affine_check(int(bpp), int(src_w), int(src_h), int(dst_w), int(dst_h),
                                                   int(nframes), _matrix(m), int(flags), int(border_mode))
+
+
+def _matrix9(m):
+    """Nine doubles for the C calls from any 3 x 3 or flat sequence (None stays a null pointer)."""
+    if m is None:
+        return None
+    v = np.asarray(m, np.float64).ravel()
+    if v.size != 9:
+        raise Mi355Error("warp_perspective", -1, "expected a 3 x 3 matrix")
+    return (ctypes.c_double * 9)(*v.tolist())
+
+
+def perspective_matrix(m, flags=INTERP_LINEAR):
+    """mi355_perspective_matrix: the (3, 3) float64 map from an output pixel to its source position that a perspective
+    call with (m, flags) uses: m itself under WARP_INVERSE_MAP, else the adjugate times 1 / det."""
+    inv = (ctypes.c_double * 9)()
+    _check("mi355_perspective_matrix", load_library().mi355_perspective_matrix(_matrix9(m), int(flags), inv))
+    return np.array(list(inv), np.float64).reshape(3, 3)
+
+
+def warp_perspective_check(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags=INTERP_LINEAR,
+                           border_mode=BORDER_CONSTANT):
+    """mi355_warp_perspective_check, a pure host function: the code (0 ok, -1 bad argument, -4 unsupported) a
+    perspective call with these values returns before any device work."""
+    return load_library().mi355_warp_perspective_check(int(bpp), int(src_w), int(src_h), int(dst_w), int(dst_h),
+                                                       int(nframes), _matrix9(m), int(flags), int(border_mode))
+
+
+def remap_check(bpp, src_w, src_h, dst_w, dst_h, nframes=1, map_kind=MAP_FIXED, interp=INTERP_LINEAR,
+                border_mode=BORDER_CONSTANT):
+    """mi355_remap_check, a pure host function: the code (0 ok, -1 bad argument, -4 unsupported) a remap call with these
+    values returns before any device work."""
+    return load_library().mi355_remap_check(int(bpp), int(src_w), int(src_h), int(dst_w), int(dst_h), int(nframes),
+                                            int(map_kind), int(interp), int(border_mode))
+
+
+def _host_maps(fn, map1, map2, map_kind, dst_w, dst_h):
+    """The two maps of a host remap call as contiguous arrays of the kind's types and of dst_h x dst_w entries (map2
+    None stays a null pointer: FIXED + NEAREST does not read it)."""
+    fixed = int(map_kind) == MAP_FIXED
+    m1 = np.ascontiguousarray(map1, np.int16 if fixed else np.float32)
+    m2 = None if map2 is None else np.ascontiguousarray(map2, np.uint16 if fixed else np.float32)
+    n = int(dst_w) * int(dst_h)
+    if m1.size != (2 * n if fixed else n) or (m2 is not None and m2.size != n):
+        raise Mi355Error(fn, -1, "expected maps of dst_h x dst_w entries")
+    return m1, m2
 
 
 def adaptive_threshold_check(w, h, nframes=1, max_value=255, type=ADAPTIVE_BINARY, block=3, delta=0.0):
@@ -569,6 +626,86 @@ class Context:
                                  False)
         return out[0] if y.ndim == 2 else out
 
+    # -- undistorting and rectifying frames (mi355_remap_batched, mi355_warp_perspective_batched) ----
+    def _remap_host(self, frames, bpp, map1, map2, map_kind, dst_w, dst_h, interp, border_mode, border_value, profile):
+        n, h, w = frames.shape[:3]
+        m1, m2 = _host_maps("remap", map1, map2, map_kind, dst_w, dst_h)
+        out = np.empty((n, int(dst_h), int(dst_w), 4) if bpp == 4 else (n, int(dst_h), int(dst_w)), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_remap_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), bpp, w, h,
+                                           int(dst_w), int(dst_h), n, _vp(m1.ctypes.data),
+                                           None if m2 is None else _vp(m2.ctypes.data), int(map_kind), int(interp),
+                                           int(border_mode), int(border_value) & 0xFFFFFFFF, prof if profile else None)
+        _check("mi355_remap_batched", rc, self._h)
+        return out, list(prof)
+
+    def remap(self, rgba, map1, map2, dst_w, dst_h, map_kind=MAP_FIXED, interp=INTERP_LINEAR,
+              border_mode=BORDER_CONSTANT, border_value=0, profile=False):
+        """cv::remap of (h, w, 4) / (n, h, w, 4) frames through one map to (dst_h, dst_w), every channel on its own.
+        MAP_FIXED: map1 (dst_h, dst_w, 2) int16 (sx, sy), map2 (dst_h, dst_w) uint16 fy*32+fx (None with
+        INTERP_NEAREST); MAP_FLOAT: map1 and map2 (dst_h, dst_w) float32 x and y.  border_value is
+        R | G << 8 | B << 16 | A << 24, used under BORDER_CONSTANT.  Under INPUT_BGR the frames have 3 channels and the
+        result is RGBA."""
+        rgba = np.ascontiguousarray(rgba, np.uint8)
+        if rgba.ndim not in (3, 4):
+            raise Mi355Error("remap", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
+        frames = rgba[None] if rgba.ndim == 3 else rgba
+        if frames.shape[3] != getattr(self, "_in_ch", 4):
+            raise Mi355Error("remap", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
+        out, prof = self._remap_host(frames, 4, map1, map2, map_kind, dst_w, dst_h, interp, border_mode, border_value,
+                                     profile)
+        if rgba.ndim == 3:
+            out = out[0]
+        return (out, prof) if profile else out
+
+    def remap_gray8(self, y, map1, map2, dst_w, dst_h, map_kind=MAP_FIXED, interp=INTERP_LINEAR,
+                    border_mode=BORDER_CONSTANT, border_value=0):
+        """cv::remap of (h, w) / (n, h, w) single-channel frames to (dst_h, dst_w); border_value's low byte is the
+        border under BORDER_CONSTANT."""
+        y = np.ascontiguousarray(y, np.uint8)
+        if y.ndim not in (2, 3):
+            raise Mi355Error("remap_gray8", -1, "expected (h, w) or (n, h, w) uint8")
+        out, _ = self._remap_host(y[None] if y.ndim == 2 else y, 1, map1, map2, map_kind, dst_w, dst_h, interp,
+                                  border_mode, border_value, False)
+        return out[0] if y.ndim == 2 else out
+
+    def _perspective_host(self, frames, bpp, m, dst_w, dst_h, flags, border_mode, border_value, profile):
+        n, h, w = frames.shape[:3]
+        out = np.empty((n, int(dst_h), int(dst_w), 4) if bpp == 4 else (n, int(dst_h), int(dst_w)), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_warp_perspective_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p),
+                                                      bpp, w, h, int(dst_w), int(dst_h), n, _matrix9(m), int(flags),
+                                                      int(border_mode), int(border_value) & 0xFFFFFFFF,
+                                                      prof if profile else None)
+        _check("mi355_warp_perspective_batched", rc, self._h)
+        return out, list(prof)
+
+    def warp_perspective(self, rgba, m, dst_w, dst_h, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT, border_value=0,
+                         profile=False):
+        """cv::warpPerspective of (h, w, 4) / (n, h, w, 4) frames through the 3 x 3 matrix m to (dst_h, dst_w), every
+        channel on its own; flags, border_value and INPUT_BGR as in warp_affine."""
+        rgba = np.ascontiguousarray(rgba, np.uint8)
+        if rgba.ndim not in (3, 4):
+            raise Mi355Error("warp_perspective", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
+        frames = rgba[None] if rgba.ndim == 3 else rgba
+        if frames.shape[3] != getattr(self, "_in_ch", 4):
+            raise Mi355Error("warp_perspective", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
+        out, prof = self._perspective_host(frames, 4, m, dst_w, dst_h, flags, border_mode, border_value, profile)
+        if rgba.ndim == 3:
+            out = out[0]
+        return (out, prof) if profile else out
+
+    def warp_perspective_gray8(self, y, m, dst_w, dst_h, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT,
+                               border_value=0):
+        """cv::warpPerspective of (h, w) / (n, h, w) single-channel frames to (dst_h, dst_w); border_value's low byte is
+        the border under BORDER_CONSTANT."""
+        y = np.ascontiguousarray(y, np.uint8)
+        if y.ndim not in (2, 3):
+            raise Mi355Error("warp_perspective_gray8", -1, "expected (h, w) or (n, h, w) uint8")
+        out, _ = self._perspective_host(y[None] if y.ndim == 2 else y, 1, m, dst_w, dst_h, flags, border_mode,
+                                        border_value, False)
+        return out[0] if y.ndim == 2 else out
+
     def _stats_gray8(self, fn, y, per_frame, dtype):
         y = np.ascontiguousarray(y, np.uint8)
         if y.ndim not in (2, 3):
@@ -678,6 +815,25 @@ class Context:
                                              int(dw), int(dh), int(nframes), _matrix(m), int(flags), int(border_mode),
                                              int(border_value) & 0xFFFFFFFF)
         _check("mi355_warp_affine_dev", rc, self._h)
+
+    def remap_dev(self, d_in, d_out, bpp, sw, sh, dw, dh, nframes, d_map1, d_map2, map_kind=MAP_FIXED,
+                  interp=INTERP_LINEAR, border_mode=BORDER_CONSTANT, border_value=0):
+        """mi355_remap_dev: nframes frames of sw x sh at d_in through the device maps d_map1 / d_map2 (dw x dh entries;
+        d_map2 0 or None with MAP_FIXED and INTERP_NEAREST) to dw x dh at d_out, bpp 4 (RGBA) or 1 (gray8); one launch,
+        no synchronisation, no allocation."""
+        rc = self._lib.mi355_remap_dev(self._h, _vp(int(d_in)), _vp(int(d_out)), int(bpp), int(sw), int(sh), int(dw),
+                                       int(dh), int(nframes), _vp(int(d_map1 or 0)), _vp(int(d_map2 or 0)),
+                                       int(map_kind), int(interp), int(border_mode), int(border_value) & 0xFFFFFFFF)
+        _check("mi355_remap_dev", rc, self._h)
+
+    def warp_perspective_dev(self, d_in, d_out, bpp, sw, sh, dw, dh, nframes, m, flags=INTERP_LINEAR,
+                             border_mode=BORDER_CONSTANT, border_value=0):
+        """mi355_warp_perspective_dev: nframes frames of sw x sh at d_in through the 3 x 3 matrix m to dw x dh at d_out,
+        bpp 4 (RGBA) or 1 (gray8); one launch, no synchronisation, no allocation."""
+        rc = self._lib.mi355_warp_perspective_dev(self._h, _vp(int(d_in)), _vp(int(d_out)), int(bpp), int(sw), int(sh),
+                                                  int(dw), int(dh), int(nframes), _matrix9(m), int(flags),
+                                                  int(border_mode), int(border_value) & 0xFFFFFFFF)
+        _check("mi355_warp_perspective_dev", rc, self._h)
 
     def adaptive_threshold_gray8_dev(self, d_in, d_out, w, h, nframes, max_value, type, block, delta):
         """mi355_adaptive_threshold_gray8_dev: nframes gray8 frames at d_in thresholded against their block x block mean
