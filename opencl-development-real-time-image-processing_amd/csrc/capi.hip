@@ -390,6 +390,20 @@ bool overlap(const void* a, size_t na, const void* b, size_t nb)
     return a0 < b0 + nb && b0 < a0 + na;
 }
 
+size_t frame_bytes(int w, int h, int nframes, int bpp) { return (size_t)w * h * nframes * (size_t)bpp; }
+
+// What every device-resident call refuses of its frame pointers, each side counted with its own shape and bytes per
+// pixel.  RGBA pixels are accessed as dwords.  The stencil and geometric kernels read neighbouring rows / halo / source
+// pixels of what another wave may already have overwritten, and the (pointwise) grayscale kernels are compiled for
+// non-aliasing pointers (__restrict__, non-temporal accesses): in-place and overlapping calls are rejected, not run,
+// for every call (the reference never aliases them either: two clCreateBuffer objects per call,
+// RT/src/Controller.cpp:234-244)
+bool bad_dev_io(const void* d_in, size_t in_bytes, int in_bpp, const void* d_out, size_t out_bytes, int out_bpp)
+{
+    return (in_bpp == 4 && (reinterpret_cast<uintptr_t>(d_in) & 3u)) ||
+           (out_bpp == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u)) || overlap(d_in, in_bytes, d_out, out_bytes);
+}
+
 // EQUALIZE_GRAY8 / OTSU_GRAY8 up to the table: the pooled histograms, zeroed in-stream, the histogram launch and the
 // table launch (into the pooled tables; Otsu's thresholds also to d_thresh when it is not null).  Only the first call
 // for a larger frame count allocates (and synchronises, in ensure()).
@@ -417,14 +431,8 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
     int rc = check_filter(filter, w, h, nframes, k, sigma, &f);
     if (rc != MI355_OK)
         return rc;
-    // RGBA pixels are accessed as dwords.  The stencil kernels read neighbouring rows / halo pixels of what another
-    // wave may already have overwritten, and the (pointwise) grayscale kernels are compiled for non-aliasing pointers
-    // (__restrict__, non-temporal accesses): in-place and overlapping calls are rejected, not run, for every filter
-    // (the reference never aliases them either: two clCreateBuffer objects per call, RT/src/Controller.cpp:234-244)
-    const size_t npx = (size_t)w * h * nframes;
-    if ((f->in_bpp == 4 && (reinterpret_cast<uintptr_t>(d_in) & 3u)) ||
-        (f->out_bpp == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u)) ||
-        overlap(d_in, npx * (size_t)f->in_bpp, d_out, npx * (size_t)f->out_bpp))
+    if (bad_dev_io(d_in, frame_bytes(w, h, nframes, f->in_bpp), f->in_bpp, d_out, frame_bytes(w, h, nframes, f->out_bpp),
+                   f->out_bpp))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const GaussCoef* coef = nullptr;
@@ -564,6 +572,54 @@ int timed_roundtrip(mi355_ctx* ctx, void* d_dst, const void* in, size_t in_bytes
     return timed_roundtrip(ctx, d_dst, in, in_bytes, out, out_bytes, prof_ns, [] { return (int)MI355_OK; }, launch);
 }
 
+// What a host-buffer call has staged for its round trip through the pooled buffers d_in / d_raw / d_out
+struct HostIO {
+    bool bgr;  // the host sends 3-byte BGR pixels to d_raw; they are expanded to RGBA in d_in on the device
+    size_t in_px, in_bytes, out_bytes;
+};
+
+// The untimed half of every host-buffer call, after the call's own pointer and value checks: the input-format rule, the
+// device, and the pooled buffers for `in_px` pixels of `in_bpp` bytes each as the kernel reads them (4 or 1) and
+// `out_bytes` of output.  Whatever may allocate, free or wait happens here (and in what the caller adds after it: its
+// coefficient table, its maps), never inside the timed window.
+int stage_host(mi355_ctx* ctx, size_t in_px, int in_bpp, size_t out_bytes, HostIO* io)
+{
+    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
+    if (bgr && in_bpp == 1)
+        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    *io = {bgr, in_px, in_px * (size_t)in_bpp, out_bytes};
+    int rc = ensure(ctx, ctx->d_in, io->in_bytes);
+    if (rc == MI355_OK && bgr)
+        rc = ensure(ctx, ctx->d_raw, in_px * 3);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, out_bytes);
+    return rc;
+}
+
+// The timed half: the round trip of what stage_host prepared.  launch() runs the call's kernels from ctx->d_in to
+// ctx->d_out; under MI355_INPUT_BGR the BGR2RGBA expansion goes in front of it and counts as kernel time.
+template <class Upload, class Launch>
+int timed_roundtrip(mi355_ctx* ctx, const HostIO& io, const uint8_t* in, uint8_t* out, uint64_t prof_ns[6],
+                    Upload upload, Launch launch)
+{
+    auto kernels = [&]() -> int {
+        if (io.bgr)
+            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
+                                            static_cast<uint8_t*>(ctx->d_in.p), io.in_px));
+        return launch();
+    };
+    return timed_roundtrip(ctx, io.bgr ? ctx->d_raw.p : ctx->d_in.p, in, io.bgr ? io.in_px * 3 : io.in_bytes, out,
+                           io.out_bytes, prof_ns, upload, kernels);
+}
+
+template <class Launch>
+int timed_roundtrip(mi355_ctx* ctx, const HostIO& io, const uint8_t* in, uint8_t* out, uint64_t prof_ns[6],
+                    Launch launch)
+{
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [] { return (int)MI355_OK; }, launch);
+}
+
 // H2D, kernel, D2H through the context's pooled buffers
 int run_host(mi355_ctx* ctx, int filter, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
              int k, float sigma, uint64_t prof_ns[6])
@@ -574,98 +630,16 @@ int run_host(mi355_ctx* ctx, int filter, const uint8_t* in, uint8_t* out, int w,
     int rc = check_filter(filter, w, h, nframes, k, sigma, &f);
     if (rc != MI355_OK)
         return rc;
-    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    if (bgr && f->in_bpp == 1)
-        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)w * h * nframes;
-    const size_t in_bytes = npx * (size_t)f->in_bpp, out_bytes = npx * (size_t)f->out_bpp;
-    rc = ensure(ctx, ctx->d_in, in_bytes);
-    if (rc == MI355_OK && bgr)
-        rc = ensure(ctx, ctx->d_raw, npx * 3);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_out, out_bytes);
+    HostIO io;
+    rc = stage_host(ctx, (size_t)w * h * nframes, f->in_bpp, frame_bytes(w, h, nframes, f->out_bpp), &io);
     const GaussCoef* coef = nullptr;
     if (rc == MI355_OK && f->table)
         rc = get_coef(ctx, k, sigma, &coef);  // built / uploaded outside the timed write/kernel/read window
     if (rc != MI355_OK)
         return rc;
-    auto launch = [&] {
-        if (bgr)  // the BGR2RGBA expansion counts as kernel time
-            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
-                                            static_cast<uint8_t*>(ctx->d_in.p), npx));
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
         return dispatch_dev(ctx, filter, ctx->d_in.p, ctx->d_out.p, w, h, nframes, k, sigma);
-    };
-    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? npx * 3 : in_bytes, out, out_bytes, prof_ns,
-                           launch);
-}
-
-// The value checks of the resize calls, before any HIP call: bytes per pixel, interpolation, both shapes; then AREA's
-// integer factors.  LINEAR at exactly half size is AREA 2 x 2, which always has them.
-int check_resize(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int interp)
-{
-    if ((bpp != 1 && bpp != 4) ||
-        (interp != MI355_INTERP_NEAREST && interp != MI355_INTERP_LINEAR && interp != MI355_INTERP_AREA) ||
-        !valid_sizes(src_w, src_h, nframes) || !valid_sizes(dst_w, dst_h, nframes))
-        return MI355_ERR_BAD_ARG;
-    if (src_w >= (1 << 29) || dst_w >= (1 << 29))  // a lane's byte offset inside a row is 32-bit
-        return MI355_ERR_BAD_ARG;
-    int nx = 0, ny = 0;
-    if (interp == MI355_INTERP_AREA && !resize_area_factors(src_w, src_h, dst_w, dst_h, &nx, &ny))
-        return MI355_ERR_UNSUPPORTED;
-    return MI355_OK;
-}
-
-int resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
-               int nframes, int interp)
-{
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
-    const int rc = check_resize(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
-    if (rc != MI355_OK)
-        return rc;
-    // each side counted with its own shape; the kernel reads source rows long after other waves stored theirs
-    const size_t in_bytes = (size_t)src_w * src_h * nframes * (size_t)bpp;
-    const size_t out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
-    if ((bpp == 4 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) ||
-        overlap(d_in, in_bytes, d_out, out_bytes))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_resize(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp, src_w,
-                               src_h, dst_w, dst_h, nframes, interp));
-    return MI355_OK;
-}
-
-// H2D, one launch, D2H through the pooled buffers, each side sized by its own shape
-int resize_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
-                int nframes, int interp, uint64_t prof_ns[6])
-{
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_resize(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
-    if (rc != MI355_OK)
-        return rc;
-    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    if (bgr && bpp == 1)
-        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_px = (size_t)src_w * src_h * nframes;
-    const size_t in_bytes = in_px * (size_t)bpp, out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
-    rc = ensure(ctx, ctx->d_in, in_bytes);
-    if (rc == MI355_OK && bgr)
-        rc = ensure(ctx, ctx->d_raw, in_px * 3);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_out, out_bytes);
-    if (rc != MI355_OK)
-        return rc;
-    auto launch = [&] {
-        if (bgr)  // the BGR2RGBA expansion counts as kernel time
-            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
-                                            static_cast<uint8_t*>(ctx->d_in.p), in_px));
-        return resize_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
-    };
-    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
-                           launch);
+    });
 }
 
 // cv::warpAffine's inverse map: m itself under MI355_WARP_INVERSE_MAP, else OpenCV's inversion, operation by operation
@@ -694,25 +668,46 @@ bool warp_flags_ok(int flags)
     return interp == MI355_INTERP_NEAREST || interp == MI355_INTERP_LINEAR;
 }
 
+bool all_finite(const double* m, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(m[i]))
+            return false;
+    return true;
+}
+
+// The argument errors every geometric call with two shapes shares
+bool bad_shapes(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int border_mode)
+{
+    return (bpp != 1 && bpp != 4) || (border_mode != MI355_BORDER_CONSTANT && border_mode != MI355_BORDER_REPLICATE) ||
+           src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0 || nframes <= 0;
+}
+
+// ... and what follows them (and the matrix, where there is one): the size limit, then the number of pixels
+int check_shape_limits(int src_w, int src_h, int dst_w, int dst_h, int nframes)
+{
+    if (src_w > MI355_MAX_WARP_SIZE || src_h > MI355_MAX_WARP_SIZE || dst_w > MI355_MAX_WARP_SIZE ||
+        dst_h > MI355_MAX_WARP_SIZE)
+        return MI355_ERR_UNSUPPORTED;
+    if (!valid_sizes(src_w, src_h, nframes) || !valid_sizes(dst_w, dst_h, nframes))
+        return MI355_ERR_BAD_ARG;
+    return MI355_OK;
+}
+
 // The value checks of the warp calls, before any HIP call: bytes per pixel, flags, border mode, both shapes, the matrix;
 // then the sizes and the inverse map the fixed-point arithmetic takes.  inv (may be null) gets the inverse map.
 int check_warp(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, const double* m, int flags,
                int border_mode, double* inv)
 {
-    if (!m || (bpp != 1 && bpp != 4) || !warp_flags_ok(flags) ||
-        (border_mode != MI355_BORDER_CONSTANT && border_mode != MI355_BORDER_REPLICATE) || src_w <= 0 || src_h <= 0 ||
-        dst_w <= 0 || dst_h <= 0 || nframes <= 0)
+    if (!m || !warp_flags_ok(flags) || bad_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode) ||
+        !all_finite(m, 6))
         return MI355_ERR_BAD_ARG;
-    for (int i = 0; i < 6; i++)
-        if (!std::isfinite(m[i]))
-            return MI355_ERR_BAD_ARG;
-    if (src_w > MI355_MAX_WARP_SIZE || src_h > MI355_MAX_WARP_SIZE || dst_w > MI355_MAX_WARP_SIZE ||
-        dst_h > MI355_MAX_WARP_SIZE)
-        return MI355_ERR_UNSUPPORTED;
+    const int rc = check_shape_limits(src_w, src_h, dst_w, dst_h, nframes);
+    if (rc != MI355_OK)
+        return rc;
     double i[6];
     warp_inverse(m, flags, i);
-    if (!valid_sizes(src_w, src_h, nframes) || !valid_sizes(dst_w, dst_h, nframes) ||
-        warp_work_items(i, dst_w, dst_h, nframes) > 0x7FFFFFF0ull)
+    if (warp_work_items(i, dst_w, dst_h, nframes) > 0x7FFFFFF0ull)
         return MI355_ERR_BAD_ARG;
     const double limit = 1048576.0;  // 2^20: below it no int sum of the coordinate arithmetic overflows
     const double rx = std::fabs(i[0]) * (double)(dst_w - 1) + std::fabs(i[1]) * (double)(dst_h - 1) + std::fabs(i[2]);
@@ -725,90 +720,16 @@ int check_warp(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes,
     return MI355_OK;
 }
 
-int warp_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
-             int nframes, const double* m, int flags, int border_mode, uint32_t border_value)
-{
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
-    double inv[6];
-    const int rc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv);
-    if (rc != MI355_OK)
-        return rc;
-    // each side counted with its own shape; the kernel reads source pixels long after other waves stored theirs
-    const size_t in_bytes = (size_t)src_w * src_h * nframes * (size_t)bpp;
-    const size_t out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
-    if ((bpp == 4 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) ||
-        overlap(d_in, in_bytes, d_out, out_bytes))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_warp_affine(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp,
-                                    src_w, src_h, dst_w, dst_h, nframes, inv, flags & ~MI355_WARP_INVERSE_MAP, border_mode,
-                                    border_value));
-    return MI355_OK;
-}
-
-// H2D, one launch, D2H through the pooled buffers, each side sized by its own shape
-int warp_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
-              int nframes, const double* m, int flags, int border_mode, uint32_t border_value, uint64_t prof_ns[6])
-{
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
-    if (rc != MI355_OK)
-        return rc;
-    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    if (bgr && bpp == 1)
-        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_px = (size_t)src_w * src_h * nframes;
-    const size_t in_bytes = in_px * (size_t)bpp, out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
-    rc = ensure(ctx, ctx->d_in, in_bytes);
-    if (rc == MI355_OK && bgr)
-        rc = ensure(ctx, ctx->d_raw, in_px * 3);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_out, out_bytes);
-    if (rc != MI355_OK)
-        return rc;
-    auto launch = [&] {
-        if (bgr)  // the BGR2RGBA expansion counts as kernel time
-            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
-                                            static_cast<uint8_t*>(ctx->d_in.p), in_px));
-        return warp_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode,
-                        border_value);
-    };
-    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
-                           launch);
-}
-
-// The argument errors every geometric call with two shapes shares
-bool bad_shapes(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int border_mode)
-{
-    return (bpp != 1 && bpp != 4) || (border_mode != MI355_BORDER_CONSTANT && border_mode != MI355_BORDER_REPLICATE) ||
-           src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0 || nframes <= 0;
-}
-
-// ... and, in the order of check_warp, the size limit and then the amount of work of remap.hip's launches
+// The shape checks of the remap and perspective calls: check_warp's, in its order, with the amount of work of remap.hip's
+// launches
 int check_two_shapes(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int border_mode)
 {
     if (bad_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode))
         return MI355_ERR_BAD_ARG;
-    if (src_w > MI355_MAX_WARP_SIZE || src_h > MI355_MAX_WARP_SIZE || dst_w > MI355_MAX_WARP_SIZE ||
-        dst_h > MI355_MAX_WARP_SIZE)
-        return MI355_ERR_UNSUPPORTED;
-    if (!valid_sizes(src_w, src_h, nframes) || !valid_sizes(dst_w, dst_h, nframes) ||
-        remap_work_items(dst_w, dst_h, nframes) > 0x7FFFFFF0ull)
+    const int rc = check_shape_limits(src_w, src_h, dst_w, dst_h, nframes);
+    if (rc == MI355_OK && remap_work_items(dst_w, dst_h, nframes) > 0x7FFFFFF0ull)
         return MI355_ERR_BAD_ARG;
-    return MI355_OK;
-}
-
-// The value checks of the remap calls, before any HIP call.
-int check_remap(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int map_kind, int interp,
-                int border_mode)
-{
-    if ((map_kind != MI355_MAP_FIXED && map_kind != MI355_MAP_FLOAT) ||
-        (interp != MI355_INTERP_NEAREST && interp != MI355_INTERP_LINEAR))
-        return MI355_ERR_BAD_ARG;
-    return check_two_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode);
+    return rc;
 }
 
 // bytes of the two maps of a remap call; map2 of FIXED + NEAREST is not read
@@ -817,81 +738,6 @@ void map_bytes(int dst_w, int dst_h, int map_kind, size_t* n1, size_t* n2)
     const size_t entries = (size_t)dst_w * dst_h;
     *n1 = entries * 4;
     *n2 = entries * (map_kind == MI355_MAP_FIXED ? 2 : 4);
-}
-
-int remap_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
-              int nframes, const void* d_map1, const void* d_map2, int map_kind, int interp, int border_mode,
-              uint32_t border_value)
-{
-    if (!ctx || !d_in || !d_out || !d_map1)
-        return MI355_ERR_BAD_ARG;
-    const int rc = check_remap(bpp, src_w, src_h, dst_w, dst_h, nframes, map_kind, interp, border_mode);
-    if (rc != MI355_OK)
-        return rc;
-    if (!d_map2 && !(map_kind == MI355_MAP_FIXED && interp == MI355_INTERP_NEAREST))
-        return MI355_ERR_BAD_ARG;
-    const size_t in_bytes = (size_t)src_w * src_h * nframes * (size_t)bpp;
-    const size_t out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
-    size_t n1 = 0, n2 = 0;
-    map_bytes(dst_w, dst_h, map_kind, &n1, &n2);
-    const uintptr_t align2 = map_kind == MI355_MAP_FIXED ? 1u : 3u;
-    if ((bpp == 4 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) ||
-        (reinterpret_cast<uintptr_t>(d_map1) & 3u) || (reinterpret_cast<uintptr_t>(d_map2) & align2) ||
-        overlap(d_in, in_bytes, d_out, out_bytes) || overlap(d_map1, n1, d_out, out_bytes) ||
-        (d_map2 && overlap(d_map2, n2, d_out, out_bytes)))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_remap(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp, src_w,
-                              src_h, dst_w, dst_h, nframes, d_map1, d_map2, map_kind, interp, border_mode, border_value));
-    return MI355_OK;
-}
-
-// H2D of the frames and of the maps, one launch, D2H through the pooled buffers, each side sized by its own shape
-int remap_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
-               int nframes, const void* map1, const void* map2, int map_kind, int interp, int border_mode,
-               uint32_t border_value, uint64_t prof_ns[6])
-{
-    if (!ctx || !in || !out || !map1)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_remap(bpp, src_w, src_h, dst_w, dst_h, nframes, map_kind, interp, border_mode);
-    if (rc != MI355_OK)
-        return rc;
-    if (!map2 && !(map_kind == MI355_MAP_FIXED && interp == MI355_INTERP_NEAREST))
-        return MI355_ERR_BAD_ARG;
-    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    if (bgr && bpp == 1)
-        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_px = (size_t)src_w * src_h * nframes;
-    const size_t in_bytes = in_px * (size_t)bpp, out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
-    size_t n1 = 0, n2 = 0;
-    map_bytes(dst_w, dst_h, map_kind, &n1, &n2);
-    rc = ensure(ctx, ctx->d_in, in_bytes);
-    if (rc == MI355_OK && bgr)
-        rc = ensure(ctx, ctx->d_raw, in_px * 3);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_out, out_bytes);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_map1, n1);
-    if (rc == MI355_OK && map2)
-        rc = ensure(ctx, ctx->d_map2, n2);
-    if (rc != MI355_OK)
-        return rc;
-    auto upload = [&] {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map1.p, map1, n1, hipMemcpyHostToDevice, ctx->stream));
-        if (map2)
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map2.p, map2, n2, hipMemcpyHostToDevice, ctx->stream));
-        return (int)MI355_OK;
-    };
-    auto launch = [&] {
-        if (bgr)  // the BGR2RGBA expansion counts as kernel time
-            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
-                                            static_cast<uint8_t*>(ctx->d_in.p), in_px));
-        return remap_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, ctx->d_map1.p,
-                         map2 ? ctx->d_map2.p : nullptr, map_kind, interp, border_mode, border_value);
-    };
-    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
-                           upload, launch);
 }
 
 // cv::warpPerspective's inverse map: m itself under MI355_WARP_INVERSE_MAP, else the adjugate times 1 / det, operation
@@ -922,79 +768,13 @@ int check_perspective(int bpp, int src_w, int src_h, int dst_w, int dst_h, int n
                       int border_mode, double* inv)
 {
     // a non-finite entry is an argument error even where the size limit would answer UNSUPPORTED (check_warp's order)
-    if (!m || !warp_flags_ok(flags) || bad_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode))
+    if (!m || !warp_flags_ok(flags) || bad_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode) ||
+        !all_finite(m, 9))
         return MI355_ERR_BAD_ARG;
-    for (int i = 0; i < 9; i++)
-        if (!std::isfinite(m[i]))
-            return MI355_ERR_BAD_ARG;
     const int rc = check_two_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode);
     if (rc == MI355_OK && inv)
         perspective_inverse(m, flags, inv);
     return rc;
-}
-
-int perspective_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
-                    int nframes, const double* m, int flags, int border_mode, uint32_t border_value)
-{
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
-    double inv[9];
-    const int rc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv);
-    if (rc != MI355_OK)
-        return rc;
-    const size_t in_bytes = (size_t)src_w * src_h * nframes * (size_t)bpp;
-    const size_t out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
-    if ((bpp == 4 && ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) ||
-        overlap(d_in, in_bytes, d_out, out_bytes))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_warp_perspective(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
-                                         bpp, src_w, src_h, dst_w, dst_h, nframes, inv, flags & ~MI355_WARP_INVERSE_MAP,
-                                         border_mode, border_value));
-    return MI355_OK;
-}
-
-// H2D, one launch, D2H through the pooled buffers, each side sized by its own shape
-int perspective_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w,
-                     int dst_h, int nframes, const double* m, int flags, int border_mode, uint32_t border_value,
-                     uint64_t prof_ns[6])
-{
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
-    if (rc != MI355_OK)
-        return rc;
-    const bool bgr = ctx->input_format == MI355_INPUT_BGR;
-    if (bgr && bpp == 1)
-        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_px = (size_t)src_w * src_h * nframes;
-    const size_t in_bytes = in_px * (size_t)bpp, out_bytes = (size_t)dst_w * dst_h * nframes * (size_t)bpp;
-    rc = ensure(ctx, ctx->d_in, in_bytes);
-    if (rc == MI355_OK && bgr)
-        rc = ensure(ctx, ctx->d_raw, in_px * 3);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_out, out_bytes);
-    if (rc != MI355_OK)
-        return rc;
-    auto launch = [&] {
-        if (bgr)  // the BGR2RGBA expansion counts as kernel time
-            HIP_TRY(ctx, launch_bgr_to_rgba(ctx->stream, static_cast<const uint8_t*>(ctx->d_raw.p),
-                                            static_cast<uint8_t*>(ctx->d_in.p), in_px));
-        return perspective_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags,
-                               border_mode, border_value);
-    };
-    return timed_roundtrip(ctx, bgr ? ctx->d_raw.p : ctx->d_in.p, in, bgr ? in_px * 3 : in_bytes, out, out_bytes, prof_ns,
-                           launch);
-}
-
-// The value checks of the adaptive-threshold calls, before any HIP call.
-int check_adaptive(int w, int h, int nframes, int max_value, int type, int block, double delta)
-{
-    if (!valid_sizes(w, h, nframes) || !odd_in(block, 3, MI355_MAX_BOX_K) || max_value < 0 || max_value > 255 ||
-        (type != MI355_ADAPTIVE_BINARY && type != MI355_ADAPTIVE_BINARY_INV) || !std::isfinite(delta))
-        return MI355_ERR_BAD_ARG;
-    return MI355_OK;
 }
 
 // cv::adaptiveThreshold's integer delta: ceil for BINARY, floor for BINARY_INV; beyond +-256 the output is constant
@@ -1002,47 +782,6 @@ int adaptive_idelta(int type, double delta)
 {
     const double d = type == MI355_ADAPTIVE_BINARY ? std::ceil(delta) : std::floor(delta);
     return d < -256.0 ? -256 : (d > 256.0 ? 256 : (int)d);
-}
-
-int adaptive_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes, int max_value, int type,
-                 int block, double delta)
-{
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
-    const int rc = check_adaptive(w, h, nframes, max_value, type, block, delta);
-    if (rc != MI355_OK)
-        return rc;
-    const size_t nbytes = (size_t)w * h * nframes;
-    if (overlap(d_in, nbytes, d_out, nbytes))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_adaptive_threshold(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
-                                           w, h, nframes, block, max_value, type == MI355_ADAPTIVE_BINARY_INV,
-                                           adaptive_idelta(type, delta)));
-    return MI355_OK;
-}
-
-// H2D, one launch, D2H through the pooled buffers
-int adaptive_host(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes, int max_value, int type,
-                  int block, double delta, uint64_t prof_ns[6])
-{
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_adaptive(w, h, nframes, max_value, type, block, delta);
-    if (rc != MI355_OK)
-        return rc;
-    if (ctx->input_format == MI355_INPUT_BGR)
-        return MI355_ERR_UNSUPPORTED;  // a gray plane has no BGR form; nothing is converted silently
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t nbytes = (size_t)w * h * nframes;
-    rc = ensure(ctx, ctx->d_in, nbytes);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_out, nbytes);
-    if (rc != MI355_OK)
-        return rc;
-    return timed_roundtrip(ctx, ctx->d_in.p, in, nbytes, out, nbytes, prof_ns, [&] {
-        return adaptive_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, max_value, type, block, delta);
-    });
 }
 
 int create_common(int device, hipStream_t stream, bool own, mi355_ctx** out)
@@ -1437,21 +1176,56 @@ MI355_API int mi355_filter_dev(mi355_ctx* ctx, int filter, const void* d_in, voi
     return dispatch_dev(ctx, filter, d_in, d_out, w, h, nframes, k, sigma);
 }
 
+// The value checks of the resize calls, before any HIP call: bytes per pixel, interpolation, both shapes; then AREA's
+// integer factors.  LINEAR at exactly half size is AREA 2 x 2, which always has them.
 MI355_API int mi355_resize_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int interp)
 {
-    return check_resize(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    if ((bpp != 1 && bpp != 4) ||
+        (interp != MI355_INTERP_NEAREST && interp != MI355_INTERP_LINEAR && interp != MI355_INTERP_AREA) ||
+        !valid_sizes(src_w, src_h, nframes) || !valid_sizes(dst_w, dst_h, nframes))
+        return MI355_ERR_BAD_ARG;
+    if (src_w >= (1 << 29) || dst_w >= (1 << 29))  // a lane's byte offset inside a row is 32-bit
+        return MI355_ERR_BAD_ARG;
+    int nx = 0, ny = 0;
+    if (interp == MI355_INTERP_AREA && !resize_area_factors(src_w, src_h, dst_w, dst_h, &nx, &ny))
+        return MI355_ERR_UNSUPPORTED;
+    return MI355_OK;
 }
 
 MI355_API int mi355_resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w,
                                int dst_h, int nframes, int interp)
 {
-    return resize_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    const int rc = mi355_resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    if (rc != MI355_OK)
+        return rc;
+    if (bad_dev_io(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp, d_out, frame_bytes(dst_w, dst_h, nframes, bpp),
+                   bpp))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_resize(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp, src_w,
+                               src_h, dst_w, dst_h, nframes, interp));
+    return MI355_OK;
 }
 
+// The host-buffer form of this and of every later call: H2D, one launch, D2H through the pooled buffers, each side
+// sized by its own shape
 MI355_API int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
                                    int dst_w, int dst_h, int nframes, int interp, uint64_t prof_ns[6])
 {
-    return resize_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, interp, prof_ns);
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = mi355_resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    if (rc != MI355_OK)
+        return rc;
+    HostIO io;
+    rc = stage_host(ctx, (size_t)src_w * src_h * nframes, bpp, frame_bytes(dst_w, dst_h, nframes, bpp), &io);
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+        return mi355_resize_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    });
 }
 
 MI355_API int mi355_rotation_matrix(double cx, double cy, double angle_deg, double scale, double m[6])
@@ -1472,11 +1246,8 @@ MI355_API int mi355_rotation_matrix(double cx, double cy, double angle_deg, doub
 
 MI355_API int mi355_warp_affine_matrix(const double m[6], int flags, double inv[6])
 {
-    if (!m || !inv || !warp_flags_ok(flags))
+    if (!m || !inv || !warp_flags_ok(flags) || !all_finite(m, 6))
         return MI355_ERR_BAD_ARG;
-    for (int i = 0; i < 6; i++)
-        if (!std::isfinite(m[i]))
-            return MI355_ERR_BAD_ARG;
     warp_inverse(m, flags, inv);
     return MI355_OK;
 }
@@ -1491,45 +1262,112 @@ MI355_API int mi355_warp_affine_dev(mi355_ctx* ctx, const void* d_in, void* d_ou
                                     int dst_w, int dst_h, int nframes, const double m[6], int flags, int border_mode,
                                     uint32_t border_value)
 {
-    return warp_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, border_value);
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    double inv[6];
+    const int rc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv);
+    if (rc != MI355_OK)
+        return rc;
+    if (bad_dev_io(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp, d_out, frame_bytes(dst_w, dst_h, nframes, bpp),
+                   bpp))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_warp_affine(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp,
+                                    src_w, src_h, dst_w, dst_h, nframes, inv, flags & ~MI355_WARP_INVERSE_MAP, border_mode,
+                                    border_value));
+    return MI355_OK;
 }
 
 MI355_API int mi355_warp_affine_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
                                         int dst_w, int dst_h, int nframes, const double m[6], int flags, int border_mode,
                                         uint32_t border_value, uint64_t prof_ns[6])
 {
-    return warp_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, border_value, prof_ns);
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    HostIO io;
+    rc = stage_host(ctx, (size_t)src_w * src_h * nframes, bpp, frame_bytes(dst_w, dst_h, nframes, bpp), &io);
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+        return mi355_warp_affine_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags,
+                                     border_mode, border_value);
+    });
 }
 
 MI355_API int mi355_remap_check(int bpp, int src_w, int src_h, int dst_w, int dst_h, int nframes, int map_kind,
                                 int interp, int border_mode)
 {
-    return check_remap(bpp, src_w, src_h, dst_w, dst_h, nframes, map_kind, interp, border_mode);
+    if ((map_kind != MI355_MAP_FIXED && map_kind != MI355_MAP_FLOAT) ||
+        (interp != MI355_INTERP_NEAREST && interp != MI355_INTERP_LINEAR))
+        return MI355_ERR_BAD_ARG;
+    return check_two_shapes(bpp, src_w, src_h, dst_w, dst_h, nframes, border_mode);
 }
 
 MI355_API int mi355_remap_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w,
                               int dst_h, int nframes, const void* d_map1, const void* d_map2, int map_kind, int interp,
                               int border_mode, uint32_t border_value)
 {
-    return remap_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes, d_map1, d_map2, map_kind, interp,
-                     border_mode, border_value);
+    if (!ctx || !d_in || !d_out || !d_map1)
+        return MI355_ERR_BAD_ARG;
+    const int rc = mi355_remap_check(bpp, src_w, src_h, dst_w, dst_h, nframes, map_kind, interp, border_mode);
+    if (rc != MI355_OK)
+        return rc;
+    if (!d_map2 && !(map_kind == MI355_MAP_FIXED && interp == MI355_INTERP_NEAREST))
+        return MI355_ERR_BAD_ARG;
+    const size_t out_bytes = frame_bytes(dst_w, dst_h, nframes, bpp);
+    size_t n1 = 0, n2 = 0;
+    map_bytes(dst_w, dst_h, map_kind, &n1, &n2);
+    const uintptr_t align2 = map_kind == MI355_MAP_FIXED ? 1u : 3u;
+    if (bad_dev_io(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp, d_out, out_bytes, bpp) ||
+        (reinterpret_cast<uintptr_t>(d_map1) & 3u) || (reinterpret_cast<uintptr_t>(d_map2) & align2) ||
+        overlap(d_map1, n1, d_out, out_bytes) || (d_map2 && overlap(d_map2, n2, d_out, out_bytes)))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_remap(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp, src_w,
+                              src_h, dst_w, dst_h, nframes, d_map1, d_map2, map_kind, interp, border_mode, border_value));
+    return MI355_OK;
 }
 
 MI355_API int mi355_remap_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
                                   int dst_w, int dst_h, int nframes, const void* map1, const void* map2, int map_kind,
                                   int interp, int border_mode, uint32_t border_value, uint64_t prof_ns[6])
 {
-    return remap_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, map1, map2, map_kind, interp, border_mode,
-                      border_value, prof_ns);
+    if (!ctx || !in || !out || !map1)
+        return MI355_ERR_BAD_ARG;
+    int rc = mi355_remap_check(bpp, src_w, src_h, dst_w, dst_h, nframes, map_kind, interp, border_mode);
+    if (rc != MI355_OK)
+        return rc;
+    if (!map2 && !(map_kind == MI355_MAP_FIXED && interp == MI355_INTERP_NEAREST))
+        return MI355_ERR_BAD_ARG;
+    HostIO io;
+    rc = stage_host(ctx, (size_t)src_w * src_h * nframes, bpp, frame_bytes(dst_w, dst_h, nframes, bpp), &io);
+    size_t n1 = 0, n2 = 0;
+    map_bytes(dst_w, dst_h, map_kind, &n1, &n2);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_map1, n1);
+    if (rc == MI355_OK && map2)
+        rc = ensure(ctx, ctx->d_map2, n2);
+    if (rc != MI355_OK)
+        return rc;
+    auto upload = [&] {  // the maps travel with the frames: H2D time
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map1.p, map1, n1, hipMemcpyHostToDevice, ctx->stream));
+        if (map2)
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map2.p, map2, n2, hipMemcpyHostToDevice, ctx->stream));
+        return (int)MI355_OK;
+    };
+    return timed_roundtrip(ctx, io, in, out, prof_ns, upload, [&] {
+        return mi355_remap_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, ctx->d_map1.p,
+                               map2 ? ctx->d_map2.p : nullptr, map_kind, interp, border_mode, border_value);
+    });
 }
 
 MI355_API int mi355_perspective_matrix(const double m[9], int flags, double inv[9])
 {
-    if (!m || !inv || !warp_flags_ok(flags))
+    if (!m || !inv || !warp_flags_ok(flags) || !all_finite(m, 9))
         return MI355_ERR_BAD_ARG;
-    for (int i = 0; i < 9; i++)
-        if (!std::isfinite(m[i]))
-            return MI355_ERR_BAD_ARG;
     perspective_inverse(m, flags, inv);
     return MI355_OK;
 }
@@ -1544,35 +1382,84 @@ MI355_API int mi355_warp_perspective_dev(mi355_ctx* ctx, const void* d_in, void*
                                          int dst_w, int dst_h, int nframes, const double m[9], int flags,
                                          int border_mode, uint32_t border_value)
 {
-    return perspective_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode,
-                           border_value);
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    double inv[9];
+    const int rc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv);
+    if (rc != MI355_OK)
+        return rc;
+    if (bad_dev_io(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp, d_out, frame_bytes(dst_w, dst_h, nframes, bpp),
+                   bpp))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_warp_perspective(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                                         bpp, src_w, src_h, dst_w, dst_h, nframes, inv, flags & ~MI355_WARP_INVERSE_MAP,
+                                         border_mode, border_value));
+    return MI355_OK;
 }
 
 MI355_API int mi355_warp_perspective_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w,
                                              int src_h, int dst_w, int dst_h, int nframes, const double m[9], int flags,
                                              int border_mode, uint32_t border_value, uint64_t prof_ns[6])
 {
-    return perspective_host(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, border_value,
-                            prof_ns);
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    HostIO io;
+    rc = stage_host(ctx, (size_t)src_w * src_h * nframes, bpp, frame_bytes(dst_w, dst_h, nframes, bpp), &io);
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+        return mi355_warp_perspective_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, m,
+                                          flags, border_mode, border_value);
+    });
 }
 
 MI355_API int mi355_adaptive_threshold_check(int w, int h, int nframes, int max_value, int type, int block,
                                              double delta)
 {
-    return check_adaptive(w, h, nframes, max_value, type, block, delta);
+    if (!valid_sizes(w, h, nframes) || !odd_in(block, 3, MI355_MAX_BOX_K) || max_value < 0 || max_value > 255 ||
+        (type != MI355_ADAPTIVE_BINARY && type != MI355_ADAPTIVE_BINARY_INV) || !std::isfinite(delta))
+        return MI355_ERR_BAD_ARG;
+    return MI355_OK;
 }
 
 MI355_API int mi355_adaptive_threshold_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h,
                                                  int nframes, int max_value, int type, int block, double delta)
 {
-    return adaptive_dev(ctx, d_in, d_out, w, h, nframes, max_value, type, block, delta);
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    const int rc = mi355_adaptive_threshold_check(w, h, nframes, max_value, type, block, delta);
+    if (rc != MI355_OK)
+        return rc;
+    if (bad_dev_io(d_in, frame_bytes(w, h, nframes, 1), 1, d_out, frame_bytes(w, h, nframes, 1), 1))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_adaptive_threshold(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                                           w, h, nframes, block, max_value, type == MI355_ADAPTIVE_BINARY_INV,
+                                           adaptive_idelta(type, delta)));
+    return MI355_OK;
 }
 
 MI355_API int mi355_adaptive_threshold_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h,
                                                      int nframes, int max_value, int type, int block, double delta,
                                                      uint64_t prof_ns[6])
 {
-    return adaptive_host(ctx, in, out, w, h, nframes, max_value, type, block, delta, prof_ns);
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = mi355_adaptive_threshold_check(w, h, nframes, max_value, type, block, delta);
+    if (rc != MI355_OK)
+        return rc;
+    HostIO io;
+    rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+        return mi355_adaptive_threshold_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, max_value, type, block,
+                                                  delta);
+    });
 }
 
 // the argument checks of the two statistics calls: mi355_filter_dev's, with `nout` bytes of 4-byte aligned output

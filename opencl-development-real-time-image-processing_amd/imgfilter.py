@@ -414,25 +414,31 @@ class Context:
         _check("mi355_ctx_set_gauss_weights", rc, self._h)
 
     # -- host-buffer calls (numpy) ------------------------------------------------------------
+    def _frames(self, fn, a, bpp):
+        """What the host-buffer call `fn` sends for `a`: contiguous uint8 (n, h, w, c) frames with the input format's
+        channel count (bpp 4) or (n, h, w) planes (bpp 1), and whether `a` was one frame, so that the result drops its
+        first axis."""
+        a = np.ascontiguousarray(a, np.uint8)
+        one_ndim = 3 if bpp == 4 else 2
+        if a.ndim not in (one_ndim, one_ndim + 1):
+            raise Mi355Error(fn, -1, "expected (h, w, 4) or (n, h, w, 4) uint8" if bpp == 4 else
+                             "expected (h, w) or (n, h, w) uint8")
+        frames = a[None] if a.ndim == one_ndim else a
+        in_ch = getattr(self, "_in_ch", 4)
+        if bpp == 4 and frames.shape[3] != in_ch:
+            raise Mi355Error(fn, -1, "expected %d channels per pixel" % in_ch)
+        return frames, a.ndim == one_ndim
+
     def _host(self, filt, rgba, k=0, sigma=0.0, profile=False):
-        rgba = np.ascontiguousarray(rgba, np.uint8)
-        if rgba.ndim == 3:
-            frames = rgba[None]
-        elif rgba.ndim == 4:
-            frames = rgba
-        else:
-            raise Mi355Error("filter", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
-        n, h, w, c = frames.shape
-        if c != getattr(self, "_in_ch", 4):
-            raise Mi355Error("filter", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
+        frames, one = self._frames("filter", rgba, 4)
+        n, h, w = frames.shape[:3]
         bpp = _out_bpp(filt)
         out = np.empty((n, h, w, 4) if bpp == 4 else (n, h, w), np.uint8)
         prof = (ctypes.c_uint64 * 6)()
         rc = self._lib.mi355_filter_batched(self._h, filt, frames.ctypes.data_as(_u8p),
                                             out.ctypes.data_as(_u8p), w, h, n, int(k), float(sigma), prof)
         _check("mi355_filter_batched", rc, self._h)
-        if rgba.ndim == 3:
-            out = out[0]
+        out = out[0] if one else out
         return (out, list(prof)) if profile else out
 
     def gray(self, rgba, profile=False):
@@ -455,16 +461,13 @@ class Context:
 
     # -- single-channel frames: (h, w) or (n, h, w) uint8 in, the same shape out --------------------
     def _host_gray8(self, filt, y, k=0, sigma=0.0):
-        y = np.ascontiguousarray(y, np.uint8)
-        if y.ndim not in (2, 3):
-            raise Mi355Error("filter", -1, "expected (h, w) or (n, h, w) uint8")
-        frames = y[None] if y.ndim == 2 else y
+        frames, one = self._frames("filter", y, 1)
         n, h, w = frames.shape
         out = np.empty((n, h, w), np.uint8)
         rc = self._lib.mi355_filter_batched(self._h, filt, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p),
                                             w, h, n, int(k), float(sigma), None)
         _check("mi355_filter_batched", rc, self._h)
-        return out[0] if y.ndim == 2 else out
+        return out[0] if one else out
 
     def gauss_gray8(self, y, k, sigma):
         """GaussianBlur.cpp:234-261 on one channel (MI355_FILTER_GAUSS_GRAY8)."""
@@ -541,10 +544,7 @@ class Context:
     def adaptive_threshold_gray8(self, y, max_value, type, block, delta, profile=False):
         """cv::adaptiveThreshold(y, max_value, ADAPTIVE_THRESH_MEAN_C, type, block, delta) of (h, w) / (n, h, w)
         single-channel frames (mi355_adaptive_threshold_gray8_batched); type is ADAPTIVE_BINARY or ADAPTIVE_BINARY_INV."""
-        y = np.ascontiguousarray(y, np.uint8)
-        if y.ndim not in (2, 3):
-            raise Mi355Error("adaptive_threshold_gray8", -1, "expected (h, w) or (n, h, w) uint8")
-        frames = y[None] if y.ndim == 2 else y
+        frames, one = self._frames("adaptive_threshold_gray8", y, 1)
         n, h, w = frames.shape
         out = np.empty((n, h, w), np.uint8)
         prof = (ctypes.c_uint64 * 6)()
@@ -552,93 +552,57 @@ class Context:
             self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, int(max_value), int(type),
             int(block), float(delta), prof if profile else None)
         _check("mi355_adaptive_threshold_gray8_batched", rc, self._h)
-        out = out[0] if y.ndim == 2 else out
+        out = out[0] if one else out
         return (out, list(prof)) if profile else out
 
-    # -- changing the frame size (mi355_resize_batched) ---------------------------------------------
-    def _resize_host(self, frames, bpp, dst_w, dst_h, interp, profile):
+    # -- calls that change the frame size: (frames, out, bpp, w, h, dst_w, dst_h, n, <the call's own>, prof_ns) -----
+    def _geom_host(self, fn_name, frames, bpp, dst_w, dst_h, profile, *tail):
         n, h, w = frames.shape[:3]
         out = np.empty((n, int(dst_h), int(dst_w), 4) if bpp == 4 else (n, int(dst_h), int(dst_w)), np.uint8)
         prof = (ctypes.c_uint64 * 6)()
-        rc = self._lib.mi355_resize_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), bpp, w, h,
-                                            int(dst_w), int(dst_h), n, int(interp), prof if profile else None)
-        _check("mi355_resize_batched", rc, self._h)
+        rc = getattr(self._lib, fn_name)(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), bpp, w, h,
+                                         int(dst_w), int(dst_h), n, *tail, prof if profile else None)
+        _check(fn_name, rc, self._h)
         return out, list(prof)
 
+    # -- changing the frame size (mi355_resize_batched) ---------------------------------------------
     def resize(self, rgba, dst_w, dst_h, interp=INTERP_LINEAR, profile=False):
         """cv::resize of (h, w, 4) / (n, h, w, 4) frames to (dst_h, dst_w), every channel on its own; interp is
         INTERP_NEAREST, INTERP_LINEAR or INTERP_AREA (integer factors only).  Under INPUT_BGR the frames have 3 channels
         and the result is RGBA."""
-        rgba = np.ascontiguousarray(rgba, np.uint8)
-        if rgba.ndim not in (3, 4):
-            raise Mi355Error("resize", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
-        frames = rgba[None] if rgba.ndim == 3 else rgba
-        if frames.shape[3] != getattr(self, "_in_ch", 4):
-            raise Mi355Error("resize", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
-        out, prof = self._resize_host(frames, 4, dst_w, dst_h, interp, profile)
-        if rgba.ndim == 3:
-            out = out[0]
+        frames, one = self._frames("resize", rgba, 4)
+        out, prof = self._geom_host("mi355_resize_batched", frames, 4, dst_w, dst_h, profile, int(interp))
+        out = out[0] if one else out
         return (out, prof) if profile else out
 
     def resize_gray8(self, y, dst_w, dst_h, interp=INTERP_LINEAR):
         """cv::resize of (h, w) / (n, h, w) single-channel frames to (dst_h, dst_w)."""
-        y = np.ascontiguousarray(y, np.uint8)
-        if y.ndim not in (2, 3):
-            raise Mi355Error("resize_gray8", -1, "expected (h, w) or (n, h, w) uint8")
-        out, _ = self._resize_host(y[None] if y.ndim == 2 else y, 1, dst_w, dst_h, interp, False)
-        return out[0] if y.ndim == 2 else out
+        frames, one = self._frames("resize_gray8", y, 1)
+        out, _ = self._geom_host("mi355_resize_batched", frames, 1, dst_w, dst_h, False, int(interp))
+        return out[0] if one else out
 
     # -- rotating, shifting and deskewing frames (mi355_warp_affine_batched) ---------------------------
-    def _warp_host(self, frames, bpp, m, dst_w, dst_h, flags, border_mode, border_value, profile):
-        n, h, w = frames.shape[:3]
-        out = np.empty((n, int(dst_h), int(dst_w), 4) if bpp == 4 else (n, int(dst_h), int(dst_w)), np.uint8)
-        prof = (ctypes.c_uint64 * 6)()
-        rc = self._lib.mi355_warp_affine_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), bpp, w,
-                                                 h, int(dst_w), int(dst_h), n, _matrix(m), int(flags), int(border_mode),
-                                                 int(border_value) & 0xFFFFFFFF, prof if profile else None)
-        _check("mi355_warp_affine_batched", rc, self._h)
-        return out, list(prof)
-
     def warp_affine(self, rgba, m, dst_w, dst_h, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT, border_value=0,
                     profile=False):
         """cv::warpAffine of (h, w, 4) / (n, h, w, 4) frames through the 2 x 3 matrix m to (dst_h, dst_w), every channel
         on its own; flags is INTERP_NEAREST or INTERP_LINEAR, optionally | WARP_INVERSE_MAP; border_value is
         R | G << 8 | B << 16 | A << 24, used under BORDER_CONSTANT.  Under INPUT_BGR the frames have 3 channels and the
         result is RGBA."""
-        rgba = np.ascontiguousarray(rgba, np.uint8)
-        if rgba.ndim not in (3, 4):
-            raise Mi355Error("warp_affine", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
-        frames = rgba[None] if rgba.ndim == 3 else rgba
-        if frames.shape[3] != getattr(self, "_in_ch", 4):
-            raise Mi355Error("warp_affine", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
-        out, prof = self._warp_host(frames, 4, m, dst_w, dst_h, flags, border_mode, border_value, profile)
-        if rgba.ndim == 3:
-            out = out[0]
+        frames, one = self._frames("warp_affine", rgba, 4)
+        out, prof = self._geom_host("mi355_warp_affine_batched", frames, 4, dst_w, dst_h, profile, _matrix(m),
+                                    int(flags), int(border_mode), int(border_value) & 0xFFFFFFFF)
+        out = out[0] if one else out
         return (out, prof) if profile else out
 
     def warp_affine_gray8(self, y, m, dst_w, dst_h, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT, border_value=0):
         """cv::warpAffine of (h, w) / (n, h, w) single-channel frames to (dst_h, dst_w); border_value's low byte is the
         border under BORDER_CONSTANT."""
-        y = np.ascontiguousarray(y, np.uint8)
-        if y.ndim not in (2, 3):
-            raise Mi355Error("warp_affine_gray8", -1, "expected (h, w) or (n, h, w) uint8")
-        out, _ = self._warp_host(y[None] if y.ndim == 2 else y, 1, m, dst_w, dst_h, flags, border_mode, border_value,
-                                 False)
-        return out[0] if y.ndim == 2 else out
+        frames, one = self._frames("warp_affine_gray8", y, 1)
+        out, _ = self._geom_host("mi355_warp_affine_batched", frames, 1, dst_w, dst_h, False, _matrix(m), int(flags),
+                                 int(border_mode), int(border_value) & 0xFFFFFFFF)
+        return out[0] if one else out
 
     # -- undistorting and rectifying frames (mi355_remap_batched, mi355_warp_perspective_batched) ----
-    def _remap_host(self, frames, bpp, map1, map2, map_kind, dst_w, dst_h, interp, border_mode, border_value, profile):
-        n, h, w = frames.shape[:3]
-        m1, m2 = _host_maps("remap", map1, map2, map_kind, dst_w, dst_h)
-        out = np.empty((n, int(dst_h), int(dst_w), 4) if bpp == 4 else (n, int(dst_h), int(dst_w)), np.uint8)
-        prof = (ctypes.c_uint64 * 6)()
-        rc = self._lib.mi355_remap_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), bpp, w, h,
-                                           int(dst_w), int(dst_h), n, _vp(m1.ctypes.data),
-                                           None if m2 is None else _vp(m2.ctypes.data), int(map_kind), int(interp),
-                                           int(border_mode), int(border_value) & 0xFFFFFFFF, prof if profile else None)
-        _check("mi355_remap_batched", rc, self._h)
-        return out, list(prof)
-
     def remap(self, rgba, map1, map2, dst_w, dst_h, map_kind=MAP_FIXED, interp=INTERP_LINEAR,
               border_mode=BORDER_CONSTANT, border_value=0, profile=False):
         """cv::remap of (h, w, 4) / (n, h, w, 4) frames through one map to (dst_h, dst_w), every channel on its own.
@@ -646,71 +610,46 @@ class Context:
         INTERP_NEAREST); MAP_FLOAT: map1 and map2 (dst_h, dst_w) float32 x and y.  border_value is
         R | G << 8 | B << 16 | A << 24, used under BORDER_CONSTANT.  Under INPUT_BGR the frames have 3 channels and the
         result is RGBA."""
-        rgba = np.ascontiguousarray(rgba, np.uint8)
-        if rgba.ndim not in (3, 4):
-            raise Mi355Error("remap", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
-        frames = rgba[None] if rgba.ndim == 3 else rgba
-        if frames.shape[3] != getattr(self, "_in_ch", 4):
-            raise Mi355Error("remap", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
-        out, prof = self._remap_host(frames, 4, map1, map2, map_kind, dst_w, dst_h, interp, border_mode, border_value,
-                                     profile)
-        if rgba.ndim == 3:
-            out = out[0]
+        frames, one = self._frames("remap", rgba, 4)
+        m1, m2 = _host_maps("remap", map1, map2, map_kind, dst_w, dst_h)
+        out, prof = self._geom_host("mi355_remap_batched", frames, 4, dst_w, dst_h, profile, _vp(m1.ctypes.data),
+                                    None if m2 is None else _vp(m2.ctypes.data), int(map_kind), int(interp),
+                                    int(border_mode), int(border_value) & 0xFFFFFFFF)
+        out = out[0] if one else out
         return (out, prof) if profile else out
 
     def remap_gray8(self, y, map1, map2, dst_w, dst_h, map_kind=MAP_FIXED, interp=INTERP_LINEAR,
                     border_mode=BORDER_CONSTANT, border_value=0):
         """cv::remap of (h, w) / (n, h, w) single-channel frames to (dst_h, dst_w); border_value's low byte is the
         border under BORDER_CONSTANT."""
-        y = np.ascontiguousarray(y, np.uint8)
-        if y.ndim not in (2, 3):
-            raise Mi355Error("remap_gray8", -1, "expected (h, w) or (n, h, w) uint8")
-        out, _ = self._remap_host(y[None] if y.ndim == 2 else y, 1, map1, map2, map_kind, dst_w, dst_h, interp,
-                                  border_mode, border_value, False)
-        return out[0] if y.ndim == 2 else out
-
-    def _perspective_host(self, frames, bpp, m, dst_w, dst_h, flags, border_mode, border_value, profile):
-        n, h, w = frames.shape[:3]
-        out = np.empty((n, int(dst_h), int(dst_w), 4) if bpp == 4 else (n, int(dst_h), int(dst_w)), np.uint8)
-        prof = (ctypes.c_uint64 * 6)()
-        rc = self._lib.mi355_warp_perspective_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p),
-                                                      bpp, w, h, int(dst_w), int(dst_h), n, _matrix9(m), int(flags),
-                                                      int(border_mode), int(border_value) & 0xFFFFFFFF,
-                                                      prof if profile else None)
-        _check("mi355_warp_perspective_batched", rc, self._h)
-        return out, list(prof)
+        frames, one = self._frames("remap_gray8", y, 1)
+        m1, m2 = _host_maps("remap", map1, map2, map_kind, dst_w, dst_h)
+        out, _ = self._geom_host("mi355_remap_batched", frames, 1, dst_w, dst_h, False, _vp(m1.ctypes.data),
+                                 None if m2 is None else _vp(m2.ctypes.data), int(map_kind), int(interp),
+                                 int(border_mode), int(border_value) & 0xFFFFFFFF)
+        return out[0] if one else out
 
     def warp_perspective(self, rgba, m, dst_w, dst_h, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT, border_value=0,
                          profile=False):
         """cv::warpPerspective of (h, w, 4) / (n, h, w, 4) frames through the 3 x 3 matrix m to (dst_h, dst_w), every
         channel on its own; flags, border_value and INPUT_BGR as in warp_affine."""
-        rgba = np.ascontiguousarray(rgba, np.uint8)
-        if rgba.ndim not in (3, 4):
-            raise Mi355Error("warp_perspective", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
-        frames = rgba[None] if rgba.ndim == 3 else rgba
-        if frames.shape[3] != getattr(self, "_in_ch", 4):
-            raise Mi355Error("warp_perspective", -1, "expected %d channels per pixel" % getattr(self, "_in_ch", 4))
-        out, prof = self._perspective_host(frames, 4, m, dst_w, dst_h, flags, border_mode, border_value, profile)
-        if rgba.ndim == 3:
-            out = out[0]
+        frames, one = self._frames("warp_perspective", rgba, 4)
+        out, prof = self._geom_host("mi355_warp_perspective_batched", frames, 4, dst_w, dst_h, profile, _matrix9(m),
+                                    int(flags), int(border_mode), int(border_value) & 0xFFFFFFFF)
+        out = out[0] if one else out
         return (out, prof) if profile else out
 
     def warp_perspective_gray8(self, y, m, dst_w, dst_h, flags=INTERP_LINEAR, border_mode=BORDER_CONSTANT,
                                border_value=0):
         """cv::warpPerspective of (h, w) / (n, h, w) single-channel frames to (dst_h, dst_w); border_value's low byte is
         the border under BORDER_CONSTANT."""
-        y = np.ascontiguousarray(y, np.uint8)
-        if y.ndim not in (2, 3):
-            raise Mi355Error("warp_perspective_gray8", -1, "expected (h, w) or (n, h, w) uint8")
-        out, _ = self._perspective_host(y[None] if y.ndim == 2 else y, 1, m, dst_w, dst_h, flags, border_mode,
-                                        border_value, False)
-        return out[0] if y.ndim == 2 else out
+        frames, one = self._frames("warp_perspective_gray8", y, 1)
+        out, _ = self._geom_host("mi355_warp_perspective_batched", frames, 1, dst_w, dst_h, False, _matrix9(m),
+                                 int(flags), int(border_mode), int(border_value) & 0xFFFFFFFF)
+        return out[0] if one else out
 
     def _stats_gray8(self, fn, y, per_frame, dtype):
-        y = np.ascontiguousarray(y, np.uint8)
-        if y.ndim not in (2, 3):
-            raise Mi355Error(fn, -1, "expected (h, w) or (n, h, w) uint8")
-        frames = y[None] if y.ndim == 2 else y
+        frames, one = self._frames(fn, y, 1)
         n, h, w = frames.shape
         out = np.empty((n, per_frame), dtype)
         d_in = self.alloc(frames.nbytes)
@@ -727,7 +666,7 @@ class Context:
                 self.free(d_out)
         finally:
             self.free(d_in)
-        return out[0] if y.ndim == 2 else out
+        return out[0] if one else out
 
     def hist_gray8(self, y):
         """The 256 bin counts of each single-channel frame (cv::calcHist), through mi355_hist_gray8_dev: (n, 256)
