@@ -23,14 +23,12 @@
 // Bands are kBoxBandPerK * k rows (at least kBoxBandFloor) so that the k start-up rows stay a fixed share, halved while
 // the launch has fewer than kBoxMinWork waves.  No cross-workgroup synchronisation, no atomics, no allocation.
 #include "box_common.hpp"
-#include "kernels.hpp"
-#include "slide_common.hpp"
+#include "wave_common.hpp"
 
 namespace mi355 {
 
 namespace {
 
-constexpr int kBoxWaves = 4;              // waves per block
 constexpr int kBoxBandPerK = 4;           // rows of the tallest band per row of the window
 constexpr int kBoxBandFloor = 32;         // ... and its least height
 constexpr int kBoxBandMin = 4;            // halving stops here
@@ -116,24 +114,21 @@ __device__ __forceinline__ uint32_t wave_scan_add(uint32_t v)
 }
 
 template <bool GRAY8, int EPI>
-__global__ __launch_bounds__(kBoxWaves* kWave) void box_kernel(const BoxArgs a)
+__global__ __launch_bounds__(kItemWaves* kWave) void box_kernel(const BoxArgs a)
 {
     static_assert(GRAY8 || EPI == kMean, "the threshold is gray8 only");
     constexpr int PX = GRAY8 ? 16 : 4, LOG_PX = GRAY8 ? 4 : 2;  // columns per lane
     constexpr int CH = 16 / PX;                                  // channels = bytes per pixel
     using PVec = typename std::conditional<GRAY8, uint32_t, u32x4>::type;  // the CH prefixes of one column
-    __shared__ __attribute__((aligned(16))) uint32_t prefix_rows[kBoxWaves][16 * kWave];
+    __shared__ __attribute__((aligned(16))) uint32_t prefix_rows[kItemWaves][16 * kWave];
 
     const int wave = threadIdx.x >> 6;
-    const uint32_t work = __builtin_amdgcn_readfirstlane(blockIdx.x * kBoxWaves + (uint32_t)wave);
-    if (work >= a.nwork)
+    WaveItem it;
+    if (!wave_item(blockIdx.x, a.nwork, a.nstrips, a.nbands, 6, a.band_rows, a.h, &it))  // it.x0 unused: halo lanes
         return;
     const int lane = threadIdx.x & 63;
-    const int strip = (int)(work % (uint32_t)a.nstrips);
-    const uint32_t t = work / (uint32_t)a.nstrips;
-    const int band = (int)(t % (uint32_t)a.nbands);
-    const size_t frame = t / (uint32_t)a.nbands;
-    const int y0 = band * a.band_rows, y1 = min(y0 + a.band_rows, a.h);
+    const int strip = it.tx, y0 = it.y0, y1 = it.y_end;
+    const size_t frame = it.frame;
     const int r = a.r;
     const int x_lane = strip * a.strip_cols + (lane - a.halo_lanes) * PX;
     const LaneSpan span = (x_lane >= 0 && x_lane + PX <= a.w) ? kInside
@@ -259,14 +254,6 @@ __global__ __launch_bounds__(kBoxWaves* kWave) void box_kernel(const BoxArgs a)
     }
 }
 
-template <bool GRAY8, int EPI>
-hipError_t launch_one(hipStream_t stream, const BoxArgs& a)
-{
-    const uint32_t nblocks = (a.nwork + kBoxWaves - 1) / kBoxWaves;
-    hipLaunchKernelGGL((box_kernel<GRAY8, EPI>), dim3(nblocks), dim3(kBoxWaves * kWave), 0, stream, a);
-    return hipGetLastError();
-}
-
 bool box_plan(const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int k, bool gray8, BoxArgs* out)
 {
     if (k < 3 || k > kBoxMaxK || (k & 1) == 0 || w <= 0 || h <= 0 || nframes <= 0)
@@ -285,13 +272,11 @@ bool box_plan(const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, in
     a.nstrips = (w + a.strip_cols - 1) / a.strip_cols;
     a.inv = box_inv(k);
     a.band_rows = kBoxBandPerK * k > kBoxBandFloor ? kBoxBandPerK * k : kBoxBandFloor;
-    auto nwork = [&](int rows) { return (size_t)a.nstrips * (size_t)((h + rows - 1) / rows) * (size_t)nframes; };
+    auto nwork = [&](int rows) { return band_items(a.nstrips, h, rows, nframes); };
     while (a.band_rows / 2 >= kBoxBandMin && nwork(a.band_rows) < kBoxMinWork)
         a.band_rows /= 2;
-    a.nbands = (h + a.band_rows - 1) / a.band_rows;
-    if (nwork(a.band_rows) > 0x7FFFFFF0ull)
+    if (!plan_bands(&a, h, nframes))
         return false;
-    a.nwork = (uint32_t)nwork(a.band_rows);
     *out = a;
     return true;
 }
@@ -304,7 +289,7 @@ hipError_t launch_box(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, i
     BoxArgs a;
     if (!box_plan(d_in, d_out, w, h, nframes, k, gray8, &a))
         return hipErrorInvalidValue;
-    return gray8 ? launch_one<true, kMean>(stream, a) : launch_one<false, kMean>(stream, a);
+    return dispatch_bool(gray8, [&](auto GRAY8) { return launch_items(box_kernel<GRAY8.value, kMean>, stream, a); });
 }
 
 hipError_t launch_adaptive_threshold(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes,
@@ -316,7 +301,7 @@ hipError_t launch_adaptive_threshold(hipStream_t stream, const uint8_t* d_in, ui
     a.thr = -idelta;
     a.on = inverse ? 0u : (uint32_t)max_value;
     a.off = inverse ? (uint32_t)max_value : 0u;
-    return launch_one<true, kThreshold>(stream, a);
+    return launch_items(box_kernel<true, kThreshold>, stream, a);
 }
 
 }  // namespace mi355

@@ -1,7 +1,8 @@
 // kernels.hpp — host-callable launchers of the gfx950 kernels (one .hip file each).
 // All launchers enqueue on `stream` and return the hipError_t of the launch.
 // The LDS-tiled kernels (gauss_tile, sobel_tile, gray8, morph, median, image2d) share their frame: tile_common.hpp;
-// the register-resident sliding-window kernels theirs: slide_common.hpp.
+// the register-resident sliding-window kernels theirs: slide_common.hpp; the kernels in which one wave walks one work
+// item alone (box, resize, warp, remap) theirs: wave_common.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -3,7 +3,7 @@
 // BORDER_REPLICATE, RGBA (every channel on its own) and gray8.
 //
 // One kernel template over <bytes per pixel, interpolation, border mode, coordinate source>.  The work decomposition
-// is warp.hip's: one wave owns a 2-D tile of output pixels, a lane owns kWarpPx = 4 adjacent output columns, 2^lx_log2
+// is warp.hip's: one wave owns a 2-D tile of output pixels, a lane owns kItemPx = 4 adjacent output columns, 2^lx_log2
 // lanes sit side by side and the 64 >> lx_log2 lane rows walk the tile top to bottom one row pass at a time; tiles are
 // ordered row-major and blocks go through xcd_remap.  What differs is where a pixel's source position comes from:
 //   perspective  the nine doubles by value; a lane keeps h0 x, h3 x, h6 x of its four columns in registers, computes
@@ -22,8 +22,6 @@
 #include <cmath>
 #include <cstdio>
 
-#include "kernels.hpp"
-#include "slide_common.hpp"
 #include "warp_common.hpp"
 
 namespace mi355 {
@@ -38,7 +36,7 @@ struct RemapArgs {
     const uint8_t* map1;  // FIXED: int16 (sx, sy) pairs; FLOAT: the x plane; perspective: unused
     const uint8_t* map2;  // FIXED: uint16 fy*32+fx (LINEAR only); FLOAT: the y plane
     int sw, sh, dw, dh;
-    int lx_log2;  // lanes side by side in a tile: tile width = kWarpPx << lx_log2
+    int lx_log2;  // lanes side by side in a tile: tile width = kItemPx << lx_log2
     int tile_h;   // output rows per tile, a multiple of 64 >> lx_log2
     int tiles_x, tiles_y;
     int nframes;
@@ -91,13 +89,13 @@ __device__ __forceinline__ void split(int X, int Y, int& sx, int& sy, uint32_t& 
 // the source positions of the lane's four columns of output row y, read from the map
 template <int INTERP, int SOURCE>
 __device__ __forceinline__ void map_coords(const RemapArgs& a, global_ptr<const uint8_t> map1,
-                                           global_ptr<const uint8_t> map2, int x0, int y, int (&sx)[kWarpPx],
-                                           int (&sy)[kWarpPx], uint32_t (&fx)[kWarpPx], uint32_t (&fy)[kWarpPx])
+                                           global_ptr<const uint8_t> map2, int x0, int y, int (&sx)[kItemPx],
+                                           int (&sy)[kItemPx], uint32_t (&fx)[kItemPx], uint32_t (&fy)[kItemPx])
 {
     const uint32_t row = (uint32_t)y * (uint32_t)a.dw;  // entries are 32-bit indices (launch: dw, dh <= kWarpMaxSize)
-    uint32_t e1[kWarpPx], e2[kWarpPx] = {};
+    uint32_t e1[kItemPx], e2[kItemPx] = {};
     constexpr bool second = SOURCE == kSrcFloat || INTERP == kLinear;
-    if (x0 + kWarpPx <= a.dw) {
+    if (x0 + kItemPx <= a.dw) {
         const uint64_t at = (uint64_t)(row + (uint32_t)x0);
         const u32x4 v = gload_a4<u32x4>(map1 + at * 4u);
         e1[0] = v.x, e1[1] = v.y, e1[2] = v.z, e1[3] = v.w;
@@ -110,7 +108,7 @@ __device__ __forceinline__ void map_coords(const RemapArgs& a, global_ptr<const 
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < kWarpPx; j++) {
+        for (int j = 0; j < kItemPx; j++) {
             const uint64_t at = (uint64_t)(row + (uint32_t)min(x0 + j, a.dw - 1));
             e1[j] = gload<uint32_t>(map1 + at * 4u);
             if constexpr (SOURCE == kSrcFloat)
@@ -120,7 +118,7 @@ __device__ __forceinline__ void map_coords(const RemapArgs& a, global_ptr<const 
         }
     }
 #pragma unroll
-    for (int j = 0; j < kWarpPx; j++) {
+    for (int j = 0; j < kItemPx; j++) {
         if constexpr (SOURCE == kSrcFloat) {
             constexpr float S = INTERP == kLinear ? 32.0f : 1.0f;
             split<INTERP>(map_round(__uint_as_float(e1[j]) * S), map_round(__uint_as_float(e2[j]) * S), sx[j], sy[j],
@@ -137,16 +135,16 @@ __device__ __forceinline__ void map_coords(const RemapArgs& a, global_ptr<const 
 // one row pass: the lane's four positions applied to the `nf` frames of the chunk
 template <int BPP, int INTERP, int BORDER, bool INTERIOR>
 __device__ __forceinline__ void row_pass(const RemapArgs& a, global_ptr<const uint8_t> src, global_ptr<uint8_t> dst,
-                                         int nf, int x0, int y, bool live, const int (&sx)[kWarpPx],
-                                         const int (&sy)[kWarpPx], const uint32_t (&fx)[kWarpPx],
-                                         const uint32_t (&fy)[kWarpPx])
+                                         int nf, int x0, int y, bool live, const int (&sx)[kItemPx],
+                                         const int (&sy)[kItemPx], const uint32_t (&fx)[kItemPx],
+                                         const uint32_t (&fy)[kItemPx])
 {
     const size_t src_frame = (size_t)a.sw * a.sh * BPP, dst_frame = (size_t)a.dw * a.dh * BPP;
     const uint32_t row = (uint32_t)y * (uint32_t)a.dw * (uint32_t)BPP;
     for (int f = 0; f < nf; f++) {
-        uint32_t px[kWarpPx];
+        uint32_t px[kItemPx];
 #pragma unroll
-        for (int j = 0; j < kWarpPx; j++)
+        for (int j = 0; j < kItemPx; j++)
             px[j] = sample_at<BPP, INTERP, BORDER, INTERIOR>(src, a, sx[j], sy[j], fx[j], fy[j]);
         if (live)
             warp_store<BPP>(dst + row, x0, a.dw, px);
@@ -156,30 +154,23 @@ __device__ __forceinline__ void row_pass(const RemapArgs& a, global_ptr<const ui
 }
 
 template <int BPP, int INTERP, int BORDER, int SOURCE>
-__global__ __launch_bounds__(kWarpWaves* kWave) void remap_kernel(const RemapArgs a)
+__global__ __launch_bounds__(kItemWaves* kWave) void remap_kernel(const RemapArgs a)
 {
-    const uint32_t block = xcd_remap(blockIdx.x, gridDim.x);
-    const uint32_t work = __builtin_amdgcn_readfirstlane(block * kWarpWaves + (uint32_t)(threadIdx.x >> 6));
-    if (work >= a.nwork)
+    WaveItem it;
+    if (!wave_item(xcd_remap(blockIdx.x, gridDim.x), a.nwork, a.tiles_x, a.tiles_y, a.lx_log2, a.tile_h, a.dh, &it))
         return;
-    const int lane = threadIdx.x & 63;
-    const int tx = (int)(work % (uint32_t)a.tiles_x);
-    const uint32_t t = work / (uint32_t)a.tiles_x;
-    const int ty = (int)(t % (uint32_t)a.tiles_y);
-    const int frame0 = (int)(t / (uint32_t)a.tiles_y) * a.fchunk;  // the chunk's first frame
+    const int frame0 = (int)it.frame * a.fchunk;  // the chunk's first frame
     const int nf = min(a.fchunk, a.nframes - frame0);
-    const int tile_w = kWarpPx << a.lx_log2;
-    const int ty0 = ty * a.tile_h, ty_end = min(ty0 + a.tile_h, a.dh);  // first row and one past the last
-    const int x0 = tx * tile_w + (lane & ((1 << a.lx_log2) - 1)) * kWarpPx;
+    const int x0 = it.x0, ty0 = it.y0, ty_end = it.y_end, ly = it.ly, y_step = it.y_step;
     const global_ptr<const uint8_t> src = uniform_ptr(a.in + (size_t)frame0 * ((size_t)a.sw * a.sh * BPP));
     const global_ptr<uint8_t> dst = uniform_ptr(a.out + (size_t)frame0 * ((size_t)a.dw * a.dh * BPP));
     const global_ptr<const uint8_t> map1 = uniform_ptr(a.map1), map2 = uniform_ptr(a.map2);
 
     // perspective: the column terms of the lane's four columns
-    double cx[kWarpPx], cy[kWarpPx], cw[kWarpPx];
+    double cx[kItemPx], cy[kItemPx], cw[kItemPx];
     if constexpr (SOURCE == kSrcPerspective) {
 #pragma unroll
-        for (int j = 0; j < kWarpPx; j++) {
+        for (int j = 0; j < kItemPx; j++) {
             const double x = (double)min(x0 + j, a.dw - 1);
             cx[j] = a.h0 * x;
             cy[j] = a.h3 * x;
@@ -188,18 +179,17 @@ __global__ __launch_bounds__(kWarpWaves* kWave) void remap_kernel(const RemapArg
     }
 
     constexpr int reach = INTERP == kLinear ? 1 : 0;
-    const int ly = lane >> a.lx_log2, y_step = kWave >> a.lx_log2;
     for (int yb = ty0; yb < ty_end; yb += y_step) {  // wave-uniform: every lane takes part in every pass's vote
         const bool live = yb + ly < ty_end;
         const int y = min(yb + ly, ty_end - 1);
-        int sx[kWarpPx], sy[kWarpPx];
-        uint32_t fx[kWarpPx], fy[kWarpPx];
+        int sx[kItemPx], sy[kItemPx];
+        uint32_t fx[kItemPx], fy[kItemPx];
         if constexpr (SOURCE == kSrcPerspective) {
             constexpr double S = INTERP == kLinear ? 32.0 : 1.0;
             const double yd = (double)y;
             const double rx = a.h1 * yd + a.h2, ry = a.h4 * yd + a.h5, rw = a.h7 * yd + a.h8;
 #pragma unroll
-            for (int j = 0; j < kWarpPx; j++) {
+            for (int j = 0; j < kItemPx; j++) {
                 const double w = cw[j] + rw;
                 const double s = (w != 0.0) ? S / w : 0.0;
                 split<INTERP>(persp_round((cx[j] + rx) * s), persp_round((cy[j] + ry) * s), sx[j], sy[j], fx[j], fy[j]);
@@ -209,41 +199,13 @@ __global__ __launch_bounds__(kWarpWaves* kWave) void remap_kernel(const RemapArg
         }
         bool inside = true;
 #pragma unroll
-        for (int j = 0; j < kWarpPx; j++)
+        for (int j = 0; j < kItemPx; j++)
             inside = inside && (unsigned)sx[j] < (unsigned)(a.sw - reach) && (unsigned)sy[j] < (unsigned)(a.sh - reach);
         if (__all(inside))
             row_pass<BPP, INTERP, BORDER, true>(a, src, dst, nf, x0, y, live, sx, sy, fx, fy);
         else
             row_pass<BPP, INTERP, BORDER, false>(a, src, dst, nf, x0, y, live, sx, sy, fx, fy);
     }
-}
-
-template <int BPP, int INTERP, int BORDER, int SOURCE>
-hipError_t launch_one(hipStream_t stream, const RemapArgs& a)
-{
-    const uint32_t nblocks = (a.nwork + kWarpWaves - 1) / kWarpWaves;
-    hipLaunchKernelGGL((remap_kernel<BPP, INTERP, BORDER, SOURCE>), dim3(nblocks), dim3(kWarpWaves * kWave), 0, stream, a);
-    return hipGetLastError();
-}
-
-template <int BPP, int SOURCE>
-hipError_t launch_source(hipStream_t stream, const RemapArgs& a, int interp, int border_mode)
-{
-    if (interp == kNearest)
-        return border_mode == kConstant ? launch_one<BPP, kNearest, kConstant, SOURCE>(stream, a)
-                                        : launch_one<BPP, kNearest, kReplicate, SOURCE>(stream, a);
-    return border_mode == kConstant ? launch_one<BPP, kLinear, kConstant, SOURCE>(stream, a)
-                                    : launch_one<BPP, kLinear, kReplicate, SOURCE>(stream, a);
-}
-
-template <int BPP>
-hipError_t launch_bpp(hipStream_t stream, const RemapArgs& a, int source, int interp, int border_mode)
-{
-    if (source == kSrcPerspective)
-        return launch_source<BPP, kSrcPerspective>(stream, a, interp, border_mode);
-    if (source == kSrcFixed)
-        return launch_source<BPP, kSrcFixed>(stream, a, interp, border_mode);
-    return launch_source<BPP, kSrcFloat>(stream, a, interp, border_mode);
 }
 
 // The tile and the frames per work item of a launch (kernels.hpp).  The tune build takes
@@ -254,13 +216,7 @@ void work_shape(int* lx_log2, int* tile_h, int* fchunk)
     *lx_log2 = kRemapLanesLog2;
     *tile_h = kRemapTileH;
     *fchunk = kRemapFrames;
-    if (const char* e = tune_env("MI355_TUNE_REMAP_TILE")) {
-        int l = 0, h = 0;
-        if (sscanf(e, "%dx%d", &l, &h) == 2 && l >= 0 && l <= 6 && h >= (kWave >> l) && h <= 4096 && h % (kWave >> l) == 0) {
-            *lx_log2 = l;
-            *tile_h = h;
-        }
-    }
+    tune_tile("MI355_TUNE_REMAP_TILE", lx_log2, tile_h);
     if (const char* e = tune_env("MI355_TUNE_REMAP_FRAMES")) {
         int f = 0;
         if (sscanf(e, "%d", &f) == 1 && f >= 1 && f <= 64)
@@ -272,38 +228,25 @@ hipError_t launch(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int b
                   int dst_h, int nframes, int source, const void* d_map1, const void* d_map2, const double* h,
                   int interp, int border_mode, uint32_t border_value)
 {
-    if ((bpp != 1 && bpp != 4) || (interp != kNearest && interp != kLinear) ||
-        (border_mode != kConstant && border_mode != kReplicate))
-        return hipErrorInvalidValue;
-    // pixel indices inside a frame, and entry indices inside a map, are 32-bit
-    if (src_w > kWarpMaxSize || src_h > kWarpMaxSize || dst_w > kWarpMaxSize || dst_h > kWarpMaxSize)
-        return hipErrorInvalidValue;
-    const uint64_t nwork = remap_work_items(dst_w, dst_h, nframes);
-    if (nwork == 0 || nwork > 0x7FFFFFF0ull)
-        return hipErrorInvalidValue;
     RemapArgs a{};
-    a.in = d_in;
-    a.out = d_out;
+    work_shape(&a.lx_log2, &a.tile_h, &a.fchunk);
+    if (!tile_args(&a, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, remap_work_items(dst_w, dst_h, nframes), interp,
+                   border_mode, border_value))
+        return hipErrorInvalidValue;
     a.map1 = static_cast<const uint8_t*>(d_map1);
     a.map2 = static_cast<const uint8_t*>(d_map2);
-    a.sw = src_w;
-    a.sh = src_h;
-    a.dw = dst_w;
-    a.dh = dst_h;
-    work_shape(&a.lx_log2, &a.tile_h, &a.fchunk);
-    const int tile_w = kWarpPx << a.lx_log2;
-    a.tiles_x = (dst_w + tile_w - 1) / tile_w;
-    a.tiles_y = (dst_h + a.tile_h - 1) / a.tile_h;
     a.nframes = nframes;
-    a.nwork = (uint32_t)nwork;
-    a.border = bpp == 4 ? border_value : (border_value & 0xFFu);
     if (h) {
         a.h0 = h[0], a.h1 = h[1], a.h2 = h[2];
         a.h3 = h[3], a.h4 = h[4], a.h5 = h[5];
         a.h6 = h[6], a.h7 = h[7], a.h8 = h[8];
     }
-    return bpp == 4 ? launch_bpp<4>(stream, a, source, interp, border_mode)
-                    : launch_bpp<1>(stream, a, source, interp, border_mode);
+    return dispatch_geom(bpp, interp, border_mode, [&](auto BPP, auto INTERP, auto BORDER) {
+        constexpr std::integer_sequence<int, kSrcPerspective, kSrcFixed, kSrcFloat> sources{};
+        return dispatch_int(source, sources, [&](auto SOURCE) {
+            return launch_items(remap_kernel<BPP.value, INTERP.value, BORDER.value, SOURCE.value>, stream, a);
+        });
+    });
 }
 
 }  // namespace
@@ -314,9 +257,7 @@ uint64_t remap_work_items(int dst_w, int dst_h, int nframes)
         return 0;
     int lx_log2 = 0, tile_h = 0, fchunk = 1;
     work_shape(&lx_log2, &tile_h, &fchunk);
-    const int tile_w = kWarpPx << lx_log2;
-    return (uint64_t)((dst_w + tile_w - 1) / tile_w) * (uint64_t)((dst_h + tile_h - 1) / tile_h) *
-           (uint64_t)((nframes + fchunk - 1) / fchunk);
+    return tile_items(dst_w, dst_h, lx_log2, tile_h, (nframes + fchunk - 1) / fchunk);
 }
 
 hipError_t launch_remap(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w, int src_h,

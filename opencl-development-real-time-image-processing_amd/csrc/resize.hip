@@ -15,8 +15,7 @@
 //            dword-aligned); other factors, ragged strips and odd alignments read pixel by pixel.
 // Source reads go straight from global memory; neighbouring lanes share cache lines.  Every source index is clamped into
 // the frame (lanes past the right end repeat the last column and store nothing), so no access leaves a frame.
-#include "kernels.hpp"
-#include "slide_common.hpp"
+#include "wave_common.hpp"
 
 namespace mi355 {
 
@@ -24,11 +23,11 @@ namespace {
 
 constexpr int kResizePx = 4;                      // output columns per lane
 constexpr int kResizeStrip = kWave * kResizePx;   // output columns per wave
-constexpr int kResizeWaves = 4;                   // waves per block
+static_assert(kResizePx == kItemPx, "wave_item and warp_store give a lane kItemPx columns");
 constexpr int kResizeBandMax = 16;                // output rows per band, halved while the launch has few waves
 constexpr size_t kResizeMinWork = 4096;           // ~4 waves per SIMD before bands grow
 
-constexpr int kNearest = 0, kLinear = 1, kArea = 3;  // MI355_INTERP_*
+constexpr int kArea = 3;  // MI355_INTERP_AREA, beside kNearest and kLinear
 
 struct ResizeArgs {
     const uint8_t* in;
@@ -41,32 +40,6 @@ struct ResizeArgs {
     float area_scale;         // AREA: 1.f / (float)(nx * ny), from the host
 };
 
-// four output pixels of a lane (RGBA: dwords; gray8: byte values) to columns x0 .. x0 + 3 of the row at `rowp`
-template <int BPP>
-__device__ __forceinline__ void store_px(global_ptr<uint8_t> rowp, int x0, int dw, const uint32_t (&px)[kResizePx])
-{
-    if constexpr (BPP == 4) {
-        if (x0 + kResizePx <= dw) {
-            gstore_a4<u32x4>(rowp + (uint32_t)x0 * 4u, u32x4{px[0], px[1], px[2], px[3]});
-        } else {
-#pragma unroll
-            for (int j = 0; j < kResizePx; j++)
-                if (x0 + j < dw)
-                    gstore_a4<uint32_t>(rowp + (uint32_t)(x0 + j) * 4u, px[j]);
-        }
-    } else {
-        global_ptr<uint8_t> p = rowp + (uint32_t)x0;
-        if (x0 + kResizePx <= dw && (reinterpret_cast<uint64_t>(p) & 3u) == 0) {
-            gstore_a4<uint32_t>(p, px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24));
-        } else {
-#pragma unroll
-            for (int j = 0; j < kResizePx; j++)
-                if (x0 + j < dw)
-                    p[j] = (uint8_t)px[j];
-        }
-    }
-}
-
 // LINEAR: H(row) >> 4 of the lane's columns, every channel: src[sx] * a0 + src[min(sx + 1, sw - 1)] * a1
 template <int BPP>
 __device__ __forceinline__ void fetch_h(global_ptr<const uint8_t> rowp, const uint32_t (&off0)[kResizePx],
@@ -76,13 +49,8 @@ __device__ __forceinline__ void fetch_h(global_ptr<const uint8_t> rowp, const ui
     uint32_t p0[kResizePx], p1[kResizePx];
 #pragma unroll
     for (int j = 0; j < kResizePx; j++) {
-        if constexpr (BPP == 4) {
-            p0[j] = gload<uint32_t>(rowp + off0[j]);
-            p1[j] = gload<uint32_t>(rowp + off1[j]);
-        } else {
-            p0[j] = gload<uint8_t>(rowp + off0[j]);
-            p1[j] = gload<uint8_t>(rowp + off1[j]);
-        }
+        p0[j] = load_px_at<BPP>(rowp + off0[j]);
+        p1[j] = load_px_at<BPP>(rowp + off1[j]);
     }
 #pragma unroll
     for (int j = 0; j < kResizePx; j++)
@@ -99,9 +67,11 @@ __device__ __forceinline__ uint32_t area_byte(uint32_t sum, float scale)
 }
 
 template <int BPP, int INTERP, int NX>
-__global__ __launch_bounds__(kResizeWaves* kWave) void resize_kernel(const ResizeArgs a)
+__global__ __launch_bounds__(kItemWaves* kWave) void resize_kernel(const ResizeArgs a)
 {
-    const uint32_t work = __builtin_amdgcn_readfirstlane(blockIdx.x * kResizeWaves + (uint32_t)(threadIdx.x >> 6));
+    // The decode stays in place, not wave_item's: through it the argument loads come in other groups, and LINEAR RGBA
+    // 4K -> 720p ran 0.5 % slower in three of four runs (profiles/wave_frame_ab.txt).
+    const uint32_t work = __builtin_amdgcn_readfirstlane(blockIdx.x * kItemWaves + (uint32_t)(threadIdx.x >> 6));
     if (work >= a.nwork)
         return;
     const int lane = threadIdx.x & 63;
@@ -178,7 +148,7 @@ __global__ __launch_bounds__(kResizeWaves* kWave) void resize_kernel(const Resiz
                     px[j] |= (uint32_t)v << (8 * c);
                 }
             }
-            store_px<BPP>(uniform_ptr(dst + (size_t)dy * dst_row), x0, a.dw, px);
+            warp_store<BPP>(uniform_ptr(dst + (size_t)dy * dst_row), x0, a.dw, px);
         }
     } else if constexpr (INTERP == kNearest) {
         uint32_t off[kResizePx];
@@ -192,13 +162,9 @@ __global__ __launch_bounds__(kResizeWaves* kWave) void resize_kernel(const Resiz
                 __builtin_amdgcn_readfirstlane(min((int)__builtin_floor((double)dy * a.scale_y), a.sh - 1));
             const global_ptr<const uint8_t> rowp = uniform_ptr(src + (size_t)sy * src_row);
 #pragma unroll
-            for (int j = 0; j < kResizePx; j++) {
-                if constexpr (BPP == 4)
-                    px[j] = gload<uint32_t>(rowp + off[j]);
-                else
-                    px[j] = gload<uint8_t>(rowp + off[j]);
-            }
-            store_px<BPP>(uniform_ptr(dst + (size_t)dy * dst_row), x0, a.dw, px);
+            for (int j = 0; j < kResizePx; j++)
+                px[j] = load_px_at<BPP>(rowp + off[j]);
+            warp_store<BPP>(uniform_ptr(dst + (size_t)dy * dst_row), x0, a.dw, px);
         }
     } else {
         const int nx = a.nx, ny = a.ny;
@@ -247,12 +213,12 @@ __global__ __launch_bounds__(kResizeWaves* kWave) void resize_kernel(const Resiz
                     for (int i = 0; i < nx; i++) {
 #pragma unroll
                         for (int j = 0; j < kResizePx; j++) {
+                            const uint32_t p = load_px_at<BPP>(rowp + col[j] + (uint32_t)i * BPP);
                             if constexpr (BPP == 4) {
-                                const uint32_t p = gload<uint32_t>(rowp + col[j] + (uint32_t)i * 4u);
                                 lo[j] += p & 0x00FF00FFu;
                                 hi[j] += (p >> 8) & 0x00FF00FFu;
                             } else {
-                                lo[j] += gload<uint8_t>(rowp + col[j] + (uint32_t)i);
+                                lo[j] += p;
                             }
                         }
                     }
@@ -272,31 +238,9 @@ __global__ __launch_bounds__(kResizeWaves* kWave) void resize_kernel(const Resiz
                     px[j] = shift2 ? (lo[j] + 2u) >> 2 : area_byte(lo[j], a.area_scale);
                 }
             }
-            store_px<BPP>(uniform_ptr(dst + (size_t)dy * dst_row), x0, a.dw, px);
+            warp_store<BPP>(uniform_ptr(dst + (size_t)dy * dst_row), x0, a.dw, px);
         }
     }
-}
-
-template <int BPP, int INTERP, int NX>
-hipError_t launch_one(hipStream_t stream, const ResizeArgs& a)
-{
-    const uint32_t nblocks = (a.nwork + kResizeWaves - 1) / kResizeWaves;
-    hipLaunchKernelGGL((resize_kernel<BPP, INTERP, NX>), dim3(nblocks), dim3(kResizeWaves * kWave), 0, stream, a);
-    return hipGetLastError();
-}
-
-template <int BPP>
-hipError_t launch_bpp(hipStream_t stream, const ResizeArgs& a, int interp)
-{
-    if (interp == kNearest)
-        return launch_one<BPP, kNearest, 0>(stream, a);
-    if (interp == kLinear)
-        return launch_one<BPP, kLinear, 0>(stream, a);
-    if (a.nx == 2)
-        return launch_one<BPP, kArea, 2>(stream, a);
-    if (a.nx == 4)
-        return launch_one<BPP, kArea, 4>(stream, a);
-    return launch_one<BPP, kArea, 0>(stream, a);
 }
 
 }  // namespace
@@ -341,14 +285,23 @@ hipError_t launch_resize(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out
     }
     a.nstrips = (dst_w + kResizeStrip - 1) / kResizeStrip;
     a.band_rows = kResizeBandMax;
-    auto nwork = [&](int rows) { return (size_t)a.nstrips * (size_t)((dst_h + rows - 1) / rows) * (size_t)nframes; };
+    auto nwork = [&](int rows) { return band_items(a.nstrips, dst_h, rows, nframes); };
     while (a.band_rows > 1 && nwork(a.band_rows) < kResizeMinWork)
         a.band_rows /= 2;
-    a.nbands = (dst_h + a.band_rows - 1) / a.band_rows;
-    if (nwork(a.band_rows) > 0x7FFFFFF0ull)
+    if (!plan_bands(&a, dst_h, nframes))
         return hipErrorInvalidValue;
-    a.nwork = (uint32_t)nwork(a.band_rows);
-    return bpp == 4 ? launch_bpp<4>(stream, a, interp) : launch_bpp<1>(stream, a, interp);
+    // AREA reads its lane's span of x-factor 2 or 4 in 16-byte loads
+    const int nx_wide = (interp == kArea && (a.nx == 2 || a.nx == 4)) ? a.nx : 0;
+    return dispatch_int(bpp, std::integer_sequence<int, 1, 4>{}, [&](auto BPP) {
+        return dispatch_int(interp, std::integer_sequence<int, kNearest, kLinear, kArea>{}, [&](auto INTERP) {
+            return dispatch_int(nx_wide, std::integer_sequence<int, 0, 2, 4>{}, [&](auto NX) {
+                if constexpr (INTERP.value == kArea || NX.value == 0)
+                    return launch_items(resize_kernel<BPP.value, INTERP.value, NX.value>, stream, a);
+                else
+                    return hipErrorInvalidValue;
+            });
+        });
+    });
 }
 
 }  // namespace mi355

@@ -3,7 +3,7 @@
 // BORDER_CONSTANT and BORDER_REPLICATE, RGBA (every channel on its own) and gray8.
 //
 // One kernel template over <bytes per pixel, interpolation, border mode>.  A work item is one wave owning a 2-D tile of
-// output pixels: a lane owns kWarpPx = 4 adjacent output columns (16 bytes per RGBA store, one dword per gray8 store where
+// output pixels: a lane owns kItemPx = 4 adjacent output columns (16 bytes per RGBA store, one dword per gray8 store where
 // the address allows it, byte stores at ragged ends and odd alignments), 2^lx_log2 lanes sit side by side and the
 // 64 >> lx_log2 lane rows walk the tile top to bottom, so the source lines of one pass are the lines the pass before
 // touched.  The host picks one of two tile shapes per launch from the map's slant (launch_warp_affine).  Tiles are ordered
@@ -19,10 +19,7 @@
 // the taps that lay outside.  Lanes past the right end repeat the last column and store nothing.  No access leaves a
 // frame.
 #include <cmath>
-#include <cstdio>
 
-#include "kernels.hpp"
-#include "slide_common.hpp"
 #include "warp_common.hpp"
 
 namespace mi355 {
@@ -33,7 +30,7 @@ struct WarpArgs {
     const uint8_t* in;
     uint8_t* out;
     int sw, sh, dw, dh;
-    int lx_log2;  // lanes side by side in a tile: tile width = kWarpPx << lx_log2
+    int lx_log2;  // lanes side by side in a tile: tile width = kItemPx << lx_log2
     int tile_h;   // output rows per tile, a multiple of 64 >> lx_log2
     int tiles_x, tiles_y;
     uint32_t nwork;
@@ -58,43 +55,37 @@ __device__ __forceinline__ uint32_t sample(global_ptr<const uint8_t> src, const 
 // the lane's rows of the tile, top to bottom
 template <int BPP, int INTERP, int BORDER, bool INTERIOR>
 __device__ __forceinline__ void walk_rows(const WarpArgs& a, global_ptr<const uint8_t> src, global_ptr<uint8_t> dst,
-                                          int x0, int y_first, int y_end, int y_step, const int (&adelta)[kWarpPx],
-                                          const int (&bdelta)[kWarpPx])
+                                          int x0, int y_first, int y_end, int y_step, const int (&adelta)[kItemPx],
+                                          const int (&bdelta)[kItemPx])
 {
     constexpr int rd = INTERP == kLinear ? 16 : 512;
     for (int y = y_first; y < y_end; y += y_step) {
         const int X0 = fix10(a.i1 * (double)y + a.i2) + rd;
         const int Y0 = fix10(a.i4 * (double)y + a.i5) + rd;
-        uint32_t px[kWarpPx];
+        uint32_t px[kItemPx];
 #pragma unroll
-        for (int j = 0; j < kWarpPx; j++)
+        for (int j = 0; j < kItemPx; j++)
             px[j] = sample<BPP, INTERP, BORDER, INTERIOR>(src, a, X0 + adelta[j], Y0 + bdelta[j]);
         warp_store<BPP>(dst + (uint32_t)y * (uint32_t)a.dw * (uint32_t)BPP, x0, a.dw, px);
     }
 }
 
 template <int BPP, int INTERP, int BORDER>
-__global__ __launch_bounds__(kWarpWaves* kWave) void warp_kernel(const WarpArgs a)
+__global__ __launch_bounds__(kItemWaves* kWave) void warp_kernel(const WarpArgs a)
 {
-    const uint32_t block = xcd_remap(blockIdx.x, gridDim.x);
-    const uint32_t work = __builtin_amdgcn_readfirstlane(block * kWarpWaves + (uint32_t)(threadIdx.x >> 6));
-    if (work >= a.nwork)
+    WaveItem it;
+    if (!wave_item(xcd_remap(blockIdx.x, gridDim.x), a.nwork, a.tiles_x, a.tiles_y, a.lx_log2, a.tile_h, a.dh, &it))
         return;
-    const int lane = threadIdx.x & 63;
-    const int tx = (int)(work % (uint32_t)a.tiles_x);
-    const uint32_t t = work / (uint32_t)a.tiles_x;
-    const int ty = (int)(t % (uint32_t)a.tiles_y);
-    const size_t frame = t / (uint32_t)a.tiles_y;
-    const int tile_w = kWarpPx << a.lx_log2;
-    const int tx0 = tx * tile_w, tx1 = min(tx0 + tile_w, a.dw) - 1;           // first and last column of the tile
-    const int ty0 = ty * a.tile_h, ty_end = min(ty0 + a.tile_h, a.dh);         // first row and one past the last
-    const int x0 = tx0 + (lane & ((1 << a.lx_log2) - 1)) * kWarpPx;
+    const size_t frame = it.frame;
+    const int x0 = it.x0, ty0 = it.y0, ty_end = it.y_end;
+    const int tile_w = kItemPx << a.lx_log2;
+    const int tx0 = it.tx * tile_w, tx1 = min(tx0 + tile_w, a.dw) - 1;  // first and last column of the tile
     const global_ptr<const uint8_t> src = uniform_ptr(a.in + frame * ((size_t)a.sw * a.sh * BPP));
     const global_ptr<uint8_t> dst = uniform_ptr(a.out + frame * ((size_t)a.dw * a.dh * BPP));
 
-    int adelta[kWarpPx], bdelta[kWarpPx];
+    int adelta[kItemPx], bdelta[kItemPx];
 #pragma unroll
-    for (int j = 0; j < kWarpPx; j++) {
+    for (int j = 0; j < kItemPx; j++) {
         const double x = (double)min(x0 + j, a.dw - 1);
         adelta[j] = fix10(a.i0 * x);
         bdelta[j] = fix10(a.i3 * x);
@@ -112,29 +103,10 @@ __global__ __launch_bounds__(kWarpWaves* kWave) void warp_kernel(const WarpArgs 
     const bool interior =
         __builtin_amdgcn_readfirstlane((int)(sx_min >= 0 && sx_max <= a.sw - 1 && sy_min >= 0 && sy_max <= a.sh - 1)) != 0;
 
-    const int y_first = ty0 + (lane >> a.lx_log2), y_step = kWave >> a.lx_log2;
     if (interior)
-        walk_rows<BPP, INTERP, BORDER, true>(a, src, dst, x0, y_first, ty_end, y_step, adelta, bdelta);
+        walk_rows<BPP, INTERP, BORDER, true>(a, src, dst, x0, ty0 + it.ly, ty_end, it.y_step, adelta, bdelta);
     else
-        walk_rows<BPP, INTERP, BORDER, false>(a, src, dst, x0, y_first, ty_end, y_step, adelta, bdelta);
-}
-
-template <int BPP, int INTERP, int BORDER>
-hipError_t launch_one(hipStream_t stream, const WarpArgs& a)
-{
-    const uint32_t nblocks = (a.nwork + kWarpWaves - 1) / kWarpWaves;
-    hipLaunchKernelGGL((warp_kernel<BPP, INTERP, BORDER>), dim3(nblocks), dim3(kWarpWaves * kWave), 0, stream, a);
-    return hipGetLastError();
-}
-
-template <int BPP>
-hipError_t launch_bpp(hipStream_t stream, const WarpArgs& a, int interp, int border_mode)
-{
-    if (interp == kNearest)
-        return border_mode == kConstant ? launch_one<BPP, kNearest, kConstant>(stream, a)
-                                        : launch_one<BPP, kNearest, kReplicate>(stream, a);
-    return border_mode == kConstant ? launch_one<BPP, kLinear, kConstant>(stream, a)
-                                    : launch_one<BPP, kLinear, kReplicate>(stream, a);
+        walk_rows<BPP, INTERP, BORDER, false>(a, src, dst, x0, ty0 + it.ly, ty_end, it.y_step, adelta, bdelta);
 }
 
 // The tile of a launch (kernels.hpp; both shapes and the rule between them come from the A/B of tools/warp_rate.py): the
@@ -145,63 +117,41 @@ void tile_shape(const double inv[6], int* lx_log2, int* tile_h)
     const bool wide = warp_tile_is_wide(inv);
     *lx_log2 = wide ? kWarpWideLanesLog2 : kWarpSquareLanesLog2;
     *tile_h = wide ? kWarpWideH : kWarpSquareH;
-    if (const char* e = tune_env("MI355_TUNE_WARP_TILE")) {
-        int l = 0, h = 0;
-        if (sscanf(e, "%dx%d", &l, &h) == 2 && l >= 0 && l <= 6 && h >= (kWave >> l) && h <= 4096 && h % (kWave >> l) == 0) {
-            *lx_log2 = l;
-            *tile_h = h;
-        }
-    }
+    tune_tile("MI355_TUNE_WARP_TILE", lx_log2, tile_h);
 }
 
 }  // namespace
 
 bool warp_tile_is_wide(const double inv[6])
 {
-    return std::fabs(inv[3]) * (double)(kWarpPx << kWarpWideLanesLog2) <= kWarpWideMaxRows;
+    return std::fabs(inv[3]) * (double)(kItemPx << kWarpWideLanesLog2) <= kWarpWideMaxRows;
 }
 
 uint64_t warp_work_items(const double inv[6], int dst_w, int dst_h, int nframes)
 {
     int lx_log2 = 0, tile_h = 0;
     tile_shape(inv, &lx_log2, &tile_h);
-    const int tile_w = kWarpPx << lx_log2;
-    return (uint64_t)((dst_w + tile_w - 1) / tile_w) * (uint64_t)((dst_h + tile_h - 1) / tile_h) * (uint64_t)nframes;
+    return tile_items(dst_w, dst_h, lx_log2, tile_h, nframes);
 }
 
 hipError_t launch_warp_affine(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int bpp, int src_w, int src_h,
                               int dst_w, int dst_h, int nframes, const double inv[6], int interp, int border_mode,
                               uint32_t border_value)
 {
-    if ((bpp != 1 && bpp != 4) || (interp != kNearest && interp != kLinear) ||
-        (border_mode != kConstant && border_mode != kReplicate))
-        return hipErrorInvalidValue;
-    // pixel indices inside a frame are 32-bit, times 4 bytes
-    if (src_w > kWarpMaxSize || src_h > kWarpMaxSize || dst_w > kWarpMaxSize || dst_h > kWarpMaxSize)
-        return hipErrorInvalidValue;
-    const uint64_t nwork = warp_work_items(inv, dst_w, dst_h, nframes);
-    if (nwork == 0 || nwork > 0x7FFFFFF0ull)
-        return hipErrorInvalidValue;
     WarpArgs a{};
-    a.in = d_in;
-    a.out = d_out;
-    a.sw = src_w;
-    a.sh = src_h;
-    a.dw = dst_w;
-    a.dh = dst_h;
     tile_shape(inv, &a.lx_log2, &a.tile_h);
-    const int tile_w = kWarpPx << a.lx_log2;
-    a.tiles_x = (dst_w + tile_w - 1) / tile_w;
-    a.tiles_y = (dst_h + a.tile_h - 1) / a.tile_h;
-    a.nwork = (uint32_t)nwork;
-    a.border = bpp == 4 ? border_value : (border_value & 0xFFu);
+    if (!tile_args(&a, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, warp_work_items(inv, dst_w, dst_h, nframes),
+                   interp, border_mode, border_value))
+        return hipErrorInvalidValue;
     a.i0 = inv[0];
     a.i1 = inv[1];
     a.i2 = inv[2];
     a.i3 = inv[3];
     a.i4 = inv[4];
     a.i5 = inv[5];
-    return bpp == 4 ? launch_bpp<4>(stream, a, interp, border_mode) : launch_bpp<1>(stream, a, interp, border_mode);
+    return dispatch_geom(bpp, interp, border_mode, [&](auto BPP, auto INTERP, auto BORDER) {
+        return launch_items(warp_kernel<BPP.value, INTERP.value, BORDER.value>, stream, a);
+    });
 }
 
 }  // namespace mi355

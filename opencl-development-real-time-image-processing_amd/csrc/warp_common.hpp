@@ -1,8 +1,8 @@
-// warp_common.hpp — the device pieces the geometric kernels share (warp.hip: cv::warpAffine; remap.hip: cv::remap and
-// cv::warpPerspective).  Both give a lane kWarpPx = 4 adjacent output columns of a row and differ only in where a
-// pixel's source position (sx, sy, fx, fy) comes from; what is done with it lives here:
-//   warp_store  the lane's four output pixels, whole where the address and the row's end allow it;
-//   load_px     one source pixel;
+// warp_common.hpp — the sampling pieces the geometric kernels share (warp.hip: cv::warpAffine; remap.hip: cv::remap and
+// cv::warpPerspective) on top of the wave-per-item frame of wave_common.hpp.  Both give a lane kItemPx = 4 adjacent
+// output columns of a row and differ only in where a pixel's source position (sx, sy, fx, fy) comes from; what is done
+// with it lives here:
+//   load_px     one source pixel by its index in the frame;
 //   blend       the LINEAR sum of include/mi355_imgfilter.h, RGBA as (R, B) / (G, A) u16 pairs;
 //   sample_at   one output pixel from (sx, sy, fx, fy): with INTERIOR no tap is tested (RGBA LINEAR: the two
 //               horizontally adjacent taps of a source row as one 8-byte load), otherwise every index is clamped into
@@ -10,52 +10,16 @@
 // No access leaves the frame.
 #pragma once
 
-#include "kernels.hpp"
-#include "slide_common.hpp"
+#include "wave_common.hpp"
 
 namespace mi355 {
 
 namespace {
 
-constexpr int kWarpPx = 4;     // output columns per lane
-constexpr int kWarpWaves = 4;  // waves (tiles) per block
-
-constexpr int kNearest = 0, kLinear = 1;     // MI355_INTERP_*
-constexpr int kConstant = 0, kReplicate = 1;  // MI355_BORDER_*
-
-// four output pixels of a lane (RGBA: dwords; gray8: byte values) to columns x0 .. x0 + 3 of the row at `rowp`
-template <int BPP>
-__device__ __forceinline__ void warp_store(global_ptr<uint8_t> rowp, int x0, int dw, const uint32_t (&px)[kWarpPx])
-{
-    if constexpr (BPP == 4) {
-        if (x0 + kWarpPx <= dw) {
-            gstore_a4<u32x4>(rowp + (uint32_t)x0 * 4u, u32x4{px[0], px[1], px[2], px[3]});
-        } else {
-#pragma unroll
-            for (int j = 0; j < kWarpPx; j++)
-                if (x0 + j < dw)
-                    gstore_a4<uint32_t>(rowp + (uint32_t)(x0 + j) * 4u, px[j]);
-        }
-    } else {
-        global_ptr<uint8_t> p = rowp + (uint32_t)x0;
-        if (x0 + kWarpPx <= dw && (reinterpret_cast<uint64_t>(p) & 3u) == 0) {
-            gstore_a4<uint32_t>(p, px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24));
-        } else {
-#pragma unroll
-            for (int j = 0; j < kWarpPx; j++)
-                if (x0 + j < dw)
-                    p[j] = (uint8_t)px[j];
-        }
-    }
-}
-
 template <int BPP>
 __device__ __forceinline__ uint32_t load_px(global_ptr<const uint8_t> src, uint32_t pixel)
 {
-    if constexpr (BPP == 4)
-        return gload<uint32_t>(src + pixel * 4u);
-    else
-        return gload<uint8_t>(src + pixel);
+    return load_px_at<BPP>(src + pixel * (uint32_t)BPP);
 }
 
 // (wx0 p00 + wx1 p01) wy0 + (wx0 p10 + wx1 p11) wy1 + 512 >> 10 per channel: the four products of the header's sum,

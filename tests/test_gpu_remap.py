@@ -144,6 +144,33 @@ def test_perspective_is_bit_identical_to_the_cpu_reference(ctx, bpp, interp, bor
     assert interior >= 1 and general >= 1, (interior, general)
 
 
+@pytest.mark.parametrize("bpp,interp", BPP_INTERP, ids=[_id(*v) for v in BPP_INTERP])
+def test_tile_grids_with_a_one_pixel_ragged_edge(ctx, bpp, interp):
+    """The work-item decode at its smallest: one ragged tile alone in a frame (5 x 3), and a 2 x 2 grid of tiles whose
+    second column and second row hold one pixel each (33 x 33), from every coordinate source.  Five frames: one whole
+    chunk of frames and a ragged one, so that tile column, tile row and chunk each show up in the output when one is
+    taken for another."""
+    sw, sh = 40, 36
+    assert cases.FRAMES_PER_ITEM == 4
+    frames = np.stack([noise(sh, sw, bpp, 31 + f) for f in range(5)])
+    for dw, dh in ((5, 3), (cases.TILE[0] + 1, cases.TILE[1] + 1)):
+        assert (dw, dh) in ((5, 3), (33, 33))
+        for border in (CONSTANT, REPLICATE):
+            for kind in (FIXED, FLOAT):
+                for name, map1, map2 in cases.remap_maps(sw, sh, dw, dh, kind, interp)[:3]:
+                    coords = map_coords(map1, map2, kind, interp)
+                    got = _remap(ctx, bpp, frames, map1, map2, kind, interp, border, 0x80FF407F)
+                    for f in range(5):
+                        assert np.array_equal(got[f], sample(frames[f], coords, interp, border, 0x80FF407F)), (
+                            (dw, dh), KIND_NAME[kind], name, f)
+            for name, m in cases.homographies(sw, sh)[2:4]:
+                coords = perspective_coords(m, dw, dh, interp)
+                got = _perspective(ctx, bpp, frames, m, dw, dh, interp, border, 0x80FF407F)
+                for f in range(5):
+                    assert np.array_equal(got[f], sample(frames[f], coords, interp, border, 0x80FF407F)), (
+                        (dw, dh), name, f)
+
+
 def _sources(sw, sh, dw, dh, interp):
     """One runner per coordinate source: (name, run(ctx, bpp, frames, border, value), coords)."""
     rot30 = rotation((sw - 1) / 2.0, (sh - 1) / 2.0, 30.0)

@@ -131,6 +131,26 @@ def test_interior_and_general_tiles_agree(ctx, bpp, interp, border):
             assert np.array_equal(got, warp_ref(img, m, dw, dh, interp, border, value)), (angle, hex(value))
 
 
+@pytest.mark.parametrize("bpp,interp,border", VARIANTS, ids=VARIANT_IDS)
+def test_tile_grids_with_a_one_pixel_ragged_edge(ctx, bpp, interp, border):
+    """The work-item decode at its smallest: one ragged tile alone in a frame (5 x 3, on either tile shape), and a 2 x 2
+    grid of tiles whose second column and second row hold one pixel each, on the square tile (33 x 33 under a turn by 30
+    degrees) and on the wide tile (65 x 17 under the identity).  Three frames, so that tile column, tile row and frame
+    each show up in the output when one is taken for another."""
+    sw, sh = 70, 40
+    frames = np.stack([noise(sh, sw, bpp, 21), extremes(sh, sw, bpp, 22), noise(sh, sw, bpp, 23)])
+    # inverse-mapped: the identity, and a turn by 30 degrees that starts inside the source and leaves it within 33 rows
+    identity, turn = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0], [0.866, -0.5, 20.0, 0.5, 0.866, 10.0]
+    flags = interp | INVERSE_MAP
+    for (dw, dh), m, tile in (((5, 3), identity, WIDE), ((5, 3), turn, SQUARE), ((33, 33), turn, SQUARE),
+                              ((65, 17), identity, WIDE)):
+        assert tile_of(m, flags) == tile
+        assert (dw, dh) == (5, 3) or (dw, dh) == (tile[0] + 1, tile[1] + 1)
+        got = _run(ctx, bpp, frames, m, dw, dh, flags, border, 0x80FF407F)
+        for f in range(3):
+            assert np.array_equal(got[f], warp_ref(frames[f], m, dw, dh, flags, border, 0x80FF407F)), ((dw, dh), f)
+
+
 @pytest.mark.parametrize("bpp,interp", BPP_INTERP, ids=BPP_INTERP_IDS)
 def test_frames_are_independent(ctx, bpp, interp):
     """Three frames of different content equal three single-frame calls, and on frames that alternate between 0 and 255
