@@ -589,6 +589,65 @@ int mi355_adaptive_threshold_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d
 int mi355_adaptive_threshold_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
                                            int max_value, int type, int block, double delta, uint64_t prof_ns[6]);
 
+/* ---- local contrast: cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst), 8-bit ------------------------
+ * Contrast-limited adaptive histogram equalization.  gray8 frames only (the single-channel rules: tightly packed, any
+ * byte alignment, any width >= 1, frames are independent, MI355_ERR_UNSUPPORTED under MI355_INPUT_BGR).  Entry points of
+ * their own, not filter ids: the parameters do not fit (k, sigma).  OpenCV is not installed where this library is built
+ * and tested: the arithmetic below restates OpenCV's plain C++ path (modules/imgproc/src/clahe.cpp, 8-bit branch) from
+ * memory, and it — not OpenCV — is the contract.  The library is built with -ffp-contract=off: nothing fuses.
+ * Geometry (host, int).  If w % tiles_x == 0 and h % tiles_y == 0: ew = w, eh = h.  Otherwise ew = w + (tiles_x - w %
+ * tiles_x) and eh = h + (tiles_y - h % tiles_y): OpenCV's quirk is kept — when only one dimension fails to divide, the
+ * other is still padded, by a full tiles_x or tiles_y.  tw = ew / tiles_x, th = eh / tiles_y, tot = tw * th.  The extended
+ * frame is cv::copyMakeBorder(BORDER_REFLECT_101) on the right and bottom only:
+ *     ext[y][x] = src[r(y, h)][r(x, w)],   r(p, n) = p < n ? p : 2n - 2 - p
+ * and never exists in memory.
+ * Tile tables (int except where marked).  For every tile (j, i), hist = the 256 counts of ext[j*th .. (j+1)*th)[i*tw ..
+ * (i+1)*tw).
+ *     cl = clip_limit > 0 ? max((int)(clip_limit * tot / 256.0), 1) : 0        fp64, truncation (capped at tot, which
+ *                                                                              cannot be observed: no bin exceeds tot)
+ *     if cl > 0:
+ *         clipped = sum over bins of max(hist[b] - cl, 0);  hist[b] = min(hist[b], cl)
+ *         batch = clipped / 256;  residual = clipped - batch * 256;  hist[b] += batch
+ *         if residual: step = max(256 / residual, 1);  bins 0, step, 2*step, ... (residual of them) get +1,
+ *                      i.e. bin b gets it iff b % step == 0 && b / step < residual
+ *     lut_scale = 255.0f / (float)tot                                          fp32, on the host
+ *     sum += hist[b];  lut[b] = saturate_u8(rint_half_even((float)sum * lut_scale))
+ * A constant frame is therefore NOT mapped to itself: a frame of 7s, 64 x 48 with 8 x 8 tiles, gives 16 with clip_limit
+ * 2.0 and 255 with clip_limit 0.
+ * Apply (fp32, in the written order, no fused multiply-add).  inv_tw = 1.0f / (float)tw and inv_th = 1.0f / (float)th are
+ * computed on the host and passed by value (the device's own fp32 division is not the contract).
+ *     txf = (float)x * inv_tw - 0.5f;  tx1 = (int)floorf(txf);  xa = txf - (float)tx1;  xa1 = 1.0f - xa
+ *     c1 = max(tx1, 0);  c2 = min(tx1 + 1, tiles_x - 1)        (rows likewise: tyf, ya, ya1, r1, r2 from y and inv_th)
+ *     v = src[y][x]
+ *     res = ((float)L[r1][c1][v] * xa1 + (float)L[r1][c2][v] * xa) * ya1
+ *         + ((float)L[r2][c1][v] * xa1 + (float)L[r2][c2][v] * xa) * ya
+ *     out = saturate_u8(rint_half_even(res))
+ * Only the w x h pixels of the source are written.
+ * MI355_ERR_BAD_ARG: a null pointer or context; sizes the filter calls reject; ew * eh >= 2^31 (the limit of the
+ * histogram calls, applied to the extended frame); tiles_x or tiles_y outside 1 .. MI355_MAX_CLAHE_TILES; a non-finite
+ * clip_limit; overlapping ranges; a d_luts that is not 4-byte aligned.
+ * MI355_ERR_UNSUPPORTED: a pad that one reflection cannot serve, ew - w > w - 1 or eh - h > h - 1 (31 x 16 with 16 x 16
+ * tiles: the quirk pads 16 rows onto 16).  OpenCV reflects repeatedly there; this library does not.
+ *   mi355_clahe_check           pure host function returning exactly these codes for these values.
+ *   mi355_clahe_gray8_dev       the rules of mi355_filter_dev: three launches (tile histograms, tables, apply) and one
+ *                               memset on the context's stream, no synchronisation.  The scratch, tiles x (1 KiB + 256 B)
+ *                               per frame, is pooled in the context: after the first call for a given (nframes, tiles_x,
+ *                               tiles_y) a call allocates nothing and waits for nothing, so it can be captured into a
+ *                               hipGraph.
+ *   mi355_clahe_luts_gray8_dev  the tables only: nframes x tiles_y x tiles_x x 256 bytes to d_luts (4-byte aligned),
+ *                               frame-major then tile-row-major.  To CLAHE what mi355_hist_gray8_dev is to equalize.
+ *   mi355_clahe_gray8_batched   host buffers: H2D, the launches, D2H through the context's pooled buffers; prof_ns (may be
+ *                               NULL) gets the six timestamps of mi355_filter_batched.
+ * Not offered: RGBA or Lab frames, 16-bit frames, the streamed, group and mi355_pool_alloc forms, row pitch and ROI. */
+#define MI355_MAX_CLAHE_TILES 16
+int mi355_clahe_check(int w, int h, int nframes, double clip_limit, int tiles_x, int tiles_y);
+int mi355_clahe_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes, double clip_limit,
+                          int tiles_x, int tiles_y);
+int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
+                              double clip_limit, int tiles_x, int tiles_y, uint64_t prof_ns[6]);
+int mi355_clahe_luts_gray8_dev(mi355_ctx* ctx, const void* d_in, uint8_t* d_luts, int w, int h, int nframes,
+                               double clip_limit, int tiles_x, int tiles_y);
+
 /* Synthetic frames: px = hash(seed, first_frame + f, y, x), A = 255; mode 1 = smooth
  * gradient + 4-bit noise, mode 2 = flat 64 x 64 patches (constant windows: the content that sends the
  * exact-by-exception kernels down their exception path), mode 3 = gray noise (r = g = b: every pixel on the

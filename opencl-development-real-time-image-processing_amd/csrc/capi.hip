@@ -1497,6 +1497,123 @@ MI355_API int mi355_otsu_thresholds_gray8_dev(mi355_ctx* ctx, const void* d_in, 
     return hist_tables(ctx, static_cast<const uint8_t*>(d_in), d_thresh, w, h, nframes, true);
 }
 
+// The value checks of every CLAHE call and, when they pass, the call's geometry: the extended frame's tile size, the
+// clip limit in counts and the three fp32 scales the kernels take by value (include/mi355_imgfilter.h, "local contrast")
+static int clahe_plan(int w, int h, int nframes, double clip_limit, int tiles_x, int tiles_y, ClaheGeom* g)
+{
+    static_assert(MI355_MAX_CLAHE_TILES == kClaheMaxTiles, "the header's limit is the kernels' limit");
+    if (!valid_sizes(w, h, nframes) || tiles_x < 1 || tiles_x > MI355_MAX_CLAHE_TILES || tiles_y < 1 ||
+        tiles_y > MI355_MAX_CLAHE_TILES || !std::isfinite(clip_limit))
+        return MI355_ERR_BAD_ARG;
+    // OpenCV's quirk: when either dimension fails to divide, both are padded, the dividing one by a whole tiles_x / _y
+    const bool divides = w % tiles_x == 0 && h % tiles_y == 0;
+    const int64_t ew = divides ? w : (int64_t)w + (tiles_x - w % tiles_x);
+    const int64_t eh = divides ? h : (int64_t)h + (tiles_y - h % tiles_y);
+    if (ew * eh >= (1ll << 31))
+        return MI355_ERR_BAD_ARG;
+    if (ew - w > w - 1 || eh - h > h - 1)
+        return MI355_ERR_UNSUPPORTED;  // one reflection cannot serve the pad
+    const int tw = (int)(ew / tiles_x), th = (int)(eh / tiles_y), tot = tw * th;
+    int cl = 0;
+    if (clip_limit > 0.0) {
+        const double c = clip_limit * (double)tot / 256.0;
+        cl = c >= (double)tot ? tot : (int)c;  // capped at tot: no bin exceeds it
+        cl = cl < 1 ? 1 : cl;
+    }
+    if (g)
+        *g = {w, h, tiles_x, tiles_y, tw, th, cl, 255.0f / (float)tot, 1.0f / (float)tw, 1.0f / (float)th};
+    return MI355_OK;
+}
+
+// CLAHE up to the tables: the pooled tile histograms, zeroed in-stream, the histogram launch and the table launch into
+// d_luts.  Only the first call for a larger frames x tiles count allocates (and synchronises, in ensure()).
+static int clahe_tables(mi355_ctx* ctx, const uint8_t* in, uint8_t* d_luts, const ClaheGeom& g, int nframes)
+{
+    const size_t nhist = (size_t)nframes * (size_t)(g.tiles_x * g.tiles_y) * 256 * sizeof(uint32_t);
+    uint32_t* hist = static_cast<uint32_t*>(ctx->d_hist.p);
+    HIP_TRY(ctx, hipMemsetAsync(hist, 0, nhist, ctx->stream));
+    HIP_TRY(ctx, launch_clahe_hist(ctx->stream, in, hist, g, nframes));
+    HIP_TRY(ctx, launch_clahe_table(ctx->stream, hist, d_luts, g, nframes));
+    return MI355_OK;
+}
+
+// the pooled scratch of a CLAHE call: 1 KiB of histogram and 256 B of table per (frame, tile)
+static int clahe_scratch(mi355_ctx* ctx, const ClaheGeom& g, int nframes)
+{
+    const size_t ntiles = (size_t)nframes * (size_t)(g.tiles_x * g.tiles_y);
+    const int rc = ensure(ctx, ctx->d_hist, ntiles * 256 * sizeof(uint32_t));
+    return rc == MI355_OK ? ensure(ctx, ctx->d_lut, ntiles * 256) : rc;
+}
+
+// the one argument check of the device-resident CLAHE calls; d_out takes the frames, or with `luts` the tables (256 bytes
+// per frame and tile, 4-byte aligned)
+static int clahe_check_dev(mi355_ctx* ctx, const void* d_in, const void* d_out, bool luts, int w, int h, int nframes,
+                           double clip_limit, int tiles_x, int tiles_y, ClaheGeom* g)
+{
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    const int rc = clahe_plan(w, h, nframes, clip_limit, tiles_x, tiles_y, g);
+    if (rc != MI355_OK)
+        return rc;
+    const size_t nin = frame_bytes(w, h, nframes, 1);
+    const size_t nout = luts ? (size_t)nframes * (size_t)(tiles_x * tiles_y) * 256 : nin;
+    if ((luts && (reinterpret_cast<uintptr_t>(d_out) & 3u)) || overlap(d_in, nin, d_out, nout))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return clahe_scratch(ctx, *g, nframes);
+}
+
+MI355_API int mi355_clahe_check(int w, int h, int nframes, double clip_limit, int tiles_x, int tiles_y)
+{
+    return clahe_plan(w, h, nframes, clip_limit, tiles_x, tiles_y, nullptr);
+}
+
+MI355_API int mi355_clahe_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes,
+                                    double clip_limit, int tiles_x, int tiles_y)
+{
+    ClaheGeom g;
+    int rc = clahe_check_dev(ctx, d_in, d_out, false, w, h, nframes, clip_limit, tiles_x, tiles_y, &g);
+    if (rc != MI355_OK)
+        return rc;
+    uint8_t* luts = static_cast<uint8_t*>(ctx->d_lut.p);
+    rc = clahe_tables(ctx, static_cast<const uint8_t*>(d_in), luts, g, nframes);
+    if (rc != MI355_OK)
+        return rc;
+    HIP_TRY(ctx, launch_clahe_apply(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), luts, g,
+                                    nframes));
+    return MI355_OK;
+}
+
+MI355_API int mi355_clahe_luts_gray8_dev(mi355_ctx* ctx, const void* d_in, uint8_t* d_luts, int w, int h, int nframes,
+                                         double clip_limit, int tiles_x, int tiles_y)
+{
+    ClaheGeom g;
+    const int rc = clahe_check_dev(ctx, d_in, d_luts, true, w, h, nframes, clip_limit, tiles_x, tiles_y, &g);
+    if (rc != MI355_OK)
+        return rc;
+    return clahe_tables(ctx, static_cast<const uint8_t*>(d_in), d_luts, g, nframes);
+}
+
+MI355_API int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
+                                        double clip_limit, int tiles_x, int tiles_y, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    ClaheGeom g;
+    int rc = clahe_plan(w, h, nframes, clip_limit, tiles_x, tiles_y, &g);
+    if (rc != MI355_OK)
+        return rc;
+    HostIO io;
+    rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
+    if (rc == MI355_OK)
+        rc = clahe_scratch(ctx, g, nframes);  // sized outside the timed write/kernel/read window
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+        return mi355_clahe_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, clip_limit, tiles_x, tiles_y);
+    });
+}
+
 MI355_API int mi355_gray_rgba8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h,
                                    int nframes)
 {

@@ -20,6 +20,7 @@
 //   apply_kernel  the frame's LUT in LDS, one ds_read_u8 per pixel; 16-byte non-temporal stores aligned on the output,
 //                 16-byte loads at whatever alignment the input then has, head and tail bytes as in hist_kernel.
 #include "common.hpp"
+#include "hist_common.hpp"
 #include "kernels.hpp"
 #include "tile_common.hpp"
 
@@ -34,59 +35,7 @@ constexpr int kHWaves = kHThreads / kWave;
 constexpr int kHistVec = 16;  // 16-byte vectors per thread of hist_kernel: 64 KiB per block, 256 atomics per flush
 constexpr int kApplyVec = 8;  // per thread of apply_kernel: 32 KiB per block
 
-
-// where the 16-byte body of a frame starts, relative to the frame, for a frame at address a of npx bytes
-__device__ __forceinline__ uint32_t head_bytes(uintptr_t a, uint32_t npx)
-{
-    const uint32_t hb = (uint32_t)((16u - (a & 15u)) & 15u);
-    return hb < npx ? hb : npx;
-}
-
-__device__ __forceinline__ void lds_add(uint32_t* hw, uint32_t bin, uint32_t n)
-{
-    __hip_atomic_fetch_add(hw + bin, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__device__ __forceinline__ void count_dword(uint32_t* hw, uint32_t d)
-{
-    const uint32_t b = d & 0xFFu;
-    if (d == b * 0x01010101u) {
-        lds_add(hw, b, 4);
-    } else {
-        lds_add(hw, b, 1);
-        lds_add(hw, (d >> 8) & 0xFFu, 1);
-        lds_add(hw, (d >> 16) & 0xFFu, 1);
-        lds_add(hw, d >> 24, 1);
-    }
-}
-
-// count the 16 bytes of v (valid lanes only) into the wave's LDS histogram hw
-__device__ __forceinline__ void count_vec(uint32_t* hw, const u32x4& v, bool valid)
-{
-    const uint32_t b = v.x & 0xFFu, rep = b * 0x01010101u;
-    const bool uni = valid && v.x == rep && v.y == rep && v.z == rep && v.w == rep;
-    const uint64_t um = __ballot(uni);
-    if (um) {
-        // the lanes whose 16 bytes all hold the first uniform lane's value: one add for all of them
-        const int leader = __ffsll((unsigned long long)um) - 1;
-        const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane((int)b, leader);
-        const uint64_t m = __ballot(uni && b == lb);
-        if ((int)__lane_id() == leader)
-            lds_add(hw, lb, 16u * (uint32_t)__popcll(m));
-        if ((m >> __lane_id()) & 1u)
-            return;
-    }
-    if (!valid)
-        return;
-    if (uni) {
-        lds_add(hw, b, 16);
-        return;
-    }
-    count_dword(hw, v.x);
-    count_dword(hw, v.y);
-    count_dword(hw, v.z);
-    count_dword(hw, v.w);
-}
+// head_bytes, lds_add, count_dword, count_vec: hist_common.hpp (shared with clahe.hip)
 
 __global__ __launch_bounds__(kHThreads) void hist_kernel(const uint8_t* __restrict__ in, uint32_t* __restrict__ hist,
                                                          uint32_t npx, uint32_t tiles)

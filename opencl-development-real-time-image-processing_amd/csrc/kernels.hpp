@@ -127,6 +127,28 @@ hipError_t launch_hist_table(hipStream_t stream, const uint32_t* d_hist, uint8_t
 hipError_t launch_lut_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, const uint8_t* d_lut, int w, int h,
                             int nframes);
 
+// CLAHE of single-channel frames (clahe.hip; semantics: include/mi355_imgfilter.h, "local contrast").  ClaheGeom is the
+// call's geometry, computed once on the host: the tile size tw x th of the extended frame (tiles_x tw >= w, tiles_y th >=
+// h, each pad served by one reflection, tiles_x tw tiles_y th < 2^31), the clip limit in counts (0 = none) and the three
+// fp32 scales 255 / (tw th), 1 / tw and 1 / th, which go to the kernels by value.
+//   launch_clahe_hist   ADDS every tile's 256 bin counts into d_hist[(f tiles + tile) * 256 ..] (tile = j tiles_x + i;
+//                       the caller zeroes it first; 16-byte aligned)
+//   launch_clahe_table  one wave per (frame, tile): clip, redistribute, prefix sum -> d_luts, 256 bytes per tile in the
+//                       same order (4-byte aligned)
+//   launch_clahe_apply  blends the four nearest tiles' table entries per pixel, d_luts 4-byte aligned
+constexpr int kClaheMaxTiles = 16;
+struct ClaheGeom {
+    int w, h, tiles_x, tiles_y;
+    int tw, th;
+    int cl;
+    float lut_scale, inv_tw, inv_th;
+};
+hipError_t launch_clahe_hist(hipStream_t stream, const uint8_t* d_in, uint32_t* d_hist, const ClaheGeom& g, int nframes);
+hipError_t launch_clahe_table(hipStream_t stream, const uint32_t* d_hist, uint8_t* d_luts, const ClaheGeom& g,
+                              int nframes);
+hipError_t launch_clahe_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, const uint8_t* d_luts,
+                              const ClaheGeom& g, int nframes);
+
 // cv::resize of tightly packed 8-bit frames (resize.hip): bpp 4 (RGBA, dword-aligned) or 1 (gray8, any byte alignment);
 // interp 0 nearest, 1 linear (11-bit fixed point; AREA's result at exactly half size), 3 area with integer factors
 // 1 .. kResizeMaxAreaFactor (resize_area_factors says whether a size pair has them; anything else is

@@ -37,6 +37,8 @@ FILTER_BOX, FILTER_BOX_GRAY8 = 48, 49
 MAX_BOX_K = 63
 # cv::adaptiveThreshold(ADAPTIVE_THRESH_MEAN_C) types (mi355_adaptive_threshold_*): cv::THRESH_BINARY / THRESH_BINARY_INV
 ADAPTIVE_BINARY, ADAPTIVE_BINARY_INV = 0, 1
+# CLAHE (mi355_clahe_*): 1 <= tiles_x, tiles_y <= MAX_CLAHE_TILES
+MAX_CLAHE_TILES = 16
 # cv::resize (mi355_resize_*): OpenCV's enum values; AREA only with integer factors 1 .. MAX_AREA_FACTOR
 INTERP_NEAREST, INTERP_LINEAR, INTERP_AREA = 0, 1, 3
 MAX_AREA_FACTOR = 16
@@ -171,6 +173,10 @@ def load_library(path=None):
         "mi355_adaptive_threshold_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double],
         "mi355_adaptive_threshold_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, ctypes.c_double,
                                                    _u64p],
+        "mi355_clahe_check": [_ci, _ci, _ci, ctypes.c_double, _ci, _ci],
+        "mi355_clahe_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, _ci, _ci],
+        "mi355_clahe_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, ctypes.c_double, _ci, _ci, _u64p],
+        "mi355_clahe_luts_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, _ci, _ci],
         "mi355_synth_rgba8_dev": [_vp, _vp, _ci, _ci, _ci, _ci, ctypes.c_uint32, _ci],
         "mi355_checksum_dev": [_vp, _vp, ctypes.c_size_t, ctypes.c_uint64, _u64p],
         "mi355_stream_copy_dev": [_vp, _vp, _vp, ctypes.c_size_t],
@@ -346,6 +352,12 @@ def adaptive_threshold_check(w, h, nframes=1, max_value=255, type=ADAPTIVE_BINAR
     with these values returns before any device work."""
     return load_library().mi355_adaptive_threshold_check(int(w), int(h), int(nframes), int(max_value), int(type),
                                                          int(block), float(delta))
+
+
+def clahe_check(w, h, nframes=1, clip_limit=40.0, tiles_x=8, tiles_y=8):
+    """mi355_clahe_check, a pure host function: the code (0 ok, -1 bad argument, -4 a pad one reflection cannot serve) a
+    CLAHE call with these values returns before any device work."""
+    return load_library().mi355_clahe_check(int(w), int(h), int(nframes), float(clip_limit), int(tiles_x), int(tiles_y))
 
 
 def device_count():
@@ -552,6 +564,20 @@ class Context:
             self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, int(max_value), int(type),
             int(block), float(delta), prof if profile else None)
         _check("mi355_adaptive_threshold_gray8_batched", rc, self._h)
+        out = out[0] if one else out
+        return (out, list(prof)) if profile else out
+
+    def clahe_gray8(self, y, clip_limit=40.0, tiles_x=8, tiles_y=8, profile=False):
+        """cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply() of (h, w) / (n, h, w) single-channel frames
+        (mi355_clahe_gray8_batched); the defaults are OpenCV's."""
+        frames, one = self._frames("clahe_gray8", y, 1)
+        n, h, w = frames.shape
+        out = np.empty((n, h, w), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_clahe_gray8_batched(
+            self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, float(clip_limit), int(tiles_x),
+            int(tiles_y), prof if profile else None)
+        _check("mi355_clahe_gray8_batched", rc, self._h)
         out = out[0] if one else out
         return (out, list(prof)) if profile else out
 
@@ -781,6 +807,19 @@ class Context:
                                                           int(nframes), int(max_value), int(type), int(block),
                                                           float(delta))
         _check("mi355_adaptive_threshold_gray8_dev", rc, self._h)
+
+    def clahe_gray8_dev(self, d_in, d_out, w, h, nframes, clip_limit=40.0, tiles_x=8, tiles_y=8):
+        """mi355_clahe_gray8_dev: CLAHE of nframes gray8 frames at d_in to d_out, no synchronisation."""
+        rc = self._lib.mi355_clahe_gray8_dev(self._h, _vp(int(d_in)), _vp(int(d_out)), int(w), int(h), int(nframes),
+                                             float(clip_limit), int(tiles_x), int(tiles_y))
+        _check("mi355_clahe_gray8_dev", rc, self._h)
+
+    def clahe_luts_gray8_dev(self, d_in, d_luts, w, h, nframes, clip_limit=40.0, tiles_x=8, tiles_y=8):
+        """mi355_clahe_luts_gray8_dev: the nframes x tiles_y x tiles_x x 256 table bytes of a CLAHE call to d_luts (4-byte
+        aligned), no synchronisation."""
+        rc = self._lib.mi355_clahe_luts_gray8_dev(self._h, _vp(int(d_in)), _vp(int(d_luts)), int(w), int(h),
+                                                  int(nframes), float(clip_limit), int(tiles_x), int(tiles_y))
+        _check("mi355_clahe_luts_gray8_dev", rc, self._h)
 
     def hist_gray8_dev(self, d_in, d_hist, w, h, nframes):
         """mi355_hist_gray8_dev: nframes x 256 uint32 counts to d_hist (overwritten), no synchronisation."""
