@@ -648,6 +648,99 @@ int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, i
 int mi355_clahe_luts_gray8_dev(mi355_ctx* ctx, const void* d_in, uint8_t* d_luts, int w, int h, int nframes,
                                double clip_limit, int tiles_x, int tiles_y);
 
+/* ---- frames from a decoder or a camera: 8-bit YUV <-> RGBA, cv::cvtColor(COLOR_YUV2RGBA_* / COLOR_RGBA2YUV_*) --------
+ * The video decoder writes NV12 surfaces with a pitch, software decoders write I420, webcams deliver YUY2, and an
+ * encoder wants NV12 or I420 back.  These calls are the first and the last step of a chain that stays on the device:
+ * mi355_yuv_to_rgba8_dev -> mi355_filter_dev ... -> mi355_rgba8_to_yuv_dev, and mi355_yuv_to_gray8_dev in front of every
+ * MI355_FILTER_*_GRAY8 id.  Entry points of their own, not filter ids and not a context input format.
+ * OpenCV is not installed where this library is built and tested, so THE ARITHMETIC BELOW IS THE CONTRACT.  The BT601
+ * constants restate OpenCV's color_yuv code from memory; nobody has compared the result with an OpenCV build here.
+ *   geometry  One rule serves a cv::Mat and a decoder surface alike.  A frame is one block of bytes:
+ *               pitch  the luma row stride in bytes; 0 = tight: w, or 2 * w for the packed layouts
+ *               rows   the number of luma rows the surface holds; 0 = h
+ *               frames follow each other at mi355_yuv_frame_bytes(layout, w, h, pitch, rows)
+ *             4:2:0 (NV12, NV21, I420, YV12): Y(x, y) is at y * pitch + x; the chroma area starts at rows * pitch.
+ *               semi-planar: the pair of pixel (x, y) is at rows * pitch + (y / 2) * pitch + 2 * (x / 2)
+ *               planar:      the first chroma plane has pitch / 2 bytes per row and rows / 2 rows, the sample of pixel
+ *                            (x, y) at (y / 2) * (pitch / 2) + x / 2 in it; the second plane follows it directly
+ *               frame bytes = pitch * rows * 3 / 2.  With pitch = w and rows = h this is exactly OpenCV's
+ *               (h * 3 / 2, w) CV_8UC1 layout; a rocDecode / VA-API surface is (its pitch, its aligned height).
+ *             packed (YUY2, UYVY): row y is at y * pitch, pixel pair (x, x + 1) at 2 * x in it; frame bytes = pitch * rows.
+ *             RGBA and gray8 frames are tightly packed as everywhere else: (nframes, h, w, 4) and (nframes, h, w).
+ *   accepted  w, h, nframes as every call here accepts them; w even; for 4:2:0 also h and rows even, and for the planar
+ *             layouts pitch even; pitch >= w (>= 2 * w packed); rows >= h; pitch * rows * nframes <= 1.2e11.  Anything
+ *             else, an unknown layout or standard included, is MI355_ERR_BAD_ARG.  The encode with a packed layout is
+ *             MI355_ERR_UNSUPPORTED.
+ *   pointers  d_rgba is dword-aligned (the RGBA rule above); d_yuv and d_gray may have ANY byte alignment, and so may
+ *             pitch.  Null pointers and ranges that overlap (the YUV side counted as nframes * frame bytes) are
+ *             MI355_ERR_BAD_ARG.  All argument checks come before any device work.
+ *   decode    int32 throughout; >> is an arithmetic shift (floor); sat clamps to 0 .. 255:
+ *               u = U - 128;  v = V - 128;  y = max(0, Y - YOFF) * CY
+ *               R = sat((y + 2^19 + CVR*v) >> 20)
+ *               G = sat((y + 2^19 + CVG*v + CUG*u) >> 20)
+ *               B = sat((y + 2^19 + CUB*u) >> 20);  A = 255
+ *             The chroma sample of a 2 x 2 block (4:2:0) or of a pixel pair (packed) serves all of its pixels; nothing
+ *             is interpolated.
+ *   encode    Y = sat((CRY*r + CGY*g + CBY*b + 2^19 + (YOFF << 20)) >> 20)     for every pixel
+ *             U = sat((CRU*r + CGU*g + CBU*b + 2^19 + (128 << 20)) >> 20)
+ *             V = sat((CBU*r + CGV*g + CBV*b + 2^19 + (128 << 20)) >> 20)
+ *             U and V are taken from the TOP-LEFT pixel of each 2 x 2 block: OpenCV's rule, not a mean.  Alpha is
+ *             ignored.  OpenCV offers the encode for I420 / YV12 only; the NV12 / NV21 encode here is the same
+ *             arithmetic stored in the interleaved layout.  Only bytes of pixels are written: the padding of a pitched
+ *             surface (columns past w, rows past h) keeps what it held.
+ *   constants                  YOFF  CY       CVR      CVG      CUG      CUB
+ *               BT601          16    1220542  1673527  -852492  -409993  2116026
+ *               BT709          16    1220945  1879825  -558796  -223607  2215014
+ *               BT601_FULL     0     1048576  1470104  -748826  -360853  1858077
+ *                              CRY     CGY     CBY     CRU      CGU      CBU     CGV      CBV
+ *               BT601          269484  528482  102760  -155188  -305135  460324  -385875  -74448
+ *               BT709          191455  644067  65019   -105533  -355018  460551  -418321  -42230
+ *               BT601_FULL     313524  615514  119538  -176932  -347356  524288  -439026  -85262
+ *             BT601 is OpenCV's: (int)(c * 2^20) of its three-decimal 1.164, 1.596, -0.813, -0.391, 2.018 and its own
+ *             encode integers — the bit-exact contract with cv::cvtColor.  The other two rows are lround(c * 2^20), in
+ *             fp64, of the exact matrix of (Kr, Kb) = (0.2126, 0.0722) and (0.299, 0.114), Kg = 1 - Kr - Kb, with the
+ *             range factors sy = 219/255, sc = 224/255 (BT709) and sy = sc = 1 (BT601_FULL):
+ *               CY = 1/sy;  CVR = 2(1-Kr)/sc;  CUB = 2(1-Kb)/sc;  CVG = -2Kr(1-Kr)/Kg/sc;  CUG = -2Kb(1-Kb)/Kg/sc
+ *               CRY = Kr*sy;  CGY = Kg*sy;  CBY = Kb*sy;  CBU = sc/2
+ *               CRU = -Kr/(2(1-Kb))*sc;  CGU = -Kg/(2(1-Kb))*sc;  CGV = -Kg/(2(1-Kr))*sc;  CBV = -Kb/(2(1-Kr))*sc
+ *             Every intermediate stays below 2^31 in magnitude for every byte triple and every row of the table.
+ *   mi355_yuv_frame_bytes   pure host function: the bytes from one frame to the next, 0 for arguments the calls reject.
+ *   mi355_yuv_check         pure host function: the code a call with these values returns before any device work
+ *                           (encode != 0: the RGBA -> YUV direction).
+ *   mi355_yuv_to_rgba8_dev, mi355_rgba8_to_yuv_dev   the rules of mi355_filter_dev: one launch on the context's stream,
+ *                           no synchronisation, no allocation, table or scratch (the constants go by value), so the first
+ *                           call a fresh context makes can be captured into a hipGraph.
+ *   mi355_yuv_to_gray8_dev  cv::cvtColor(COLOR_YUV2GRAY_*): the Y bytes unchanged, with no range expansion, packed into
+ *                           (nframes, h, w) — the feeder of every MI355_FILTER_*_GRAY8 id.  The same rules.
+ *   mi355_yuv_to_rgba8_batched, mi355_rgba8_to_yuv_batched   host buffers: H2D, the launch, D2H through the context's
+ *                           pooled buffers, each side sized by its own bytes; prof_ns (may be NULL) gets the six
+ *                           timestamps of mi355_filter_batched.  The padding of a pitched host result is zero.  The
+ *                           context's input format describes the frames of the filter calls, not these: under
+ *                           MI355_INPUT_BGR both return MI355_ERR_UNSUPPORTED.
+ * Not offered: a YUV input format of the filter calls, 10-bit (P010) and 4:4:4 frames, chroma interpolation, a mean-of-four
+ * chroma on encode, one pointer per plane, streamed and group forms. */
+#define MI355_YUV_NV12 0 /* Y plane, then rows of interleaved (U, V) pairs     cv::COLOR_YUV2RGBA_NV12 */
+#define MI355_YUV_NV21 1 /* Y plane, then rows of interleaved (V, U) pairs     cv::COLOR_YUV2RGBA_NV21 */
+#define MI355_YUV_I420 2 /* Y plane, U plane, V plane                          cv::COLOR_YUV2RGBA_I420 / COLOR_RGBA2YUV_I420 */
+#define MI355_YUV_YV12 3 /* Y plane, V plane, U plane                          cv::COLOR_YUV2RGBA_YV12 / COLOR_RGBA2YUV_YV12 */
+#define MI355_YUV_YUY2 4 /* packed Y0 U Y1 V, 2 bytes per pixel (decode only)  cv::COLOR_YUV2RGBA_YUY2 */
+#define MI355_YUV_UYVY 5 /* packed U Y0 V Y1, 2 bytes per pixel (decode only)  cv::COLOR_YUV2RGBA_UYVY */
+#define MI355_YUV_BT601 0      /* limited range; OpenCV's constants, the bit-exact contract with cv::cvtColor */
+#define MI355_YUV_BT709 1      /* limited range, HD video */
+#define MI355_YUV_BT601_FULL 2 /* full range (JFIF / MJPEG cameras) */
+size_t mi355_yuv_frame_bytes(int layout, int w, int h, int pitch, int rows);
+int mi355_yuv_check(int layout, int standard, int w, int h, int nframes, int pitch, int rows, int encode);
+int mi355_yuv_to_rgba8_dev(mi355_ctx* ctx, const void* d_yuv, void* d_rgba, int w, int h, int nframes, int layout,
+                           int standard, int pitch, int rows);
+int mi355_rgba8_to_yuv_dev(mi355_ctx* ctx, const void* d_rgba, void* d_yuv, int w, int h, int nframes, int layout,
+                           int standard, int pitch, int rows);
+int mi355_yuv_to_gray8_dev(mi355_ctx* ctx, const void* d_yuv, void* d_gray, int w, int h, int nframes, int layout,
+                           int pitch, int rows);
+int mi355_yuv_to_rgba8_batched(mi355_ctx* ctx, const uint8_t* yuv, uint8_t* rgba, int w, int h, int nframes, int layout,
+                               int standard, int pitch, int rows, uint64_t prof_ns[6]);
+int mi355_rgba8_to_yuv_batched(mi355_ctx* ctx, const uint8_t* rgba, uint8_t* yuv, int w, int h, int nframes, int layout,
+                               int standard, int pitch, int rows, uint64_t prof_ns[6]);
+
 /* Synthetic frames: px = hash(seed, first_frame + f, y, x), A = 255; mode 1 = smooth
  * gradient + 4-bit noise, mode 2 = flat 64 x 64 patches (constant windows: the content that sends the
  * exact-by-exception kernels down their exception path), mode 3 = gray noise (r = g = b: every pixel on the

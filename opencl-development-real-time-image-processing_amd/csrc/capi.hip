@@ -1614,6 +1614,150 @@ MI355_API int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8
     });
 }
 
+// ---- YUV frames ------------------------------------------------------------------------------------------------------
+// The integers of the header's table, one row per MI355_YUV_BT* standard.
+static const YuvDecodeCoef kYuvDecode[3] = {
+    {16, 1220542, 1673527, -852492, -409993, 2116026},  // BT601: OpenCV's three-decimal constants
+    {16, 1220945, 1879825, -558796, -223607, 2215014},  // BT709
+    {0, 1048576, 1470104, -748826, -360853, 1858077},   // BT601_FULL
+};
+static const YuvEncodeCoef kYuvEncode[3] = {
+    {269484, 528482, 102760, -155188, -305135, 460324, -385875, -74448, (1 << 19) + (16 << 20)},
+    {191455, 644067, 65019, -105533, -355018, 460551, -418321, -42230, (1 << 19) + (16 << 20)},
+    {313524, 615514, 119538, -176932, -347356, 524288, -439026, -85262, 1 << 19},
+};
+
+// The value checks of every YUV call and, when they pass, the surface with pitch and rows resolved.
+static int yuv_plan(int layout, int standard, int w, int h, int nframes, int pitch, int rows, int encode, YuvFrames* out)
+{
+    if (layout < MI355_YUV_NV12 || layout > MI355_YUV_UYVY || standard < MI355_YUV_BT601 ||
+        standard > MI355_YUV_BT601_FULL || !valid_sizes(w, h, nframes) || (w & 1) || pitch < 0 || rows < 0)
+        return MI355_ERR_BAD_ARG;
+    const bool packed = yuv_layout_packed(layout);
+    const bool planar = layout == MI355_YUV_I420 || layout == MI355_YUV_YV12;
+    const int64_t tight = packed ? 2 * (int64_t)w : (int64_t)w;
+    if (tight > 0x7FFFFFFF)
+        return MI355_ERR_BAD_ARG;
+    const YuvFrames s = {layout, w, h, nframes, pitch ? pitch : (int)tight, rows ? rows : h};
+    if (s.pitch < tight || s.rows < h || (!packed && ((h & 1) || (s.rows & 1))) || (planar && (s.pitch & 1)))
+        return MI355_ERR_BAD_ARG;
+    // the surfaces of a call, padding included, stay below 2^37 bytes: far beyond the HBM, and no size_t sum wraps
+    if ((double)s.pitch * (double)s.rows * (double)nframes > 1.2e11)
+        return MI355_ERR_BAD_ARG;
+    if (encode && packed)
+        return MI355_ERR_UNSUPPORTED;
+    if (out)
+        *out = s;
+    return MI355_OK;
+}
+
+// the one argument check of the three device-resident YUV calls; `other_bpp` is 4 (RGBA) or 1 (gray8)
+static int yuv_check_dev(mi355_ctx* ctx, const void* d_yuv, const void* d_other, int other_bpp, bool yuv_is_input,
+                         int layout, int standard, int w, int h, int nframes, int pitch, int rows, YuvFrames* s)
+{
+    if (!ctx || !d_yuv || !d_other)
+        return MI355_ERR_BAD_ARG;
+    const int rc = yuv_plan(layout, standard, w, h, nframes, pitch, rows, yuv_is_input ? 0 : 1, s);
+    if (rc != MI355_OK)
+        return rc;
+    const size_t nyuv = yuv_frame_size(*s) * (size_t)nframes, nother = frame_bytes(w, h, nframes, other_bpp);
+    const bool bad = yuv_is_input ? bad_dev_io(d_yuv, nyuv, 1, d_other, nother, other_bpp)
+                                  : bad_dev_io(d_other, nother, other_bpp, d_yuv, nyuv, 1);
+    if (bad)
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return MI355_OK;
+}
+
+MI355_API size_t mi355_yuv_frame_bytes(int layout, int w, int h, int pitch, int rows)
+{
+    YuvFrames s;
+    return yuv_plan(layout, MI355_YUV_BT601, w, h, 1, pitch, rows, 0, &s) == MI355_OK ? yuv_frame_size(s) : 0;
+}
+
+MI355_API int mi355_yuv_check(int layout, int standard, int w, int h, int nframes, int pitch, int rows, int encode)
+{
+    return yuv_plan(layout, standard, w, h, nframes, pitch, rows, encode, nullptr);
+}
+
+MI355_API int mi355_yuv_to_rgba8_dev(mi355_ctx* ctx, const void* d_yuv, void* d_rgba, int w, int h, int nframes,
+                                     int layout, int standard, int pitch, int rows)
+{
+    YuvFrames s;
+    const int rc = yuv_check_dev(ctx, d_yuv, d_rgba, 4, true, layout, standard, w, h, nframes, pitch, rows, &s);
+    if (rc != MI355_OK)
+        return rc;
+    HIP_TRY(ctx, launch_yuv_to_rgba(ctx->stream, static_cast<const uint8_t*>(d_yuv), static_cast<uint8_t*>(d_rgba), s,
+                                    kYuvDecode[standard]));
+    return MI355_OK;
+}
+
+MI355_API int mi355_rgba8_to_yuv_dev(mi355_ctx* ctx, const void* d_rgba, void* d_yuv, int w, int h, int nframes,
+                                     int layout, int standard, int pitch, int rows)
+{
+    YuvFrames s;
+    const int rc = yuv_check_dev(ctx, d_yuv, d_rgba, 4, false, layout, standard, w, h, nframes, pitch, rows, &s);
+    if (rc != MI355_OK)
+        return rc;
+    HIP_TRY(ctx, launch_rgba_to_yuv(ctx->stream, static_cast<const uint8_t*>(d_rgba), static_cast<uint8_t*>(d_yuv), s,
+                                    kYuvEncode[standard]));
+    return MI355_OK;
+}
+
+MI355_API int mi355_yuv_to_gray8_dev(mi355_ctx* ctx, const void* d_yuv, void* d_gray, int w, int h, int nframes,
+                                     int layout, int pitch, int rows)
+{
+    YuvFrames s;
+    const int rc = yuv_check_dev(ctx, d_yuv, d_gray, 1, true, layout, MI355_YUV_BT601, w, h, nframes, pitch, rows, &s);
+    if (rc != MI355_OK)
+        return rc;
+    HIP_TRY(ctx, launch_yuv_to_gray(ctx->stream, static_cast<const uint8_t*>(d_yuv), static_cast<uint8_t*>(d_gray), s));
+    return MI355_OK;
+}
+
+// The host-buffer form of both directions: the pooled buffers sized by each side's own bytes, then the round trip.  The
+// context's input format describes the frames of the filter calls, not these: under MI355_INPUT_BGR nothing is guessed.
+static int yuv_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes, int layout,
+                       int standard, int pitch, int rows, bool encode, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    YuvFrames s;
+    int rc = yuv_plan(layout, standard, w, h, nframes, pitch, rows, encode ? 1 : 0, &s);
+    if (rc != MI355_OK)
+        return rc;
+    if (ctx->input_format == MI355_INPUT_BGR)
+        return MI355_ERR_UNSUPPORTED;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nyuv = yuv_frame_size(s) * (size_t)nframes, nrgba = frame_bytes(w, h, nframes, 4);
+    const size_t in_bytes = encode ? nrgba : nyuv, out_bytes = encode ? nyuv : nrgba;
+    rc = ensure(ctx, ctx->d_in, in_bytes);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_out, out_bytes);
+    if (rc != MI355_OK)
+        return rc;
+    const bool padded = encode && (s.pitch != w || s.rows != h);
+    return timed_roundtrip(ctx, ctx->d_in.p, in, in_bytes, out, out_bytes, prof_ns, [&] {
+        if (!encode)
+            return mi355_yuv_to_rgba8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, layout, standard, pitch, rows);
+        if (padded)  // the kernel never writes padding; the host gets zeros there, not the pool's previous content
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_out.p, 0, out_bytes, ctx->stream));
+        return mi355_rgba8_to_yuv_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, layout, standard, pitch, rows);
+    });
+}
+
+MI355_API int mi355_yuv_to_rgba8_batched(mi355_ctx* ctx, const uint8_t* yuv, uint8_t* rgba, int w, int h, int nframes,
+                                         int layout, int standard, int pitch, int rows, uint64_t prof_ns[6])
+{
+    return yuv_batched(ctx, yuv, rgba, w, h, nframes, layout, standard, pitch, rows, false, prof_ns);
+}
+
+MI355_API int mi355_rgba8_to_yuv_batched(mi355_ctx* ctx, const uint8_t* rgba, uint8_t* yuv, int w, int h, int nframes,
+                                         int layout, int standard, int pitch, int rows, uint64_t prof_ns[6])
+{
+    return yuv_batched(ctx, rgba, yuv, w, h, nframes, layout, standard, pitch, rows, true, prof_ns);
+}
+
 MI355_API int mi355_gray_rgba8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h,
                                    int nframes)
 {

@@ -220,6 +220,29 @@ hipError_t launch_synth(hipStream_t stream, uint8_t* d_out, int w, int h, int nf
 // packed BGR (3 B/px) -> RGBA (A = 255), cv::cvtColor(BGR2RGBA)
 hipError_t launch_bgr_to_rgba(hipStream_t stream, const uint8_t* d_bgr, uint8_t* d_rgba, size_t npx);
 
+// 8-bit YUV frames <-> RGBA and their luma planes (yuv.hip; semantics: include/mi355_imgfilter.h, "frames from a decoder
+// or a camera").  YuvFrames is a call's surface with pitch and rows resolved (never 0) and checked by the caller: layout
+// 0 NV12, 1 NV21, 2 I420, 3 YV12 (4:2:0: w, h, rows even, planar pitch even), 4 YUY2, 5 UYVY (packed, 2 bytes per pixel).
+// The coefficients go to the kernels by value; ybias = 2^19 + (YOFF << 20).  d_rgba is dword-aligned; d_yuv and d_gray
+// take any byte alignment.  One launch each; no table, no scratch, no allocation.  Only pixel bytes are stored: the
+// padding of a pitched surface is never written.  launch_rgba_to_yuv takes the 4:2:0 layouts only.
+struct YuvFrames {
+    int layout, w, h, nframes, pitch, rows;
+};
+struct YuvDecodeCoef {
+    int yoff, cy, cvr, cvg, cug, cub;
+};
+struct YuvEncodeCoef {
+    int cry, cgy, cby, cru, cgu, cbu, cgv, cbv, ybias;
+};
+inline bool yuv_layout_packed(int layout) { return layout >= 4; }
+size_t yuv_frame_size(const YuvFrames& s);  // bytes from one frame to the next
+hipError_t launch_yuv_to_rgba(hipStream_t stream, const uint8_t* d_yuv, uint8_t* d_rgba, const YuvFrames& s,
+                              const YuvDecodeCoef& c);
+hipError_t launch_rgba_to_yuv(hipStream_t stream, const uint8_t* d_rgba, uint8_t* d_yuv, const YuvFrames& s,
+                              const YuvEncodeCoef& c);
+hipError_t launch_yuv_to_gray(hipStream_t stream, const uint8_t* d_yuv, uint8_t* d_gray, const YuvFrames& s);
+
 // streaming device-to-device copy (non-temporal, 16 B/lane): the on-box "read N + write N bytes" ceiling
 hipError_t launch_stream_copy(hipStream_t stream, const uint8_t* d_src, uint8_t* d_dst, size_t nbytes);
 

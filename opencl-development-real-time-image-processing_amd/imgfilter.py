@@ -48,6 +48,9 @@ BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
 MAX_WARP_SIZE = 32766
 # cv::remap (mi355_remap_*): FIXED = int16 (sx, sy) pairs + uint16 fy*32+fx (cv::convertMaps), FLOAT = float x and y planes
 MAP_FIXED, MAP_FLOAT = 0, 1
+# YUV frames (mi355_yuv_*): the layouts (YUY2 and UYVY decode only) and the conversion standards
+YUV_NV12, YUV_NV21, YUV_I420, YUV_YV12, YUV_YUY2, YUV_UYVY = 0, 1, 2, 3, 4, 5
+YUV_BT601, YUV_BT709, YUV_BT601_FULL = 0, 1, 2
 GAUSS_FAST, GAUSS_EXACT = 0, 1
 INPUT_RGBA, INPUT_BGR = 0, 1
 IMPL_AUTO, IMPL_TILE, IMPL_MFMA, IMPL_VALU = 0, 1, 2, 3
@@ -177,6 +180,12 @@ def load_library(path=None):
         "mi355_clahe_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, _ci, _ci],
         "mi355_clahe_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, ctypes.c_double, _ci, _ci, _u64p],
         "mi355_clahe_luts_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, _ci, _ci],
+        "mi355_yuv_check": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_yuv_to_rgba8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_rgba8_to_yuv_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_yuv_to_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_yuv_to_rgba8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _u64p],
+        "mi355_rgba8_to_yuv_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _u64p],
         "mi355_synth_rgba8_dev": [_vp, _vp, _ci, _ci, _ci, _ci, ctypes.c_uint32, _ci],
         "mi355_checksum_dev": [_vp, _vp, ctypes.c_size_t, ctypes.c_uint64, _u64p],
         "mi355_stream_copy_dev": [_vp, _vp, _vp, ctypes.c_size_t],
@@ -214,6 +223,9 @@ def load_library(path=None):
             continue  # an older build under MI355_IMGFILTER_LIB
         fn.argtypes = args
         fn.restype = _ci
+    if hasattr(lib, "mi355_yuv_frame_bytes") or path == _LIB:
+        lib.mi355_yuv_frame_bytes.argtypes = [_ci, _ci, _ci, _ci, _ci]
+        lib.mi355_yuv_frame_bytes.restype = ctypes.c_size_t
     lib.mi355_strerror.argtypes = [_ci]
     lib.mi355_strerror.restype = ctypes.c_char_p
     lib.mi355_build_info.argtypes = []
@@ -358,6 +370,19 @@ def clahe_check(w, h, nframes=1, clip_limit=40.0, tiles_x=8, tiles_y=8):
     """mi355_clahe_check, a pure host function: the code (0 ok, -1 bad argument, -4 a pad one reflection cannot serve) a
     CLAHE call with these values returns before any device work."""
     return load_library().mi355_clahe_check(int(w), int(h), int(nframes), float(clip_limit), int(tiles_x), int(tiles_y))
+
+
+def yuv_frame_bytes(layout, w, h, pitch=0, rows=0):
+    """mi355_yuv_frame_bytes, a pure host function: the bytes from one YUV frame to the next (pitch 0 = tight, rows 0 = h),
+    0 for arguments the YUV calls reject."""
+    return int(load_library().mi355_yuv_frame_bytes(int(layout), int(w), int(h), int(pitch), int(rows)))
+
+
+def yuv_check(layout, standard, w, h, nframes=1, pitch=0, rows=0, encode=False):
+    """mi355_yuv_check, a pure host function: the code (0 ok, -1 bad argument, -4 the encode of a packed layout) a YUV
+    call with these values returns before any device work."""
+    return load_library().mi355_yuv_check(int(layout), int(standard), int(w), int(h), int(nframes), int(pitch),
+                                          int(rows), 1 if encode else 0)
 
 
 def device_count():
@@ -579,6 +604,42 @@ class Context:
             int(tiles_y), prof if profile else None)
         _check("mi355_clahe_gray8_batched", rc, self._h)
         out = out[0] if one else out
+        return (out, list(prof)) if profile else out
+
+    # -- frames from a decoder or a camera (mi355_yuv_to_rgba8_batched / mi355_rgba8_to_yuv_batched) -----
+    def yuv_to_rgba8(self, yuv, w, h, layout, standard=YUV_BT601, pitch=0, rows=0, profile=False):
+        """cv::cvtColor(COLOR_YUV2RGBA_*) of whole frames in host memory: `yuv` holds n frames of yuv_frame_bytes(layout,
+        w, h, pitch, rows) bytes each, back to back, in any shape; returns (n, h, w, 4) RGBA with A = 255."""
+        yuv = np.ascontiguousarray(yuv, np.uint8).ravel()
+        fb = yuv_frame_bytes(layout, w, h, pitch, rows)
+        n = yuv.size // fb if fb else 1
+        if fb and (n < 1 or n * fb != yuv.size):
+            raise Mi355Error("yuv_to_rgba8", -1, "expected a whole number of frames of %d bytes" % fb)
+        out = np.empty((n, int(h), int(w), 4), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_yuv_to_rgba8_batched(self._h, yuv.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), int(w),
+                                                  int(h), n, int(layout), int(standard), int(pitch), int(rows),
+                                                  prof if profile else None)
+        _check("mi355_yuv_to_rgba8_batched", rc, self._h)
+        return (out, list(prof)) if profile else out
+
+    def rgba8_to_yuv(self, rgba, layout, standard=YUV_BT601, pitch=0, rows=0, profile=False):
+        """cv::cvtColor(COLOR_RGBA2YUV_I420 / _YV12), and the same arithmetic for NV12 / NV21, of (h, w, 4) / (n, h, w, 4)
+        RGBA frames in host memory (always RGBA, whatever the context's input format): returns (n, frame bytes) uint8,
+        or (frame bytes,) for one frame; the padding of a pitched result is zero."""
+        a = np.ascontiguousarray(rgba, np.uint8)
+        if a.ndim not in (3, 4) or a.shape[-1] != 4:
+            raise Mi355Error("rgba8_to_yuv", -1, "expected (h, w, 4) or (n, h, w, 4) uint8")
+        frames = a[None] if a.ndim == 3 else a
+        n, h, w = frames.shape[:3]
+        fb = yuv_frame_bytes(layout, w, h, pitch, rows)
+        out = np.empty((n, max(fb, 1)), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_rgba8_to_yuv_batched(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n,
+                                                  int(layout), int(standard), int(pitch), int(rows),
+                                                  prof if profile else None)
+        _check("mi355_rgba8_to_yuv_batched", rc, self._h)
+        out = out[0] if a.ndim == 3 else out
         return (out, list(prof)) if profile else out
 
     # -- calls that change the frame size: (frames, out, bpp, w, h, dst_w, dst_h, n, <the call's own>, prof_ns) -----
@@ -842,6 +903,27 @@ class Context:
         no synchronisation."""
         rc = self._lib.mi355_bgr_to_rgba8_dev(self._h, _vp(int(d_bgr)), _vp(int(d_rgba)), int(w), int(h), int(nframes))
         _check("mi355_bgr_to_rgba8_dev", rc, self._h)
+
+    def yuv_to_rgba8_dev(self, d_yuv, d_rgba, w, h, nframes, layout, standard=YUV_BT601, pitch=0, rows=0):
+        """mi355_yuv_to_rgba8_dev: nframes YUV frames at d_yuv (any byte alignment) to RGBA at d_rgba (dword-aligned); one
+        launch, no synchronisation, no allocation."""
+        rc = self._lib.mi355_yuv_to_rgba8_dev(self._h, _vp(int(d_yuv)), _vp(int(d_rgba)), int(w), int(h), int(nframes),
+                                              int(layout), int(standard), int(pitch), int(rows))
+        _check("mi355_yuv_to_rgba8_dev", rc, self._h)
+
+    def rgba8_to_yuv_dev(self, d_rgba, d_yuv, w, h, nframes, layout, standard=YUV_BT601, pitch=0, rows=0):
+        """mi355_rgba8_to_yuv_dev: nframes RGBA frames at d_rgba to 4:2:0 frames at d_yuv (any byte alignment; padding is
+        not written); one launch, no synchronisation, no allocation."""
+        rc = self._lib.mi355_rgba8_to_yuv_dev(self._h, _vp(int(d_rgba)), _vp(int(d_yuv)), int(w), int(h), int(nframes),
+                                              int(layout), int(standard), int(pitch), int(rows))
+        _check("mi355_rgba8_to_yuv_dev", rc, self._h)
+
+    def yuv_to_gray8_dev(self, d_yuv, d_gray, w, h, nframes, layout, pitch=0, rows=0):
+        """mi355_yuv_to_gray8_dev: the luma bytes of nframes YUV frames, unchanged, to tightly packed (n, h, w) planes at
+        d_gray; one launch, no synchronisation, no allocation."""
+        rc = self._lib.mi355_yuv_to_gray8_dev(self._h, _vp(int(d_yuv)), _vp(int(d_gray)), int(w), int(h), int(nframes),
+                                              int(layout), int(pitch), int(rows))
+        _check("mi355_yuv_to_gray8_dev", rc, self._h)
 
     def checksum_dev(self, d_buf, nbytes, index_base=0):
         out = ctypes.c_uint64(0)
