@@ -404,23 +404,8 @@ bool bad_dev_io(const void* d_in, size_t in_bytes, int in_bpp, const void* d_out
            (out_bpp == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u)) || overlap(d_in, in_bytes, d_out, out_bytes);
 }
 
-// EQUALIZE_GRAY8 / OTSU_GRAY8 up to the table: the pooled histograms, zeroed in-stream, the histogram launch and the
-// table launch (into the pooled tables; Otsu's thresholds also to d_thresh when it is not null).  Only the first call
-// for a larger frame count allocates (and synchronises, in ensure()).
-int hist_tables(mi355_ctx* ctx, const uint8_t* in, int32_t* d_thresh, int w, int h, int nframes, bool otsu)
-{
-    int rc = ensure(ctx, ctx->d_hist, (size_t)nframes * 256 * sizeof(uint32_t));
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_lut, (size_t)nframes * 256);
-    if (rc != MI355_OK)
-        return rc;
-    uint32_t* hist = static_cast<uint32_t*>(ctx->d_hist.p);
-    HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)nframes * 256 * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, launch_hist(ctx->stream, in, hist, w, h, nframes));
-    HIP_TRY(ctx, launch_hist_table(ctx->stream, hist, static_cast<uint8_t*>(ctx->d_lut.p), d_thresh, w, h, nframes,
-                                   otsu));
-    return MI355_OK;
-}
+// EQUALIZE_GRAY8 / OTSU_GRAY8 up to the tables in ctx->d_lut; Otsu's thresholds also to d_thresh if not null (below)
+int hist_tables(mi355_ctx* ctx, const uint8_t* in, int32_t* d_thresh, int w, int h, int nframes, bool otsu);
 
 int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int w, int h, int nframes,
                  int k, float sigma)
@@ -1462,6 +1447,36 @@ MI355_API int mi355_adaptive_threshold_gray8_batched(mi355_ctx* ctx, const uint8
     });
 }
 
+// the pooled scratch of the statistics and CLAHE calls: 1 KiB of histogram and 256 B of table per frame or tile (row)
+static int hist_scratch(mi355_ctx* ctx, size_t rows)
+{
+    const int rc = ensure(ctx, ctx->d_hist, rows * 256 * sizeof(uint32_t));
+    return rc == MI355_OK ? ensure(ctx, ctx->d_lut, rows * 256) : rc;
+}
+
+// that scratch with the histograms, ctx->d_hist.p, zeroed in-stream
+static int zeroed_hists(mi355_ctx* ctx, size_t rows)
+{
+    const int rc = hist_scratch(ctx, rows);
+    if (rc == MI355_OK)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_hist.p, 0, rows * 256 * sizeof(uint32_t), ctx->stream));
+    return rc;
+}
+
+namespace {
+int hist_tables(mi355_ctx* ctx, const uint8_t* in, int32_t* d_thresh, int w, int h, int nframes, bool otsu)
+{
+    const int rc = zeroed_hists(ctx, (size_t)nframes);
+    if (rc != MI355_OK)
+        return rc;
+    uint32_t* hist = static_cast<uint32_t*>(ctx->d_hist.p);
+    HIP_TRY(ctx, launch_hist(ctx->stream, in, hist, w, h, nframes));
+    HIP_TRY(ctx, launch_hist_table(ctx->stream, hist, static_cast<uint8_t*>(ctx->d_lut.p), d_thresh, w, h, nframes,
+                                   otsu));
+    return MI355_OK;
+}
+}  // namespace
+
 // the argument checks of the two statistics calls: mi355_filter_dev's, with `nout` bytes of 4-byte aligned output
 static int check_stats_call(mi355_ctx* ctx, const void* d_in, const void* d_out, int w, int h, int nframes, size_t nout)
 {
@@ -1492,9 +1507,7 @@ MI355_API int mi355_otsu_thresholds_gray8_dev(mi355_ctx* ctx, const void* d_in, 
 {
     const size_t nbytes = (size_t)(nframes > 0 ? nframes : 0) * sizeof(int32_t);
     const int rc = check_stats_call(ctx, d_in, d_thresh, w, h, nframes, nbytes);
-    if (rc != MI355_OK)
-        return rc;
-    return hist_tables(ctx, static_cast<const uint8_t*>(d_in), d_thresh, w, h, nframes, true);
+    return rc == MI355_OK ? hist_tables(ctx, static_cast<const uint8_t*>(d_in), d_thresh, w, h, nframes, true) : rc;
 }
 
 // The value checks of every CLAHE call and, when they pass, the call's geometry: the extended frame's tile size, the
@@ -1525,28 +1538,19 @@ static int clahe_plan(int w, int h, int nframes, double clip_limit, int tiles_x,
     return MI355_OK;
 }
 
-// CLAHE up to the tables: the pooled tile histograms, zeroed in-stream, the histogram launch and the table launch into
-// d_luts.  Only the first call for a larger frames x tiles count allocates (and synchronises, in ensure()).
+// CLAHE up to the tables: the zeroed tile histograms, the histogram launch and the table launch into d_luts
 static int clahe_tables(mi355_ctx* ctx, const uint8_t* in, uint8_t* d_luts, const ClaheGeom& g, int nframes)
 {
-    const size_t nhist = (size_t)nframes * (size_t)(g.tiles_x * g.tiles_y) * 256 * sizeof(uint32_t);
+    const int rc = zeroed_hists(ctx, (size_t)nframes * (size_t)(g.tiles_x * g.tiles_y));
+    if (rc != MI355_OK)
+        return rc;
     uint32_t* hist = static_cast<uint32_t*>(ctx->d_hist.p);
-    HIP_TRY(ctx, hipMemsetAsync(hist, 0, nhist, ctx->stream));
     HIP_TRY(ctx, launch_clahe_hist(ctx->stream, in, hist, g, nframes));
     HIP_TRY(ctx, launch_clahe_table(ctx->stream, hist, d_luts, g, nframes));
     return MI355_OK;
 }
 
-// the pooled scratch of a CLAHE call: 1 KiB of histogram and 256 B of table per (frame, tile)
-static int clahe_scratch(mi355_ctx* ctx, const ClaheGeom& g, int nframes)
-{
-    const size_t ntiles = (size_t)nframes * (size_t)(g.tiles_x * g.tiles_y);
-    const int rc = ensure(ctx, ctx->d_hist, ntiles * 256 * sizeof(uint32_t));
-    return rc == MI355_OK ? ensure(ctx, ctx->d_lut, ntiles * 256) : rc;
-}
-
-// the one argument check of the device-resident CLAHE calls; d_out takes the frames, or with `luts` the tables (256 bytes
-// per frame and tile, 4-byte aligned)
+// the one argument check of the device-resident CLAHE calls; d_out takes the frames, or with `luts` the aligned tables
 static int clahe_check_dev(mi355_ctx* ctx, const void* d_in, const void* d_out, bool luts, int w, int h, int nframes,
                            double clip_limit, int tiles_x, int tiles_y, ClaheGeom* g)
 {
@@ -1560,7 +1564,7 @@ static int clahe_check_dev(mi355_ctx* ctx, const void* d_in, const void* d_out, 
     if ((luts && (reinterpret_cast<uintptr_t>(d_out) & 3u)) || overlap(d_in, nin, d_out, nout))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return clahe_scratch(ctx, *g, nframes);
+    return hist_scratch(ctx, (size_t)nframes * (size_t)(tiles_x * tiles_y));
 }
 
 MI355_API int mi355_clahe_check(int w, int h, int nframes, double clip_limit, int tiles_x, int tiles_y)
@@ -1573,14 +1577,12 @@ MI355_API int mi355_clahe_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_ou
 {
     ClaheGeom g;
     int rc = clahe_check_dev(ctx, d_in, d_out, false, w, h, nframes, clip_limit, tiles_x, tiles_y, &g);
+    if (rc == MI355_OK)
+        rc = clahe_tables(ctx, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(ctx->d_lut.p), g, nframes);
     if (rc != MI355_OK)
         return rc;
-    uint8_t* luts = static_cast<uint8_t*>(ctx->d_lut.p);
-    rc = clahe_tables(ctx, static_cast<const uint8_t*>(d_in), luts, g, nframes);
-    if (rc != MI355_OK)
-        return rc;
-    HIP_TRY(ctx, launch_clahe_apply(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), luts, g,
-                                    nframes));
+    HIP_TRY(ctx, launch_clahe_apply(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                                    static_cast<const uint8_t*>(ctx->d_lut.p), g, nframes));
     return MI355_OK;
 }
 
@@ -1589,9 +1591,7 @@ MI355_API int mi355_clahe_luts_gray8_dev(mi355_ctx* ctx, const void* d_in, uint8
 {
     ClaheGeom g;
     const int rc = clahe_check_dev(ctx, d_in, d_luts, true, w, h, nframes, clip_limit, tiles_x, tiles_y, &g);
-    if (rc != MI355_OK)
-        return rc;
-    return clahe_tables(ctx, static_cast<const uint8_t*>(d_in), d_luts, g, nframes);
+    return rc == MI355_OK ? clahe_tables(ctx, static_cast<const uint8_t*>(d_in), d_luts, g, nframes) : rc;
 }
 
 MI355_API int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
@@ -1606,7 +1606,7 @@ MI355_API int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8
     HostIO io;
     rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
     if (rc == MI355_OK)
-        rc = clahe_scratch(ctx, g, nframes);  // sized outside the timed write/kernel/read window
+        rc = hist_scratch(ctx, (size_t)nframes * (size_t)(tiles_x * tiles_y));  // outside the timed window
     if (rc != MI355_OK)
         return rc;
     return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {

@@ -1,25 +1,19 @@
-// clahe.hip — contrast-limited adaptive histogram equalization of single-channel frames
-// (cv::createCLAHE(clip, Size(tiles_x, tiles_y))->apply(), 8-bit).  Semantics: include/mi355_imgfilter.h, "local
-// contrast".
+// clahe.hip — contrast-limited adaptive histogram equalization of single-channel frames (cv::createCLAHE(clip,
+// Size(tiles_x, tiles_y))->apply(), 8-bit).  Semantics: include/mi355_imgfilter.h, "local contrast".
 //
 // The frame is extended on the right and bottom to ew x eh = tiles_x tw x tiles_y th by one reflection
-// (BORDER_REFLECT_101); the extended frame never exists in memory.  Three launches on one stream, the kernel boundaries
-// being the only cross-workgroup synchronisation (hist.hip's shape):
-//   clahe_hist_kernel   a block of 256 threads owns a band of rows of one (frame, tile).  A tile row is tw bytes of the
-//                       source at whatever alignment it has: a thread takes one 16-byte aligned chunk of one row, as a
-//                       vector if the row covers all of it and byte by byte otherwise, or the row's reflected columns
-//                       (at most tiles_x of them: a contiguous run of the same source row, read backwards in effect).
-//                       Reflected rows are source rows.  Per-wave LDS histograms with equal bytes merged first
-//                       (hist_common.hpp); nonzero bins go by agent-scope integer atomics into the zeroed histogram;
-//   clahe_table_kernel  one wave per (frame, tile): the clip, the closed-form redistribution of the clipped counts, an
-//                       integer prefix sum across lanes, one fp32 multiply and rint per bin;
+// (BORDER_REFLECT_101); the extended frame never exists in memory.  The three launches, the block histogram frame, the
+// byte-range walk and the table scan are hist_common.hpp's (DESIGN.md sections 6d and 6d.1):
+//   clahe_hist_kernel   a block owns a band of rows of one (frame, tile).  A tile row is tw bytes of the source at
+//                       whatever alignment it has: a thread takes one 16-byte aligned chunk of one row, as a vector if
+//                       the row covers all of it and byte by byte otherwise, or the row's reflected columns (at most
+//                       tiles_x: a run of the same source row, read backwards).  Reflected rows are source rows;
+//   clahe_table_kernel  one wave per (frame, tile): the clip, the closed-form redistribution, the table scan;
 //   clahe_apply_kernel  the rows of a frame fall into tiles_y + 1 groups that share one pair (r1, r2) of tile rows.  A
-//                       block owns up to kApplyBytes of consecutive rows of one group as one flat byte range, stages the
-//                       two tile rows' tables in LDS with the four bytes a pixel blends side by side ((tiles_x + 1) x
-//                       256 dwords, one per pair of neighbouring tile columns and source byte: one ds_read_b32 per pixel
-//                       instead of four ds_read_u8), and blends them in fp32 (-ffp-contract=off: nothing fuses).  16-byte
-//                       non-temporal stores aligned on the output, 16-byte loads at whatever alignment the input then
-//                       has, head and tail bytes as in hist.hip.
+//                       block owns up to kApplyBlockBytes of consecutive rows of one group as one byte range aligned on
+//                       the output, stages the two tile rows' tables in LDS with the four bytes a pixel blends side by
+//                       side ((tiles_x + 1) x 256 dwords, one per pair of neighbouring tile columns and source byte: one
+//                       ds_read_b32 per pixel instead of four ds_read_u8), and blends them in fp32.
 //                       The group boundaries are found on the host with the function the kernel uses for its weights
 //                       (clahe_cell: one IEEE multiply, one subtract, one floor), so both agree on every row.
 #include "common.hpp"
@@ -33,10 +27,6 @@ namespace mi355 {
 
 namespace {
 
-constexpr int kCThreads = 256;
-constexpr int kCWaves = kCThreads / kWave;
-constexpr uint32_t kBandBytes = 64 * 1024;   // of a tile per block of clahe_hist_kernel: hist_kernel's 64 KiB
-constexpr uint32_t kApplyBytes = 32 * 1024;  // of a frame per block of clahe_apply_kernel: apply_kernel's 32 KiB
 constexpr int kGroups = kClaheMaxTiles + 1;
 
 // The apply stage's cell of position p along one axis: tf = (float)p * inv - 0.5f, t1 = floor(tf), *a = tf - t1.
@@ -55,15 +45,13 @@ struct ClaheRows {
     uint32_t blk0[kGroups + 1];
 };
 
-__global__ __launch_bounds__(kCThreads) void clahe_hist_kernel(const uint8_t* __restrict__ in,
-                                                               uint32_t* __restrict__ hist, ClaheGeom g,
-                                                               uint32_t band_rows, uint32_t nbands)
+__global__ __launch_bounds__(kHistThreads) void clahe_hist_kernel(const uint8_t* __restrict__ in,
+                                                                  uint32_t* __restrict__ hist, ClaheGeom g,
+                                                                  uint32_t band_rows, uint32_t nbands)
 {
-    __shared__ uint32_t sh[kCWaves * 256];
+    __shared__ uint32_t sh[kHistWaves * 256];
     const int tid = threadIdx.x;
-    for (int i = tid; i < kCWaves * 256; i += kCThreads)
-        sh[i] = 0;
-    __syncthreads();
+    uint32_t* hw = block_hists_begin(sh);
     const uint32_t w = (uint32_t)g.w, h = (uint32_t)g.h, tw = (uint32_t)g.tw, th = (uint32_t)g.th;
     const uint32_t ntiles = (uint32_t)(g.tiles_x * g.tiles_y);
     const uint32_t ft = blockIdx.x / nbands, band = blockIdx.x - ft * nbands;  // ft = frame * ntiles + tile
@@ -79,8 +67,7 @@ __global__ __launch_bounds__(kCThreads) void clahe_hist_kernel(const uint8_t* __
     const uint32_t r0 = band * band_rows;
     const uint32_t r1 = r0 + band_rows < th ? r0 + band_rows : th;
     const uint32_t items = (r1 - r0) * slots;
-    uint32_t* hw = sh + (tid / kWave) * 256;
-    for (uint32_t k0 = 0; k0 < items; k0 += kCThreads) {
+    for (uint32_t k0 = 0; k0 < items; k0 += kHistThreads) {
         const uint32_t k = k0 + tid;
         bool full = false;
         u32x4 v = {0, 0, 0, 0};
@@ -111,13 +98,7 @@ __global__ __launch_bounds__(kCThreads) void clahe_hist_kernel(const uint8_t* __
         for (uint32_t x = lo; x < hi; x++)
             lds_add(hw, row[x], 1);
     }
-    __syncthreads();
-    uint32_t s = 0;
-#pragma unroll
-    for (int wv = 0; wv < kCWaves; wv++)
-        s += sh[wv * 256 + tid];
-    if (s)
-        __hip_atomic_fetch_add(hist + (size_t)ft * 256 + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    block_hists_flush(sh, hist + (size_t)ft * 256);
 }
 
 // one wave per (frame, tile): lane l holds bins 4 l .. 4 l + 3
@@ -146,21 +127,11 @@ __global__ __launch_bounds__(kWave) void clahe_table_kernel(const uint32_t* __re
             hv[j] += batch + (residual && q * step == b && q < residual ? 1u : 0u);
         }
     }
-    // inclusive prefix sum of the per-lane sums (integers: exact in any order)
-    const uint32_t lsum = hv.x + hv.y + hv.z + hv.w;
-    uint32_t inc = lsum;
-#pragma unroll
-    for (int d = 1; d < kWave; d *= 2) {
-        const uint32_t o = __shfl_up(inc, d);
-        if (lane >= d)
-            inc += o;
-    }
-    uint32_t c = inc - lsum, out = 0;
+    uint32_t c = bins_below(hv, lane), out = 0;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         c += hv[j];
-        const float v = __builtin_rintf((float)(int)c * lut_scale);
-        out |= (v >= 255.0f ? 255u : (uint32_t)v) << (8 * j);
+        out |= table_byte(c, lut_scale) << (8 * j);
     }
     reinterpret_cast<uint32_t*>(lut + t * 256)[lane] = out;
 }
@@ -207,10 +178,10 @@ __device__ __forceinline__ u32x4 clahe_vec(const uint32_t* sq, const u32x4& v, u
     return o;
 }
 
-__global__ __launch_bounds__(kCThreads) void clahe_apply_kernel(const uint8_t* __restrict__ in,
-                                                                uint8_t* __restrict__ out,
-                                                                const uint8_t* __restrict__ lut, ClaheGeom g,
-                                                                ClaheRows rows, uint32_t chunk_rows)
+__global__ __launch_bounds__(kHistThreads) void clahe_apply_kernel(const uint8_t* __restrict__ in,
+                                                                   uint8_t* __restrict__ out,
+                                                                   const uint8_t* __restrict__ lut, ClaheGeom g,
+                                                                   ClaheRows rows, uint32_t chunk_rows)
 {
     __shared__ u32x4 sq4[(kClaheMaxTiles + 1) * 64];
     const int tid = threadIdx.x;
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(kCThreads) void clahe_apply_kernel(const uint8_t* _
     const uint32_t* bot_g = reinterpret_cast<const uint32_t*>(lut + frame_lut + (size_t)r2 * row_dwords * 4);
     // stage the two tile rows' tables, the four bytes of a column pair and a source byte side by side: one LDS read per
     // pixel.  Pair pc = floor(txf) + 1 in 0 .. tiles_x is the columns c1 = max(pc - 1, 0), c2 = min(pc, tiles_x - 1).
-    for (uint32_t i = tid; i < ((uint32_t)g.tiles_x + 1u) * 64u; i += kCThreads) {
+    for (uint32_t i = tid; i < ((uint32_t)g.tiles_x + 1u) * 64u; i += kHistThreads) {
         const uint32_t pc = i / 64u, v4 = i - pc * 64u;  // source bytes 4 v4 .. 4 v4 + 3
         const uint32_t c1 = pc > 0 ? pc - 1 : 0, c2 = pc < (uint32_t)g.tiles_x - 1 ? pc : (uint32_t)g.tiles_x - 1;
         const uint32_t ta = top_g[c1 * 64 + v4], tb = top_g[c2 * 64 + v4];
@@ -257,33 +228,26 @@ __global__ __launch_bounds__(kCThreads) void clahe_apply_kernel(const uint8_t* _
     const uint8_t* p = in + at;
     uint8_t* q = out + at;
     const uint32_t nb = (uint32_t)(y_hi - y_lo) * w;  // this block's bytes: rows y_lo .. y_hi - 1 as one flat range
-    const uint32_t head = head_bytes(reinterpret_cast<uintptr_t>(q), nb);
-    const uint32_t nvec = (nb - head) / 16, body_end = head + 16 * nvec;
-    for (uint32_t j = tid; j < nvec; j += kCThreads) {
-        const uint32_t i0 = head + 16 * j;
+    const ByteRange r = byte_range(q, nb);
+    for (uint32_t j = tid; j < r.nvec; j += kHistThreads) {
+        const uint32_t i0 = r.head + 16 * j;
         const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_a1*>(p + i0));
         const uint32_t yr = i0 / w, x = i0 - yr * w;
         const u32x4 o = x + 16 <= w ? clahe_vec<false>(sq, v, x, y_lo + (int)yr, w, g.inv_tw, g.inv_th)
                                     : clahe_vec<true>(sq, v, x, y_lo + (int)yr, w, g.inv_tw, g.inv_th);
         __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(q + i0));
     }
-    // the head (tid 0 .. 15) and the tail (tid 16 .. 31) of the range, byte by byte
-    uint32_t i = nb;
-    if ((uint32_t)tid < head)
-        i = (uint32_t)tid;
-    else if (tid >= 16 && tid < 32)
-        i = body_end + (uint32_t)(tid - 16);
-    if (i < nb) {
+    for_edge_byte(r, nb, tid, [&](uint32_t i) {
         const uint32_t yr = i / w, x = i - yr * w;
         float wy;
         (void)clahe_cell(y_lo + (int)yr, g.inv_th, &wy);
         q[i] = (uint8_t)(uint32_t)clahe_px(sq, p[i], x, g.inv_tw, wy, 1.0f - wy);
-    }
+    });
 }
 
 bool clahe_sizes_ok(const ClaheGeom& g, int nframes)
 {
-    return g.w > 0 && g.h > 0 && nframes > 0 && g.tiles_x >= 1 && g.tiles_x <= kClaheMaxTiles &&
+    return hist_frames_ok(g.w, g.h, nframes) && g.tiles_x >= 1 && g.tiles_x <= kClaheMaxTiles &&
            g.tiles_y >= 1 && g.tiles_y <= kClaheMaxTiles && g.tw >= 1 && g.th >= 1 &&
            (uint64_t)g.tw * g.tiles_x * (uint64_t)g.th * g.tiles_y < (1ull << 31) &&
            g.tw * g.tiles_x - g.w <= g.w - 1 && g.th * g.tiles_y - g.h <= g.h - 1;
@@ -310,15 +274,15 @@ hipError_t launch_clahe_hist(hipStream_t stream, const uint8_t* d_in, uint32_t* 
 {
     if (!clahe_sizes_ok(g, nframes))
         return hipErrorInvalidValue;
-    uint32_t band_rows = kBandBytes / (uint32_t)g.tw;
+    uint32_t band_rows = kHistBlockBytes / (uint32_t)g.tw;
     band_rows = band_rows < 1 ? 1 : (band_rows > (uint32_t)g.th ? (uint32_t)g.th : band_rows);
     const uint32_t nbands = ((uint32_t)g.th + band_rows - 1) / band_rows;
     band_rows = ((uint32_t)g.th + nbands - 1) / nbands;  // bands of equal size
     const uint64_t blocks = (uint64_t)nframes * (uint64_t)(g.tiles_x * g.tiles_y) * nbands;
-    if (blocks > 0x7FFFFFFFull)
+    if (!grid_fits(blocks))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(clahe_hist_kernel, dim3((uint32_t)blocks), dim3(kCThreads), 0, stream, d_in, d_hist, g, band_rows,
-                       nbands);
+    hipLaunchKernelGGL(clahe_hist_kernel, dim3((uint32_t)blocks), dim3(kHistThreads), 0, stream, d_in, d_hist, g,
+                       band_rows, nbands);
     return hipGetLastError();
 }
 
@@ -328,7 +292,7 @@ hipError_t launch_clahe_table(hipStream_t stream, const uint32_t* d_hist, uint8_
     if (!clahe_sizes_ok(g, nframes) || g.cl < 0)
         return hipErrorInvalidValue;
     const uint64_t blocks = (uint64_t)nframes * (uint64_t)(g.tiles_x * g.tiles_y);
-    if (blocks > 0x7FFFFFFFull)
+    if (!grid_fits(blocks))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(clahe_table_kernel, dim3((uint32_t)blocks), dim3(kWave), 0, stream, d_hist, d_luts,
                        (uint32_t)g.cl, g.lut_scale);
@@ -340,7 +304,7 @@ hipError_t launch_clahe_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* 
 {
     if (!clahe_sizes_ok(g, nframes))
         return hipErrorInvalidValue;
-    uint32_t chunk_rows = kApplyBytes / (uint32_t)g.w;
+    uint32_t chunk_rows = kApplyBlockBytes / (uint32_t)g.w;
     chunk_rows = chunk_rows < 1 ? 1 : chunk_rows;
     ClaheRows rows;
     uint64_t blk = 0;
@@ -351,10 +315,10 @@ hipError_t launch_clahe_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* 
         rows.blk0[i] = (uint32_t)blk;
     }
     const uint64_t blocks = blk * (uint64_t)nframes;
-    if (blk == 0 || blocks > 0x7FFFFFFFull)
+    if (blk == 0 || !grid_fits(blocks))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(clahe_apply_kernel, dim3((uint32_t)blocks), dim3(kCThreads), 0, stream, d_in, d_out, d_luts, g,
-                       rows, chunk_rows);
+    hipLaunchKernelGGL(clahe_apply_kernel, dim3((uint32_t)blocks), dim3(kHistThreads), 0, stream, d_in, d_out, d_luts,
+                       g, rows, chunk_rows);
     return hipGetLastError();
 }
 

@@ -2,23 +2,14 @@
 // equalization (MI355_FILTER_EQUALIZE_GRAY8, cv::equalizeHist) and Otsu thresholding (MI355_FILTER_OTSU_GRAY8,
 // cv::threshold(THRESH_BINARY | THRESH_OTSU)).  Semantics: include/mi355_imgfilter.h.
 //
-// Every frame is the flat byte range [f * npx, (f + 1) * npx), npx = w * h < 2^31 (OpenCV counts pixels in an int).
-// Three launches on one stream, the kernel boundaries being the only cross-workgroup synchronisation:
-//   hist_kernel   a block of 256 threads takes 256 x kHistVec 16-byte vectors of one frame (the frame's body from its
-//                 first 16-byte-aligned input byte; the unaligned head and tail, < 16 bytes each, go byte by byte in
-//                 the frame's first block).  Each wave counts into a private 256-bin LDS histogram with ds_add_u32;
-//                 the block sums its four and adds every nonzero bin once into the frame's row of a zeroed global
-//                 histogram (agent-scope integer atomics: exact, so the result does not depend on arrival order).
-//                 Flat content would put up to 64 lanes of one ds_add on one address (64-way serialised): equal bytes
-//                 are merged first.  Lanes whose 16 bytes all equal the wave's first such value add one count for all
-//                 of them, other lanes with 16 equal bytes add 16 once, dwords of 4 equal bytes add 4 once, and only
-//                 the rest add byte by byte;
-//   table_kernel  one wave per frame reads the histogram and writes a 256-byte table (LUT) per frame.  Equalize: an
-//                 integer prefix sum across lanes (exact in any order), then one fp32 multiply and rint per bin.
-//                 Otsu: OpenCV's serial fp64 loop in one lane, operation by operation (-ffp-contract=off: no fused
+// Every frame is the flat byte range [f * npx, (f + 1) * npx), npx = w * h < 2^31.  The three launches, the block
+// histogram frame, the byte-range walk and the table scan are hist_common.hpp's:
+//   hist_kernel   256 x kHistVec vectors of a frame's body per block, aligned on the input; head and tail in its first;
+//   table_kernel  one wave per frame makes its histogram a 256-byte table (LUT).  Equalize: the table scan from the
+//                 first occupied bin.  Otsu: OpenCV's serial fp64 loop in one lane, operation by operation (no fused
 //                 multiply-add; the fp64 divisions are the IEEE correctly rounded sequence), then lut[v] = v > t;
-//   apply_kernel  the frame's LUT in LDS, one ds_read_u8 per pixel; 16-byte non-temporal stores aligned on the output,
-//                 16-byte loads at whatever alignment the input then has, head and tail bytes as in hist_kernel.
+//   apply_kernel  the frame's LUT in LDS, one ds_read_u8 per pixel; 256 x kApplyVec vectors per block, aligned on the
+//                 output (non-temporal stores).
 #include "common.hpp"
 #include "hist_common.hpp"
 #include "kernels.hpp"
@@ -30,53 +21,32 @@ namespace mi355 {
 
 namespace {
 
-constexpr int kHThreads = 256;
-constexpr int kHWaves = kHThreads / kWave;
-constexpr int kHistVec = 16;  // 16-byte vectors per thread of hist_kernel: 64 KiB per block, 256 atomics per flush
-constexpr int kApplyVec = 8;  // per thread of apply_kernel: 32 KiB per block
-
-// head_bytes, lds_add, count_dword, count_vec: hist_common.hpp (shared with clahe.hip)
-
-__global__ __launch_bounds__(kHThreads) void hist_kernel(const uint8_t* __restrict__ in, uint32_t* __restrict__ hist,
-                                                         uint32_t npx, uint32_t tiles)
+__global__ __launch_bounds__(kHistThreads) void hist_kernel(const uint8_t* __restrict__ in, uint32_t* __restrict__ hist,
+                                                            uint32_t npx, uint32_t tiles)
 {
-    __shared__ uint32_t sh[kHWaves * 256];
+    __shared__ uint32_t sh[kHistWaves * 256];
     const int tid = threadIdx.x;
-    for (int i = tid; i < kHWaves * 256; i += kHThreads)
-        sh[i] = 0;
-    __syncthreads();
+    uint32_t* hw = block_hists_begin(sh);
     const uint32_t f = blockIdx.x / tiles, tile = blockIdx.x - f * tiles;
     const uint8_t* p = in + (size_t)f * npx;
-    const uint32_t head = head_bytes(reinterpret_cast<uintptr_t>(p), npx);
-    const uint32_t nvec = (npx - head) / 16, body_end = head + 16 * nvec;
-    const u32x4* vp = reinterpret_cast<const u32x4*>(p + head);
-    uint32_t* hw = sh + (tid / kWave) * 256;
-    const uint32_t j0 = tile * (kHThreads * kHistVec) + tid;
+    const ByteRange r = byte_range(p, npx);
+    const u32x4* vp = reinterpret_cast<const u32x4*>(p + r.head);
+    const uint32_t j0 = tile * (kHistThreads * kHistVec) + tid;
 #pragma unroll
     for (int u0 = 0; u0 < kHistVec; u0 += 4) {
         u32x4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const uint32_t j = j0 + (u0 + u) * kHThreads;
-            v[u] = j < nvec ? __builtin_nontemporal_load(vp + j) : u32x4{0, 0, 0, 0};
+            const uint32_t j = j0 + (u0 + u) * kHistThreads;
+            v[u] = j < r.nvec ? __builtin_nontemporal_load(vp + j) : u32x4{0, 0, 0, 0};
         }
 #pragma unroll
         for (int u = 0; u < 4; u++)
-            count_vec(hw, v[u], j0 + (u0 + u) * kHThreads < nvec);
+            count_vec(hw, v[u], j0 + (u0 + u) * kHistThreads < r.nvec);
     }
-    if (tile == 0) {
-        if ((uint32_t)tid < head)
-            lds_add(hw, p[tid], 1);
-        else if (tid >= 16 && tid < 32 && body_end + (uint32_t)(tid - 16) < npx)
-            lds_add(hw, p[body_end + (tid - 16)], 1);
-    }
-    __syncthreads();
-    uint32_t s = 0;
-#pragma unroll
-    for (int wv = 0; wv < kHWaves; wv++)
-        s += sh[wv * 256 + tid];
-    if (s)
-        __hip_atomic_fetch_add(hist + (size_t)f * 256 + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tile == 0)
+        for_edge_byte(r, npx, tid, [&](uint32_t e) { lds_add(hw, p[e], 1); });
+    block_hists_flush(sh, hist + (size_t)f * 256);
 }
 
 // OpenCV's getThreshVal_Otsu_8u loop (include/mi355_imgfilter.h), one lane; h = the frame's 256 counts in LDS
@@ -129,27 +99,12 @@ __global__ __launch_bounds__(kWave) void table_kernel(const uint32_t* __restrict
             out = (uint32_t)i0 * 0x01010101u;
         } else {
             const float scale = 255.0f / (float)(int)(total - h0);
-            // inclusive prefix sum of the per-lane sums (integers: exact in any order)
-            const uint32_t lsum = hv.x + hv.y + hv.z + hv.w;
-            uint32_t inc = lsum;
-#pragma unroll
-            for (int d = 1; d < kWave; d *= 2) {
-                const uint32_t o = __shfl_up(inc, d);
-                if (lane >= d)
-                    inc += o;
-            }
-            uint32_t c = inc - lsum;
+            uint32_t c = bins_below(hv, lane);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 c += hv[j];
-                const int i = 4 * lane + j;
-                uint32_t byte = 0;
-                if (i > i0) {
-                    // sum of the bins i0 + 1 .. i (the bins below i0 are empty); (float)sum * scale, cvRound
-                    const float v = __builtin_rintf((float)(int)(c - h0) * scale);
-                    byte = v >= 255.0f ? 255u : (uint32_t)v;
-                }
-                out |= byte << (8 * j);
+                // bin i > i0: the sum of the bins i0 + 1 .. i (the bins below i0 are empty)
+                out |= (4 * lane + j > i0 ? table_byte(c - h0, scale) : 0u) << (8 * j);
             }
         }
     } else {
@@ -184,8 +139,9 @@ __device__ __forceinline__ uint32_t lut_dword(const uint8_t* sl, uint32_t d)
            ((uint32_t)sl[d >> 24] << 24);
 }
 
-__global__ __launch_bounds__(kHThreads) void apply_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
-                                                          const uint8_t* __restrict__ lut, uint32_t npx, uint32_t tiles)
+__global__ __launch_bounds__(kHistThreads) void apply_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                                             const uint8_t* __restrict__ lut, uint32_t npx,
+                                                             uint32_t tiles)
 {
     __shared__ uint8_t sl[256];
     const int tid = threadIdx.x;
@@ -194,41 +150,35 @@ __global__ __launch_bounds__(kHThreads) void apply_kernel(const uint8_t* __restr
     __syncthreads();
     const uint8_t* p = in + (size_t)f * npx;
     uint8_t* q = out + (size_t)f * npx;
-    const uint32_t head = head_bytes(reinterpret_cast<uintptr_t>(q), npx);
-    const uint32_t nvec = (npx - head) / 16, body_end = head + 16 * nvec;
-    const uint32_t j0 = tile * (kHThreads * kApplyVec) + tid;
+    const ByteRange r = byte_range(q, npx);
+    const uint32_t j0 = tile * (kHistThreads * kApplyVec) + tid;
     u32x4 v[kApplyVec];
 #pragma unroll
     for (int u = 0; u < kApplyVec; u++) {
-        const uint32_t j = j0 + u * kHThreads;
-        if (j < nvec)
-            v[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_a1*>(p + head + 16 * (size_t)j));
+        const uint32_t j = j0 + u * kHistThreads;
+        if (j < r.nvec)
+            v[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_a1*>(p + r.head + 16 * (size_t)j));
     }
 #pragma unroll
     for (int u = 0; u < kApplyVec; u++) {
-        const uint32_t j = j0 + u * kHThreads;
-        if (j < nvec) {
+        const uint32_t j = j0 + u * kHistThreads;
+        if (j < r.nvec) {
             const u32x4 o = {lut_dword(sl, v[u].x), lut_dword(sl, v[u].y), lut_dword(sl, v[u].z), lut_dword(sl, v[u].w)};
-            __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(q + head) + j);
+            __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(q + r.head) + j);
         }
     }
-    if (tile == 0) {
-        if ((uint32_t)tid < head)
-            q[tid] = sl[p[tid]];
-        else if (tid >= 16 && tid < 32 && body_end + (uint32_t)(tid - 16) < npx)
-            q[body_end + (tid - 16)] = sl[p[body_end + (tid - 16)]];
-    }
+    if (tile == 0)
+        for_edge_byte(r, npx, tid, [&](uint32_t e) { q[e] = sl[p[e]]; });
 }
 
 // blocks of one frame for `per_block` 16-byte vectors per block, and the whole grid; false if it is too large
 bool grid_of(int w, int h, int nframes, int per_block, uint32_t* tiles, uint32_t* blocks)
 {
-    const uint64_t npx = (uint64_t)w * (uint64_t)h;
-    if (w <= 0 || h <= 0 || nframes <= 0 || npx >= (1ull << 31))
+    if (!hist_frames_ok(w, h, nframes))
         return false;
-    const uint64_t t = (npx / 16 + (uint64_t)per_block - 1) / (uint64_t)per_block;
+    const uint64_t t = ((uint64_t)(w * h) / 16 + (uint64_t)per_block - 1) / (uint64_t)per_block;
     const uint64_t tt = t ? t : 1;  // a frame shorter than one vector still has its head / tail block
-    if (tt * (uint64_t)nframes > 0x7FFFFFFFull)
+    if (!grid_fits(tt * (uint64_t)nframes))
         return false;
     *tiles = (uint32_t)tt;
     *blocks = (uint32_t)(tt * (uint64_t)nframes);
@@ -240,16 +190,17 @@ bool grid_of(int w, int h, int nframes, int per_block, uint32_t* tiles, uint32_t
 hipError_t launch_hist(hipStream_t stream, const uint8_t* d_in, uint32_t* d_hist, int w, int h, int nframes)
 {
     uint32_t tiles = 0, blocks = 0;
-    if (!grid_of(w, h, nframes, kHThreads * kHistVec, &tiles, &blocks))
+    if (!grid_of(w, h, nframes, kHistThreads * kHistVec, &tiles, &blocks))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hist_kernel, dim3(blocks), dim3(kHThreads), 0, stream, d_in, d_hist, (uint32_t)(w * h), tiles);
+    hipLaunchKernelGGL(hist_kernel, dim3(blocks), dim3(kHistThreads), 0, stream, d_in, d_hist, (uint32_t)(w * h),
+                       tiles);
     return hipGetLastError();
 }
 
 hipError_t launch_hist_table(hipStream_t stream, const uint32_t* d_hist, uint8_t* d_lut, int32_t* d_thresh, int w,
                              int h, int nframes, bool otsu)
 {
-    if (w <= 0 || h <= 0 || nframes <= 0 || (uint64_t)w * (uint64_t)h >= (1ull << 31))
+    if (!hist_frames_ok(w, h, nframes))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(table_kernel, dim3((unsigned)nframes), dim3(kWave), 0, stream, d_hist, d_lut, d_thresh,
                        (uint32_t)(w * h), otsu ? 1 : 0);
@@ -260,9 +211,9 @@ hipError_t launch_lut_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* d_
                             int nframes)
 {
     uint32_t tiles = 0, blocks = 0;
-    if (!grid_of(w, h, nframes, kHThreads * kApplyVec, &tiles, &blocks))
+    if (!grid_of(w, h, nframes, kHistThreads * kApplyVec, &tiles, &blocks))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(kHThreads), 0, stream, d_in, d_out, d_lut, (uint32_t)(w * h),
+    hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(kHistThreads), 0, stream, d_in, d_out, d_lut, (uint32_t)(w * h),
                        tiles);
     return hipGetLastError();
 }

@@ -1,19 +1,35 @@
-// hist_common.hpp — what the histogram kernels share (hist.hip: whole frames, clahe.hip: tiles of a frame): where the
-// 16-byte body of a byte range starts, and counting bytes into a wave's private 256-bin LDS histogram with equal bytes
-// merged first.  Flat content would put up to 64 lanes of one ds_add on one address (64-way serialised): lanes whose 16
-// bytes all equal the wave's first such value add one count for all of them, other lanes with 16 equal bytes add 16
-// once, dwords of 4 equal bytes add 4 once, and only the rest add byte by byte.
+// hist_common.hpp — what the histogram kernels share (hist.hip: whole frames, clahe.hip: tiles of a frame; DESIGN.md
+// section 6d).  Both run three launches on one stream, the kernel boundaries being the only cross-workgroup
+// synchronisation: count into a zeroed global histogram, make a 256-byte table of every 256-bin row, apply the tables.
+//   counting     into a wave's private 256-bin LDS histogram, equal bytes merged first.  Flat content would put up to 64
+//                lanes of one ds_add on one address (64-way serialised): lanes whose 16 bytes all equal the wave's first
+//                such value add one count for all of them, other lanes with 16 equal bytes add 16 once, dwords of 4
+//                equal bytes add 4 once, and only the rest add byte by byte;
+//   block frame  block_hists_begin / _flush around the counting loop: the block sums its waves' histograms and adds
+//                every nonzero bin once into a global row (agent-scope integer atomics: exact in any arrival order);
+//   byte range   16-byte vectors from the first 16-byte-aligned byte of one side (the input when counting, the output
+//                when applying; the other side at whatever alignment it then has); the head and the tail, < 16 bytes
+//                each, go byte by byte in threads 0..15 and 16..31 of one block;
+//   table scan   lane l of one wave holds bins 4 l .. 4 l + 3: an integer prefix sum across lanes (exact in any order),
+//                then one fp32 multiply and rint per bin (-ffp-contract=off: nothing fuses).
 #pragma once
 #include "common.hpp"
 
 namespace mi355 {
 
-// where the 16-byte body of a frame starts, relative to the frame, for a frame at address a of npx bytes
-__device__ __forceinline__ uint32_t head_bytes(uintptr_t a, uint32_t npx)
+constexpr int kHistThreads = 256;  // of every block that counts or applies
+constexpr int kHistWaves = kHistThreads / kWave;
+constexpr int kHistVec = 16;  // 16-byte vectors per thread of a counting block
+constexpr int kApplyVec = 8;  // per thread of an applying block
+constexpr uint32_t kHistBlockBytes = kHistThreads * kHistVec * 16;    // 64 KiB per block, 256 atomics per flush
+constexpr uint32_t kApplyBlockBytes = kHistThreads * kApplyVec * 16;  // 32 KiB per block
+
+// host: frames of w x h < 2^31 pixels (OpenCV counts pixels in an int), and a block count that fits a grid
+inline bool hist_frames_ok(int w, int h, int nframes)
 {
-    const uint32_t hb = (uint32_t)((16u - (a & 15u)) & 15u);
-    return hb < npx ? hb : npx;
+    return w > 0 && h > 0 && nframes > 0 && (uint64_t)w * (uint64_t)h < (1ull << 31);
 }
+inline bool grid_fits(uint64_t blocks) { return blocks <= 0x7FFFFFFFull; }
 
 __device__ __forceinline__ void lds_add(uint32_t* hw, uint32_t bin, uint32_t n)
 {
@@ -59,6 +75,73 @@ __device__ __forceinline__ void count_vec(uint32_t* hw, const u32x4& v, bool val
     count_dword(hw, v.y);
     count_dword(hw, v.z);
     count_dword(hw, v.w);
+}
+
+// zeroes the block's kHistWaves x 256 LDS bins sh; returns the calling wave's 256
+__device__ __forceinline__ uint32_t* block_hists_begin(uint32_t* sh)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < kHistWaves * 256; i += kHistThreads)
+        sh[i] = 0;
+    __syncthreads();
+    return sh + (tid / kWave) * 256;
+}
+
+// after the block's counting: thread t adds bin t of the waves' sum into the global histogram `row`, if it is not zero
+__device__ __forceinline__ void block_hists_flush(const uint32_t* sh, uint32_t* row)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();
+    uint32_t s = 0;
+#pragma unroll
+    for (int wv = 0; wv < kHistWaves; wv++)
+        s += sh[wv * 256 + tid];
+    if (s)
+        __hip_atomic_fetch_add(row + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// nbytes bytes: head bytes [0, head), nvec vectors that are 16-byte aligned at `aligned_side`, tail bytes from body_end
+struct ByteRange {
+    uint32_t head, nvec, body_end;
+};
+__device__ __forceinline__ ByteRange byte_range(const void* aligned_side, uint32_t nbytes)
+{
+    const uint32_t hb = (uint32_t)((16u - (reinterpret_cast<uintptr_t>(aligned_side) & 15u)) & 15u);
+    const uint32_t head = hb < nbytes ? hb : nbytes;  // a range shorter than its head is all head
+    const uint32_t nvec = (nbytes - head) / 16;
+    return {head, nvec, head + 16 * nvec};
+}
+
+// f(i) in the thread that owns byte i of the range's head (threads 0..15) or tail (threads 16..31), if tid owns one.
+// A callback, not an index to test: the kernels then compile to the two-branch code they had with the walk written out.
+template <class F>
+__device__ __forceinline__ void for_edge_byte(const ByteRange& r, uint32_t nbytes, int tid, F f)
+{
+    if ((uint32_t)tid < r.head)
+        f((uint32_t)tid);
+    else if (tid >= 16 && tid < 32 && r.body_end + (uint32_t)(tid - 16) < nbytes)
+        f(r.body_end + (uint32_t)(tid - 16));
+}
+
+// the sum of every bin of the wave below lane's four, hv: the inclusive scan of the per-lane sums, less the lane's own
+__device__ __forceinline__ uint32_t bins_below(const u32x4& hv, int lane)
+{
+    const uint32_t lsum = hv.x + hv.y + hv.z + hv.w;
+    uint32_t inc = lsum;
+#pragma unroll
+    for (int d = 1; d < kWave; d *= 2) {
+        const uint32_t o = __shfl_up(inc, d);
+        if (lane >= d)
+            inc += o;
+    }
+    return inc - lsum;
+}
+
+// a table entry from a cumulative count: (float)count * scale, cvRound, saturated to a byte
+__device__ __forceinline__ uint32_t table_byte(uint32_t count, float scale)
+{
+    const float v = __builtin_rintf((float)(int)count * scale);
+    return v >= 255.0f ? 255u : (uint32_t)v;
 }
 
 }  // namespace mi355
