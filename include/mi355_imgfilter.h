@@ -648,6 +648,55 @@ int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, i
 int mi355_clahe_luts_gray8_dev(mi355_ctx* ctx, const void* d_in, uint8_t* d_luts, int w, int h, int nframes,
                                double clip_limit, int tiles_x, int tiles_y);
 
+/* ---- the blobs of a mask: cv::connectedComponentsWithStats(mask, labels, stats, centroids, connectivity, CV_32S) --------
+ * Connected-component labelling of gray8 masks, with the per-label boxes, areas and coordinate sums.  gray8 frames only
+ * (the single-channel rules: tightly packed, any byte alignment, any width >= 1, frames are independent,
+ * MI355_ERR_UNSUPPORTED under MI355_INPUT_BGR in the host form).  Entry points of their own, not filter ids: the outputs
+ * do not fit (k, sigma).  OpenCV is not installed where this library is built and tested: nobody has compared these
+ * calls with an OpenCV build; the rules below — not OpenCV — are the contract.  Everything is integer arithmetic.
+ * Foreground.  A pixel is foreground iff its byte is not zero.
+ * Connectivity.  4: left, right, up, down.  8: the four diagonals as well.  Row ends do not wrap: (w - 1, y) and
+ * (0, y + 1) are not neighbours; nor are the last row of frame f and the first row of frame f + 1.
+ * Labels.  int32 d_labels[nframes][h][w].  Background is 0.  The components of a frame are numbered 1 .. N - 1 in raster
+ * order of their first pixel: component A has a smaller number than component B iff the smallest y * w + x in A is
+ * smaller than the smallest in B.  One right answer per input, the same bits on every run and for every work
+ * decomposition; it is what scipy.ndimage.label produces.  OpenCV numbers components in the order in which its
+ * block-based scan creates provisional labels, so its labels may be a PERMUTATION of these; the partition of the pixels
+ * into components, and therefore the set of stats rows, is the same.
+ * Count.  int32 d_count[nframes] = N, the number of labels including the background: the value
+ * cv::connectedComponents returns.  An all-background frame has N = 1.
+ * Statistics (optional).  stats_rows is the number of rows per frame; 0: none, and d_stats and d_sums may be NULL.  Row l
+ * describes label l; row 0 is the background, as in OpenCV.
+ *     int32  d_stats[nframes][stats_rows][5] = {left, top, width, height, area}        (CC_STAT_LEFT .. CC_STAT_AREA)
+ *     uint64 d_sums[nframes][stats_rows][2]  = {sum of x, sum of y} over the label's pixels
+ * The centroid is ((double)sum_x / (double)area, (double)sum_y / (double)area), taken on the host: no floating-point sum
+ * runs on the device, so nothing depends on the order in which pixels arrive.  A row whose label has no pixel (l >= N,
+ * or row 0 of an all-foreground frame) is five zeros and two zeros: every byte of both buffers is defined.  Labels
+ * >= stats_rows are still labelled and counted; they have no row.  Compare d_count with stats_rows to see a truncation.
+ * MI355_ERR_BAD_ARG, before any device work: a null context or pointer (d_stats and d_sums only when stats_rows > 0);
+ * sizes the histogram calls reject (w * h >= 2^31 among them: a provisional label is a pixel index plus one in an
+ * int32); a connectivity other than 4 or 8; stats_rows < 0 or > MI355_MAX_CCL_STATS_ROWS; a d_labels, d_count or d_stats
+ * that is not 4-byte aligned; a d_sums that is not 8-byte aligned; an output range that overlaps the input or another
+ * output.
+ *   mi355_ccl_check          pure host function returning the code a call with these values returns before any device work.
+ *   mi355_ccl_gray8_dev      the rules of mi355_filter_dev: up to eight launches on the context's stream, no
+ *                            synchronisation.  d_labels itself is the union-find parent array; nothing else is kept per
+ *                            pixel.  The scratch, 4 bytes per 2048 pixels (per-block component counts, then their
+ *                            offsets), is pooled in the context: after the first call for a given (w, h, nframes) a call
+ *                            allocates nothing and waits for nothing, so it can be captured into a hipGraph.
+ *   mi355_ccl_gray8_batched  host buffers: H2D, the launches, D2H through the context's pooled buffers; prof_ns (may be
+ *                            NULL) gets the six timestamps of mi355_filter_batched.  The copies of count, stats and sums
+ *                            are enqueued ahead of the labels' and fall into the kernel interval.
+ * Not offered: CV_16U labels, OpenCV's exact label permutation, contours, moments beyond the first, per-label pixel
+ * lists, RGBA input, the streamed and group forms, row pitch and ROI. */
+#define MI355_MAX_CCL_STATS_ROWS 16777216 /* 2^24 */
+int mi355_ccl_check(int w, int h, int nframes, int connectivity, int stats_rows);
+int mi355_ccl_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_labels, int32_t* d_count, int32_t* d_stats,
+                        uint64_t* d_sums, int w, int h, int nframes, int connectivity, int stats_rows);
+int mi355_ccl_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t* labels, int32_t* count, int32_t* stats,
+                            uint64_t* sums, int w, int h, int nframes, int connectivity, int stats_rows,
+                            uint64_t prof_ns[6]);
+
 /* ---- frames from a decoder or a camera: 8-bit YUV <-> RGBA, cv::cvtColor(COLOR_YUV2RGBA_* / COLOR_RGBA2YUV_*) --------
  * The video decoder writes NV12 surfaces with a pitch, software decoders write I420, webcams deliver YUY2, and an
  * encoder wants NV12 or I420 back.  These calls are the first and the last step of a chain that stays on the device:

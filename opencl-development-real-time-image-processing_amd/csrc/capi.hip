@@ -54,6 +54,7 @@ struct mi355_ctx {
     DevBuf d_flags = {};  // per-work-item flags of the two-kernel Gaussian (gauss_wide.hip)
     DevBuf d_hist = {};   // per-frame 256-bin histograms of EQUALIZE_GRAY8 / OTSU_GRAY8 (hist.hip)
     DevBuf d_lut = {};    // their per-frame 256-byte tables
+    DevBuf d_ccl = {};    // per-block component counts, then offsets, of the labelling calls (ccl.hip)
     DevBuf d_map1 = {}, d_map2 = {};  // the maps of mi355_remap_batched
     unsigned long long* d_acc = nullptr;
     float* d_img_table = nullptr;  // image2d-mode Gaussian table (k*k floats, MI355_MAX_GAUSS_K^2 capacity)
@@ -844,7 +845,7 @@ MI355_API int mi355_ctx_destroy(mi355_ctx* ctx)
     for (void* p : ctx->pinned)
         (void)hipHostFree(p);
     for (void* p : {(void*)ctx->d_acc, (void*)ctx->d_img_table, ctx->d_in.p, ctx->d_out.p, ctx->d_raw.p, ctx->d_flags.p,
-                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_map1.p, ctx->d_map2.p})
+                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_ccl.p, ctx->d_map1.p, ctx->d_map2.p})
         if (p)
             (void)hipFree(p);
     for (int i = 0; i < mi355_ctx::kSlots; i++) {
@@ -1611,6 +1612,108 @@ MI355_API int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8
         return rc;
     return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
         return mi355_clahe_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, clip_limit, tiles_x, tiles_y);
+    });
+}
+
+// ---- the blobs of a mask ---------------------------------------------------------------------------------------------
+// What a labelling call writes: byte counts of the four outputs for values that passed ccl_values
+struct CclBytes {
+    size_t in, labels, count, stats, sums;
+};
+
+// The value checks of every labelling call (include/mi355_imgfilter.h, "the blobs of a mask")
+static int ccl_values(int w, int h, int nframes, int connectivity, int stats_rows, CclBytes* nb)
+{
+    static_assert(MI355_MAX_CCL_STATS_ROWS == kCclMaxStatsRows, "the header's limit is the kernels' limit");
+    const int rc = check_filter(MI355_FILTER_EQUALIZE_GRAY8, w, h, nframes, 0, 0.0f, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    if ((connectivity != 4 && connectivity != 8) || stats_rows < 0 || stats_rows > MI355_MAX_CCL_STATS_ROWS)
+        return MI355_ERR_BAD_ARG;
+    if (nb) {
+        const size_t px = (size_t)w * h * nframes, rows = (size_t)nframes * (size_t)stats_rows;
+        *nb = {px, px * sizeof(int32_t), (size_t)nframes * sizeof(int32_t), rows * 5 * sizeof(int32_t),
+               rows * 2 * sizeof(uint64_t)};
+    }
+    return MI355_OK;
+}
+
+MI355_API int mi355_ccl_check(int w, int h, int nframes, int connectivity, int stats_rows)
+{
+    return ccl_values(w, h, nframes, connectivity, stats_rows, nullptr);
+}
+
+MI355_API int mi355_ccl_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_labels, int32_t* d_count,
+                                  int32_t* d_stats, uint64_t* d_sums, int w, int h, int nframes, int connectivity,
+                                  int stats_rows)
+{
+    if (!ctx || !d_in || !d_labels || !d_count)
+        return MI355_ERR_BAD_ARG;
+    CclBytes nb;
+    const int rc = ccl_values(w, h, nframes, connectivity, stats_rows, &nb);
+    if (rc != MI355_OK)
+        return rc;
+    if (stats_rows > 0 && (!d_stats || !d_sums))
+        return MI355_ERR_BAD_ARG;
+    // the ranges in play: the input and the outputs this call writes
+    const void* ptr[5] = {d_in, d_labels, d_count, d_stats, d_sums};
+    const size_t len[5] = {nb.in, nb.labels, nb.count, nb.stats, nb.sums};
+    const uintptr_t align[5] = {1, 4, 4, 4, 8};
+    const int n = stats_rows > 0 ? 5 : 3;
+    for (int i = 0; i < n; i++) {
+        if (reinterpret_cast<uintptr_t>(ptr[i]) & (align[i] - 1))
+            return MI355_ERR_BAD_ARG;
+        for (int j = 0; j < i; j++)
+            if (overlap(ptr[i], len[i], ptr[j], len[j]))
+                return MI355_ERR_BAD_ARG;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int erc = ensure(ctx, ctx->d_ccl, ccl_scratch_bytes(w, h, nframes));
+    if (erc != MI355_OK)
+        return erc;
+    HIP_TRY(ctx, launch_ccl(ctx->stream, static_cast<const uint8_t*>(d_in), d_labels, d_count, d_stats, d_sums,
+                            static_cast<uint32_t*>(ctx->d_ccl.p), w, h, nframes, connectivity == 8, stats_rows));
+    return MI355_OK;
+}
+
+MI355_API int mi355_ccl_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t* labels, int32_t* count,
+                                      int32_t* stats, uint64_t* sums, int w, int h, int nframes, int connectivity,
+                                      int stats_rows, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !labels || !count)
+        return MI355_ERR_BAD_ARG;
+    CclBytes nb;
+    int rc = ccl_values(w, h, nframes, connectivity, stats_rows, &nb);
+    if (rc != MI355_OK)
+        return rc;
+    if (stats_rows > 0 && (!stats || !sums))
+        return MI355_ERR_BAD_ARG;
+    // the four outputs side by side in the pooled output buffer, the sums on an 8-byte boundary
+    const size_t at_count = nb.labels, at_stats = at_count + nb.count;
+    const size_t at_sums = (at_stats + nb.stats + 7) & ~(size_t)7;
+    HostIO io;
+    rc = stage_host(ctx, nb.in, 1, at_sums + nb.sums, &io);  // BGR input: unsupported
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_ccl, ccl_scratch_bytes(w, h, nframes));  // outside the timed window
+    if (rc != MI355_OK)
+        return rc;
+    io.out_bytes = nb.labels;  // what the round trip reads back behind the kernels; the small outputs go ahead of it
+    uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out.p);
+    return timed_roundtrip(ctx, io, in, reinterpret_cast<uint8_t*>(labels), prof_ns, [&] {
+        const int lrc = mi355_ccl_gray8_dev(ctx, ctx->d_in.p, reinterpret_cast<int32_t*>(d_out),
+                                            reinterpret_cast<int32_t*>(d_out + at_count),
+                                            stats_rows ? reinterpret_cast<int32_t*>(d_out + at_stats) : nullptr,
+                                            stats_rows ? reinterpret_cast<uint64_t*>(d_out + at_sums) : nullptr, w, h,
+                                            nframes, connectivity, stats_rows);
+        if (lrc != MI355_OK)
+            return lrc;
+        // the few rows that leave the device beside the labels: enqueued here, so they count as kernel time
+        HIP_TRY(ctx, hipMemcpyAsync(count, d_out + at_count, nb.count, hipMemcpyDeviceToHost, ctx->stream));
+        if (stats_rows) {
+            HIP_TRY(ctx, hipMemcpyAsync(stats, d_out + at_stats, nb.stats, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(sums, d_out + at_sums, nb.sums, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        return (int)MI355_OK;
     });
 }
 

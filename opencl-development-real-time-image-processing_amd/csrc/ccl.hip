@@ -1,0 +1,593 @@
+// ccl.hip — connected-component labelling with statistics of single-channel masks
+// (cv::connectedComponentsWithStats(mask, labels, stats, centroids, connectivity, CV_32S)).  Semantics:
+// include/mi355_imgfilter.h, "the blobs of a mask"; design, loop bounds and the staleness argument: DESIGN.md section 6j.
+//
+// The int32 label output is the union-find parent array from the first launch to the last; the only scratch is one
+// count (then offset) per kCclFlatPx pixels.  A pixel's entry holds a LABEL VALUE v = (index of another pixel of the
+// same frame and component) + 1, never larger than the pixel's own index + 1; a root holds its own index + 1;
+// background holds 0.  Kernel boundaries are the only ordering between workgroups: no flag, no grid barrier, no ticket.
+//   ccl_local_kernel     a block owns a 64 x 32 tile: row masks in LDS from 16-byte aligned vectors of the source (a
+//                        row is at any alignment: chunks the row does not cover whole go byte by byte), every pixel
+//                        starts at the first pixel of its row run (bit operations on the 64-bit row mask), runs of
+//                        neighbouring rows are united in LDS, and every pixel stores its tile root's value;
+//   ccl_seam_kernel      one thread per pixel of a tile's top row or left column (not the frame's): unions with the
+//                        foreground neighbours across the border, in global memory, agent-scope atomics only;
+//   ccl_compress_kernel  the same threads and the pixel opposite each: parent[q] and parent[parent[q]] take q's root.
+//                        Only tile roots ever get a new parent in the seam launch, and a tile root with a new parent
+//                        has a border pixel in its tile component, so afterwards EVERY tile root holds its root;
+//   ccl_flatten_kernel   a block owns kCclFlatPx raster-consecutive pixels: two loads give a pixel its root (no walk);
+//                        a root takes -(its rank among the roots of the block + 1) instead, the block stores its count;
+//   ccl_scan_kernel      one block per frame: counts -> exclusive offsets, in place, and the frame's N;
+//   ccl_relabel_kernel   final number = block offset + rank + 1 from the root's entry; with statistics every wave
+//                        finds its row runs of equal labels (one accumulate per run, closed-form sums), a block merges
+//                        runs in a 64-slot LDS table and adds each occupied slot once to the global row;
+//   ccl_stats_init / _finish   the accumulators' identities before, {left, top, width, height, area} and the empty rows
+//                        after.
+#include "common.hpp"
+#include "hist_common.hpp"
+#include "kernels.hpp"
+
+namespace mi355 {
+
+namespace {
+
+constexpr int kTileW = 64;  // one wave lane per tile column: a tile row's foreground is one 64-bit mask
+constexpr int kTileH = 32;
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kRowsPerWave = kTileH / kWaves;
+constexpr int kRowChunks = kTileW / 16 + 1;  // 16-byte aligned chunks that 64 bytes at any alignment can touch
+constexpr int kFlatIters = kCclFlatPx / kThreads;  // a wave owns kFlatIters x 64 consecutive pixels of a flat block
+constexpr int kSlots = 64;                         // of a block's LDS statistics table
+static_assert(kTileW == kWave && kTileH * kRowChunks <= kThreads && kCclFlatPx % kThreads == 0, "tile geometry");
+
+#define CCL_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
+#define CCL_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+struct CclGeom {
+    uint32_t w, h, npx;  // npx = w h < 2^31
+    uint32_t ntx, nty;   // tiles per frame
+    uint32_t seam_h;     // (nty - 1) w: the pixels of the tiles' top rows, the frame's first row apart
+    uint32_t seam;       // seam_h + (ntx - 1) h: with the pixels of the tiles' left columns
+    uint32_t nflat;      // flat blocks per frame
+};
+
+// ---- the tile in LDS ----------------------------------------------------------------------------------------------------
+// bound: the walk goes to strictly smaller indices, fewer than kTileW kTileH steps
+__device__ __forceinline__ uint32_t lds_find(uint32_t* lab, uint32_t a)
+{
+    for (;;) {
+        const uint32_t p = __hip_atomic_load(lab + a, CCL_WG);
+        if (p == a)
+            return a;
+        a = p;
+    }
+}
+
+// bound: max(a, b) strictly decreases with every trip, fewer than kTileW kTileH trips
+__device__ __forceinline__ void lds_union(uint32_t* lab, uint32_t a, uint32_t b)
+{
+    a = lds_find(lab, a);
+    b = lds_find(lab, b);
+    while (a != b) {
+        if (a < b) {
+            const uint32_t t = a;
+            a = b;
+            b = t;
+        }
+        const uint32_t old = __hip_atomic_fetch_min(lab + a, b, CCL_WG);
+        if (old == a)
+            break;
+        a = old;
+    }
+}
+
+__device__ __forceinline__ uint64_t row_mask(const uint32_t* smask, int r)
+{
+    return (uint64_t)smask[2 * r] | ((uint64_t)smask[2 * r + 1] << 32);
+}
+
+__global__ __launch_bounds__(kThreads) void ccl_local_kernel(const uint8_t* __restrict__ in, int32_t* __restrict__ labels,
+                                                             CclGeom g, int conn8)
+{
+    __shared__ uint32_t smask[kTileH * 2];
+    __shared__ uint32_t lab[kTileH * kTileW];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    const uint32_t tiles = g.ntx * g.nty;
+    const uint32_t f = blockIdx.x / tiles, t = blockIdx.x - f * tiles;
+    const uint32_t tj = t / g.ntx, ti = t - tj * g.ntx;
+    const uint32_t x0 = ti * kTileW, y0 = tj * kTileH;
+    const int n = (int)(g.w - x0 < (uint32_t)kTileW ? g.w - x0 : (uint32_t)kTileW);     // columns of the frame
+    const int rows = (int)(g.h - y0 < (uint32_t)kTileH ? g.h - y0 : (uint32_t)kTileH);  // rows of the frame
+    const uint8_t* p = in + (size_t)f * g.npx;
+    if (tid < kTileH * 2)
+        smask[tid] = 0;
+    __syncthreads();
+    // the foreground bits of (row r, aligned chunk s)
+    if (tid < kTileH * kRowChunks) {
+        const int r = tid / kRowChunks, s = tid - r * kRowChunks;
+        if (r < rows) {
+            const uint8_t* row = p + (size_t)(y0 + (uint32_t)r) * g.w + x0;
+            const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15u);
+            const int c0 = 16 * s - mis;  // the chunk is bytes c0 .. c0 + 15 of the row's n bytes
+            const int b0 = c0 > 0 ? c0 : 0, b1 = c0 + 16 < n ? c0 + 16 : n;
+            uint32_t bits = 0;  // bit i: byte b0 + i is not zero
+            if (b1 - b0 == 16) {
+                const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + c0));
+#pragma unroll
+                for (int d = 0; d < 4; d++)
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        bits |= (((v[d] >> (8 * e)) & 0xFFu) ? 1u : 0u) << (4 * d + e);
+            } else {
+                for (int b = b0; b < b1; b++)  // bound: fewer than 16 bytes
+                    bits |= (row[b] ? 1u : 0u) << (b - b0);
+            }
+            if (bits) {
+                const uint64_t m = (uint64_t)bits << b0;
+                if ((uint32_t)m)
+                    __hip_atomic_fetch_or(smask + 2 * r, (uint32_t)m, CCL_WG);
+                if ((uint32_t)(m >> 32))
+                    __hip_atomic_fetch_or(smask + 2 * r + 1, (uint32_t)(m >> 32), CCL_WG);
+            }
+        }
+    }
+    __syncthreads();
+    // every pixel starts at the first pixel of its row run
+#pragma unroll
+    for (int i = 0; i < kRowsPerWave; i++) {
+        const int r = wv + kWaves * i;
+        const uint64_t m = row_mask(smask, r);
+        const uint64_t z = ~m & ((1ull << lane) - 1);  // the background pixels left of the lane
+        const int start = z ? 64 - __clzll((long long)z) : 0;
+        lab[r * kTileW + lane] = (uint32_t)(r * kTileW + start);
+    }
+    __syncthreads();
+    // unite the runs of neighbouring rows: once per pair of runs where the row masks show that a left neighbour does it
+#pragma unroll
+    for (int i = 0; i < kRowsPerWave; i++) {
+        const int r = wv + kWaves * i;
+        if (r == 0)
+            continue;
+        const uint64_t cur = row_mask(smask, r), up = row_mask(smask, r - 1);
+        if (!((cur >> lane) & 1u))
+            continue;
+        const bool c_l = lane > 0 && ((cur >> (lane - 1)) & 1u), c_r = lane < 63 && ((cur >> (lane + 1)) & 1u);
+        const bool u_l = lane > 0 && ((up >> (lane - 1)) & 1u), u_r = lane < 63 && ((up >> (lane + 1)) & 1u);
+        const uint32_t me = (uint32_t)(r * kTileW + lane), above = me - kTileW;
+        if ((up >> lane) & 1u) {
+            if (!(c_l && u_l))
+                lds_union(lab, me, above);
+        } else if (conn8) {
+            // the pixel above is background: the two diagonal neighbours are in runs of their own
+            if (u_l && !c_l)
+                lds_union(lab, me, above - 1);
+            if (u_r && !c_r)
+                lds_union(lab, me, above + 1);
+        }
+    }
+    __syncthreads();
+    int32_t* out = labels + (size_t)f * g.npx;
+#pragma unroll
+    for (int i = 0; i < kRowsPerWave; i++) {
+        const int r = wv + kWaves * i;
+        if (r >= rows || lane >= n)
+            continue;
+        int32_t v = 0;
+        if ((row_mask(smask, r) >> lane) & 1u) {
+            const uint32_t root = lds_find(lab, (uint32_t)(r * kTileW + lane));
+            v = (int32_t)((y0 + root / kTileW) * g.w + x0 + (root & (kTileW - 1)) + 1u);
+        }
+        out[(size_t)(y0 + (uint32_t)r) * g.w + x0 + (uint32_t)lane] = v;
+    }
+}
+
+// ---- the parent array in global memory while other workgroups write it ----------------------------------------------------
+// bound: the walk goes to strictly smaller values, fewer than w h steps.  A value read late or early is still an
+// ancestor: an entry only ever decreases, and only to an ancestor of what it held
+__device__ __forceinline__ int32_t agent_find(int32_t* lab, int32_t v)
+{
+    for (;;) {
+        const int32_t nx = __hip_atomic_load(lab + (v - 1), CCL_AGENT);
+        if (nx == v)
+            return v;
+        v = nx;
+    }
+}
+
+// bound: max(a, b) strictly decreases with every trip, fewer than w h trips; no compare-and-swap, nothing is retried
+__device__ __forceinline__ void agent_union(int32_t* lab, int32_t a, int32_t b)
+{
+    a = agent_find(lab, a);
+    b = agent_find(lab, b);
+    while (a != b) {
+        if (a < b) {
+            const int32_t t = a;
+            a = b;
+            b = t;
+        }
+        const int32_t old = __hip_atomic_fetch_min(lab + (a - 1), b, CCL_AGENT);
+        if (old == a)
+            break;
+        a = old;
+    }
+}
+
+// The seam pixel of item i of a frame: (x, y) in the top row of a tile (horizontal = true, y > 0) or in the left column
+// of a tile (x > 0).  A tile's corner pixel appears once as each.
+__device__ __forceinline__ void seam_pixel(const CclGeom& g, uint32_t i, bool* horizontal, uint32_t* x, uint32_t* y)
+{
+    if (i < g.seam_h) {
+        const uint32_t k = i / g.w;
+        *horizontal = true;
+        *x = i - k * g.w;
+        *y = (k + 1) * kTileH;
+    } else {
+        const uint32_t j = i - g.seam_h, k = j / g.h;
+        *horizontal = false;
+        *x = (k + 1) * kTileW;
+        *y = j - k * g.h;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void ccl_seam_kernel(const uint8_t* __restrict__ in, int32_t* labels, CclGeom g,
+                                                            uint32_t bpf, int conn8)
+{
+    const uint32_t f = blockIdx.x / bpf, i = (blockIdx.x - f * bpf) * kThreads + threadIdx.x;
+    if (i >= g.seam)
+        return;
+    bool hor;
+    uint32_t x, y;
+    seam_pixel(g, i, &hor, &x, &y);
+    const uint8_t* p = in + (size_t)f * g.npx;
+    int32_t* lab = labels + (size_t)f * g.npx;
+    const uint32_t w = g.w, at = y * w + x;
+    if (!p[at])
+        return;
+    const int32_t me = (int32_t)at + 1;
+    if (hor) {
+        // the row above belongs to another tile: the local kernel's rule, on the frame's rows
+        const bool c_l = x > 0 && p[at - 1], c_r = x + 1 < w && p[at + 1];
+        const bool u_l = x > 0 && p[at - w - 1], u_r = x + 1 < w && p[at - w + 1];
+        if (p[at - w]) {
+            if (!(c_l && u_l))
+                agent_union(lab, me, me - (int32_t)w);
+        } else if (conn8) {
+            if (u_l && !c_l)
+                agent_union(lab, me, me - (int32_t)w - 1);
+            if (u_r && !c_r)
+                agent_union(lab, me, me - (int32_t)w + 1);
+        }
+    } else {
+        // the column on the left belongs to another tile; the pair one row up does it when both its pixels are set and
+        // the local kernel has united this pixel with the one above it (a tile's top row is united with the row above
+        // by the branch above, which may itself count on this union: no skipping there)
+        if (p[at - 1]) {
+            if (!(y % kTileH != 0 && p[at - w] && p[at - w - 1]))
+                agent_union(lab, me, me - 1);
+        } else if (conn8) {
+            if (y > 0 && p[at - w - 1] && !p[at - w])
+                agent_union(lab, me, me - (int32_t)w - 1);
+            if (y + 1 < g.h && p[at + w - 1] && !p[at + w])
+                agent_union(lab, me, me + (int32_t)w - 1);
+        }
+    }
+}
+
+// parent[q] and parent[parent[q]] take q's root.  No union runs in this launch, so a root stays a root and every store
+// writes the one final value of its entry; concurrent readers see the old ancestor or the root
+__device__ __forceinline__ void compress_pixel(int32_t* lab, uint32_t q)
+{
+    const int32_t a = __hip_atomic_load(lab + q, CCL_AGENT);
+    const int32_t r = agent_find(lab, a);
+    if (a != r)
+        __hip_atomic_store(lab + (a - 1), r, CCL_AGENT);
+    if (a != r)
+        __hip_atomic_store(lab + q, r, CCL_AGENT);
+}
+
+__global__ __launch_bounds__(kThreads) void ccl_compress_kernel(const uint8_t* __restrict__ in, int32_t* labels,
+                                                                CclGeom g, uint32_t bpf)
+{
+    const uint32_t f = blockIdx.x / bpf, i = (blockIdx.x - f * bpf) * kThreads + threadIdx.x;
+    if (i >= g.seam)
+        return;
+    bool hor;
+    uint32_t x, y;
+    seam_pixel(g, i, &hor, &x, &y);
+    const uint8_t* p = in + (size_t)f * g.npx;
+    int32_t* lab = labels + (size_t)f * g.npx;
+    const uint32_t at = y * g.w + x, opposite = hor ? at - g.w : at - 1;
+    if (p[at])
+        compress_pixel(lab, at);
+    if (p[opposite])
+        compress_pixel(lab, opposite);
+}
+
+// ---- flat blocks: kCclFlatPx raster-consecutive pixels, a wave kFlatIters x 64 of them in order -------------------------
+__device__ __forceinline__ uint32_t flat_pixel(uint32_t b, int wv, int i, int lane)
+{
+    return b * kCclFlatPx + (uint32_t)((wv * kFlatIters + i) * kWave + lane);
+}
+
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m, int lane)
+{
+    return (uint32_t)__popcll(m & ((1ull << lane) - 1));
+}
+
+__global__ __launch_bounds__(kThreads) void ccl_flatten_kernel(int32_t* labels, uint32_t* __restrict__ counts, CclGeom g)
+{
+    __shared__ uint32_t s_cnt[kWaves];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    const uint32_t f = blockIdx.x / g.nflat, b = blockIdx.x - f * g.nflat;
+    int32_t* lab = labels + (size_t)f * g.npx;
+    int rank[kFlatIters];  // of the roots among the wave's roots, -1: not a root
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int i = 0; i < kFlatIters; i++) {
+        const uint32_t px = flat_pixel(b, wv, i, lane);
+        bool is_root = false;
+        if (px < g.npx) {
+            // only this thread writes lab[px]; lab[a - 1] is a tile root's entry: its root since the compress launch, or
+            // itself, or already its rank (negative) if it is a root of this launch
+            const int32_t a = lab[px];
+            if (a > 0) {
+                const int32_t v = __hip_atomic_load(lab + (a - 1), CCL_WG);
+                const int32_t root = v < 0 ? a : v;
+                is_root = root == (int32_t)px + 1;
+                if (!is_root && root != a)
+                    __hip_atomic_store(lab + px, root, CCL_WG);
+            }
+        }
+        const uint64_t m = __ballot(is_root);
+        rank[i] = is_root ? (int)(cnt + lanes_below(m, lane)) : -1;
+        cnt += (uint32_t)__popcll(m);
+    }
+    if (lane == 0)
+        s_cnt[wv] = cnt;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; k++) {
+        before += k < wv ? s_cnt[k] : 0;
+        total += s_cnt[k];
+    }
+#pragma unroll
+    for (int i = 0; i < kFlatIters; i++)
+        if (rank[i] >= 0)
+            __hip_atomic_store(lab + flat_pixel(b, wv, i, lane), -(int32_t)(before + (uint32_t)rank[i] + 1u), CCL_WG);
+    if (tid == 0)
+        counts[(size_t)f * g.nflat + b] = total;
+}
+
+// one block per frame: the frame's block counts become exclusive offsets in place; N = the roots + 1 (the background)
+__global__ __launch_bounds__(kThreads) void ccl_scan_kernel(uint32_t* __restrict__ counts, int32_t* __restrict__ count,
+                                                            uint32_t nflat)
+{
+    __shared__ uint32_t s_sum[kWaves];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    uint32_t* c = counts + (size_t)blockIdx.x * nflat;
+    uint32_t carry = 0;
+    for (uint32_t k0 = 0; k0 < nflat; k0 += kThreads) {  // bound: nflat / 256 trips, rounded up
+        const uint32_t k = k0 + tid;
+        const uint32_t own = k < nflat ? c[k] : 0;
+        uint32_t inc = own;
+#pragma unroll
+        for (int d = 1; d < kWave; d *= 2) {
+            const uint32_t o = __shfl_up(inc, d);
+            if (lane >= d)
+                inc += o;
+        }
+        if (lane == kWave - 1)
+            s_sum[wv] = inc;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (int j = 0; j < kWaves; j++) {
+            before += j < wv ? s_sum[j] : 0;
+            total += s_sum[j];
+        }
+        if (k < nflat)
+            c[k] = carry + before + inc - own;
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0)
+        count[blockIdx.x] = (int32_t)(carry + 1u);
+}
+
+// ---- statistics -----------------------------------------------------------------------------------------------------------
+// While they accumulate, a row of d_stats is {min x, min y, max x, max y, area} and a row of d_sums {sum x, sum y}.
+struct RunStats {
+    int x0, x1, y;
+    uint32_t n;
+    uint64_t sx, sy;
+};
+
+__device__ __forceinline__ void stats_to_global(int32_t* st, unsigned long long* sm, int minx, int miny, int maxx,
+                                                int maxy, uint32_t area, uint64_t sx, uint64_t sy)
+{
+    __hip_atomic_fetch_min(st + 0, minx, CCL_AGENT);
+    __hip_atomic_fetch_min(st + 1, miny, CCL_AGENT);
+    __hip_atomic_fetch_max(st + 2, maxx, CCL_AGENT);
+    __hip_atomic_fetch_max(st + 3, maxy, CCL_AGENT);
+    __hip_atomic_fetch_add(st + 4, (int32_t)area, CCL_AGENT);
+    __hip_atomic_fetch_add(sm + 0, (unsigned long long)sx, CCL_AGENT);
+    __hip_atomic_fetch_add(sm + 1, (unsigned long long)sy, CCL_AGENT);
+}
+
+struct BlockStats {
+    int32_t key[kSlots];  // the slot's label, -1: free
+    int32_t minx[kSlots], miny[kSlots], maxx[kSlots], maxy[kSlots];
+    uint32_t area[kSlots];
+    unsigned long long sx[kSlots], sy[kSlots];
+};
+
+template <bool kStats>
+__global__ __launch_bounds__(kThreads) void ccl_relabel_kernel(int32_t* labels, const uint32_t* __restrict__ offsets,
+                                                               int32_t* stats, unsigned long long* sums, CclGeom g,
+                                                               uint32_t stats_rows)
+{
+    __shared__ BlockStats bs;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    const uint32_t f = blockIdx.x / g.nflat, b = blockIdx.x - f * g.nflat;
+    int32_t* lab = labels + (size_t)f * g.npx;
+    const uint32_t* offs = offsets + (size_t)f * g.nflat;
+    int32_t* st = kStats ? stats + (size_t)f * stats_rows * 5 : nullptr;
+    unsigned long long* sm = kStats ? sums + (size_t)f * stats_rows * 2 : nullptr;
+    if (kStats) {
+        if (tid < kSlots) {
+            bs.key[tid] = -1;
+            bs.minx[tid] = bs.miny[tid] = 0x7FFFFFFF;
+            bs.maxx[tid] = bs.maxy[tid] = -1;
+            bs.area[tid] = 0;
+            bs.sx[tid] = bs.sy[tid] = 0;
+        }
+        __syncthreads();
+    }
+    const uint32_t own_off = offs[b];
+#pragma unroll 2
+    for (int i = 0; i < kFlatIters; i++) {
+        const uint32_t px = flat_pixel(b, wv, i, lane);
+        const bool valid = px < g.npx;
+        int32_t fin = 0;
+        if (valid) {
+            // only this thread writes lab[px].  A root's entry is its rank (negative) or, once its own thread has been
+            // here, its final number (positive): both give the same number
+            const int32_t a = lab[px];
+            if (a < 0) {
+                fin = (int32_t)own_off - a;
+            } else if (a > 0) {
+                const int32_t v = __hip_atomic_load(lab + (a - 1), CCL_WG);
+                fin = v < 0 ? (int32_t)offs[(uint32_t)(a - 1) / kCclFlatPx] - v : v;
+            }
+            if (a != 0)
+                __hip_atomic_store(lab + px, fin, CCL_WG);
+        }
+        if (!kStats)
+            continue;
+        // the wave's 64 pixels are consecutive: a run is a stretch of one label in one row, its first lane accumulates it
+        const uint32_t y = px / g.w, x = px - y * g.w;
+        const int32_t left = __shfl_up(fin, 1);
+        const bool head = valid && (lane == 0 || x == 0 || left != fin);
+        const uint64_t hm = __ballot(head);
+        const int nvalid = __popcll(__ballot(valid));  // the valid lanes are the first ones
+        if (!head || (uint32_t)fin >= stats_rows)
+            continue;
+        const uint64_t later = lane < 63 ? hm & ~((2ull << lane) - 1) : 0;
+        const uint32_t n = (uint32_t)((later ? __ffsll((long long)later) - 1 : nvalid) - lane);
+        const uint64_t sx = (uint64_t)n * x + (uint64_t)n * (n - 1) / 2, sy = (uint64_t)n * y;
+        const int x1 = (int)(x + n - 1);
+        const int s = fin & (kSlots - 1);
+        int32_t expected = -1;
+        const bool mine = __hip_atomic_compare_exchange_strong(&bs.key[s], &expected, fin, __ATOMIC_RELAXED,
+                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ||
+                          expected == fin;
+        if (mine) {
+            __hip_atomic_fetch_min(&bs.minx[s], (int32_t)x, CCL_WG);
+            __hip_atomic_fetch_min(&bs.miny[s], (int32_t)y, CCL_WG);
+            __hip_atomic_fetch_max(&bs.maxx[s], x1, CCL_WG);
+            __hip_atomic_fetch_max(&bs.maxy[s], (int32_t)y, CCL_WG);
+            __hip_atomic_fetch_add(&bs.area[s], n, CCL_WG);
+            __hip_atomic_fetch_add(&bs.sx[s], (unsigned long long)sx, CCL_WG);
+            __hip_atomic_fetch_add(&bs.sy[s], (unsigned long long)sy, CCL_WG);
+        } else {
+            // the slot holds another label of this block
+            stats_to_global(st + (size_t)fin * 5, sm + (size_t)fin * 2, (int)x, (int)y, x1, (int)y, n, sx, sy);
+        }
+    }
+    if (kStats) {
+        __syncthreads();
+        if (tid < kSlots && bs.key[tid] >= 0) {
+            const size_t l = (size_t)bs.key[tid];
+            stats_to_global(st + l * 5, sm + l * 2, bs.minx[tid], bs.miny[tid], bs.maxx[tid], bs.maxy[tid], bs.area[tid],
+                            bs.sx[tid], bs.sy[tid]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void ccl_stats_init_kernel(int32_t* __restrict__ stats,
+                                                                  unsigned long long* __restrict__ sums, uint64_t rows)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= rows)
+        return;
+    int32_t* st = stats + r * 5;
+    st[0] = st[1] = 0x7FFFFFFF;
+    st[2] = st[3] = -1;
+    st[4] = 0;
+    sums[r * 2] = sums[r * 2 + 1] = 0;
+}
+
+// {min x, min y, max x, max y, area} -> {left, top, width, height, area}; a row without a pixel is all zeros
+__global__ __launch_bounds__(kThreads) void ccl_stats_finish_kernel(int32_t* __restrict__ stats, uint64_t rows)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= rows)
+        return;
+    int32_t* st = stats + r * 5;
+    if (st[4] == 0) {
+        st[0] = st[1] = st[2] = st[3] = 0;
+    } else {
+        st[2] = st[2] - st[0] + 1;
+        st[3] = st[3] - st[1] + 1;
+    }
+}
+
+bool ccl_geom(int w, int h, int nframes, CclGeom* g)
+{
+    if (!hist_frames_ok(w, h, nframes))
+        return false;
+    const uint32_t uw = (uint32_t)w, uh = (uint32_t)h, npx = uw * uh;
+    const uint32_t ntx = (uw + kTileW - 1) / kTileW, nty = (uh + kTileH - 1) / kTileH;
+    const uint32_t seam_h = (nty - 1) * uw;
+    *g = {uw, uh, npx, ntx, nty, seam_h, seam_h + (ntx - 1) * uh, (npx + kCclFlatPx - 1) / kCclFlatPx};
+    return true;
+}
+
+}  // namespace
+
+size_t ccl_scratch_bytes(int w, int h, int nframes)
+{
+    CclGeom g;
+    return ccl_geom(w, h, nframes, &g) ? (size_t)nframes * g.nflat * sizeof(uint32_t) : 0;
+}
+
+hipError_t launch_ccl(hipStream_t stream, const uint8_t* d_in, int32_t* d_labels, int32_t* d_count, int32_t* d_stats,
+                      uint64_t* d_sums, uint32_t* d_scratch, int w, int h, int nframes, bool conn8, int stats_rows)
+{
+    CclGeom g;
+    if (!ccl_geom(w, h, nframes, &g) || stats_rows < 0 || stats_rows > kCclMaxStatsRows)
+        return hipErrorInvalidValue;
+    const uint64_t tiles = (uint64_t)nframes * g.ntx * g.nty;
+    const uint32_t seam_bpf = (g.seam + kThreads - 1) / kThreads;
+    const uint64_t seam_blocks = (uint64_t)nframes * seam_bpf, flat_blocks = (uint64_t)nframes * g.nflat;
+    const uint64_t rows = (uint64_t)nframes * (uint64_t)stats_rows, row_blocks = (rows + kThreads - 1) / kThreads;
+    if (!grid_fits(tiles) || !grid_fits(seam_blocks) || !grid_fits(flat_blocks) || !grid_fits(row_blocks))
+        return hipErrorInvalidValue;
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(d_sums);
+    if (rows)
+        hipLaunchKernelGGL(ccl_stats_init_kernel, dim3((uint32_t)row_blocks), dim3(kThreads), 0, stream, d_stats, sums,
+                           rows);
+    hipLaunchKernelGGL(ccl_local_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, stream, d_in, d_labels, g,
+                       conn8 ? 1 : 0);
+    if (g.seam) {
+        hipLaunchKernelGGL(ccl_seam_kernel, dim3((uint32_t)seam_blocks), dim3(kThreads), 0, stream, d_in, d_labels, g,
+                           seam_bpf, conn8 ? 1 : 0);
+        hipLaunchKernelGGL(ccl_compress_kernel, dim3((uint32_t)seam_blocks), dim3(kThreads), 0, stream, d_in, d_labels, g,
+                           seam_bpf);
+    }
+    hipLaunchKernelGGL(ccl_flatten_kernel, dim3((uint32_t)flat_blocks), dim3(kThreads), 0, stream, d_labels, d_scratch, g);
+    hipLaunchKernelGGL(ccl_scan_kernel, dim3((uint32_t)nframes), dim3(kThreads), 0, stream, d_scratch, d_count, g.nflat);
+    if (rows) {
+        hipLaunchKernelGGL(ccl_relabel_kernel<true>, dim3((uint32_t)flat_blocks), dim3(kThreads), 0, stream, d_labels,
+                           d_scratch, d_stats, sums, g, (uint32_t)stats_rows);
+        hipLaunchKernelGGL(ccl_stats_finish_kernel, dim3((uint32_t)row_blocks), dim3(kThreads), 0, stream, d_stats, rows);
+    } else {
+        hipLaunchKernelGGL(ccl_relabel_kernel<false>, dim3((uint32_t)flat_blocks), dim3(kThreads), 0, stream, d_labels,
+                           d_scratch, (int32_t*)nullptr, (unsigned long long*)nullptr, g, 0u);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace mi355

@@ -149,6 +149,18 @@ hipError_t launch_clahe_table(hipStream_t stream, const uint32_t* d_hist, uint8_
 hipError_t launch_clahe_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, const uint8_t* d_luts,
                               const ClaheGeom& g, int nframes);
 
+// cv::connectedComponentsWithStats of single-channel masks (ccl.hip; semantics: include/mi355_imgfilter.h, "the blobs of
+// a mask"): frames of w * h < 2^31 pixels at any byte alignment, a pixel is foreground iff its byte is not zero.
+// d_labels (int32 per pixel, 4-byte aligned) is the union-find parent array until the last launch; d_count takes N per
+// frame; d_scratch takes ccl_scratch_bytes(): one count, then offset, per kCclFlatPx raster-consecutive pixels, nothing
+// per pixel.  stats_rows 0 .. kCclMaxStatsRows rows per frame of d_stats (5 int32) and d_sums (2 uint64, 8-byte aligned),
+// both unused (may be null) when it is 0.  Up to eight launches on the stream, no allocation, no wait.
+constexpr int kCclFlatPx = 2048;
+constexpr int kCclMaxStatsRows = 1 << 24;
+size_t ccl_scratch_bytes(int w, int h, int nframes);  // 0 for sizes launch_ccl rejects
+hipError_t launch_ccl(hipStream_t stream, const uint8_t* d_in, int32_t* d_labels, int32_t* d_count, int32_t* d_stats,
+                      uint64_t* d_sums, uint32_t* d_scratch, int w, int h, int nframes, bool conn8, int stats_rows);
+
 // cv::resize of tightly packed 8-bit frames (resize.hip): bpp 4 (RGBA, dword-aligned) or 1 (gray8, any byte alignment);
 // interp 0 nearest, 1 linear (11-bit fixed point; AREA's result at exactly half size), 3 area with integer factors
 // 1 .. kResizeMaxAreaFactor (resize_area_factors says whether a size pair has them; anything else is

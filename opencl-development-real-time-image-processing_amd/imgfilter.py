@@ -39,6 +39,8 @@ MAX_BOX_K = 63
 ADAPTIVE_BINARY, ADAPTIVE_BINARY_INV = 0, 1
 # CLAHE (mi355_clahe_*): 1 <= tiles_x, tiles_y <= MAX_CLAHE_TILES
 MAX_CLAHE_TILES = 16
+# connected components (mi355_ccl_*): connectivity 4 or 8, 0 <= stats_rows <= MAX_CCL_STATS_ROWS
+MAX_CCL_STATS_ROWS = 1 << 24
 # cv::resize (mi355_resize_*): OpenCV's enum values; AREA only with integer factors 1 .. MAX_AREA_FACTOR
 INTERP_NEAREST, INTERP_LINEAR, INTERP_AREA = 0, 1, 3
 MAX_AREA_FACTOR = 16
@@ -180,6 +182,9 @@ def load_library(path=None):
         "mi355_clahe_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, _ci, _ci],
         "mi355_clahe_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, ctypes.c_double, _ci, _ci, _u64p],
         "mi355_clahe_luts_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, ctypes.c_double, _ci, _ci],
+        "mi355_ccl_check": [_ci, _ci, _ci, _ci, _ci],
+        "mi355_ccl_gray8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci],
+        "mi355_ccl_gray8_batched": [_vp, _u8p, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _u64p],
         "mi355_yuv_check": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_yuv_to_rgba8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_rgba8_to_yuv_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
@@ -370,6 +375,12 @@ def clahe_check(w, h, nframes=1, clip_limit=40.0, tiles_x=8, tiles_y=8):
     """mi355_clahe_check, a pure host function: the code (0 ok, -1 bad argument, -4 a pad one reflection cannot serve) a
     CLAHE call with these values returns before any device work."""
     return load_library().mi355_clahe_check(int(w), int(h), int(nframes), float(clip_limit), int(tiles_x), int(tiles_y))
+
+
+def ccl_check(w, h, nframes=1, connectivity=8, stats_rows=0):
+    """mi355_ccl_check, a pure host function: the code (0 ok, -1 bad argument) a labelling call with these values returns
+    before any device work."""
+    return load_library().mi355_ccl_check(int(w), int(h), int(nframes), int(connectivity), int(stats_rows))
 
 
 def yuv_frame_bytes(layout, w, h, pitch=0, rows=0):
@@ -605,6 +616,32 @@ class Context:
         _check("mi355_clahe_gray8_batched", rc, self._h)
         out = out[0] if one else out
         return (out, list(prof)) if profile else out
+
+    def ccl_gray8(self, mask, connectivity=8, stats_rows=0, profile=False):
+        """cv::connectedComponentsWithStats of (h, w) / (n, h, w) single-channel masks (mi355_ccl_gray8_batched): int32
+        labels numbered by first pixel and the label count N (background included; an int for one frame, else (n,)
+        int32).  With stats_rows > 0 also stats (stats_rows, 5) int32 {left, top, width, height, area} and centroids
+        (stats_rows, 2) float64 = coordinate sums / area, NaN for a row without a pixel; each with a leading n for a
+        batch.  Returns (labels, count) or (labels, count, stats, centroids); with profile, the six timestamps follow."""
+        frames, one = self._frames("ccl_gray8", mask, 1)
+        n, h, w = frames.shape
+        rows = int(stats_rows)
+        labels = np.empty((n, h, w), np.int32)
+        count = np.empty(n, np.int32)
+        stats = np.empty((n, max(rows, 0), 5), np.int32)
+        sums = np.empty((n, max(rows, 0), 2), np.uint64)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_ccl_gray8_batched(
+            self._h, frames.ctypes.data_as(_u8p), labels.ctypes.data_as(_vp), count.ctypes.data_as(_vp),
+            stats.ctypes.data_as(_vp) if rows > 0 else None, sums.ctypes.data_as(_vp) if rows > 0 else None, w, h, n,
+            int(connectivity), rows, prof if profile else None)
+        _check("mi355_ccl_gray8_batched", rc, self._h)
+        out = (labels[0], int(count[0])) if one else (labels, count)
+        if rows > 0:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                centroids = sums.astype(np.float64) / stats[:, :, 4:5].astype(np.float64)
+            out += (stats[0], centroids[0]) if one else (stats, centroids)
+        return out + (list(prof),) if profile else out
 
     # -- frames from a decoder or a camera (mi355_yuv_to_rgba8_batched / mi355_rgba8_to_yuv_batched) -----
     def yuv_to_rgba8(self, yuv, w, h, layout, standard=YUV_BT601, pitch=0, rows=0, profile=False):
@@ -881,6 +918,15 @@ class Context:
         rc = self._lib.mi355_clahe_luts_gray8_dev(self._h, _vp(int(d_in)), _vp(int(d_luts)), int(w), int(h),
                                                   int(nframes), float(clip_limit), int(tiles_x), int(tiles_y))
         _check("mi355_clahe_luts_gray8_dev", rc, self._h)
+
+    def ccl_gray8_dev(self, d_in, d_labels, d_count, d_stats, d_sums, w, h, nframes, connectivity=8, stats_rows=0):
+        """mi355_ccl_gray8_dev: labels (int32 per pixel) of nframes gray8 masks at d_in to d_labels, N per frame to
+        d_count, and with stats_rows > 0 that many rows per frame of 5 int32 to d_stats and 2 uint64 to d_sums (both may
+        be 0 / None otherwise); no synchronisation."""
+        rc = self._lib.mi355_ccl_gray8_dev(self._h, _vp(int(d_in or 0)), _vp(int(d_labels or 0)), _vp(int(d_count or 0)),
+                                           _vp(int(d_stats or 0)), _vp(int(d_sums or 0)), int(w), int(h), int(nframes),
+                                           int(connectivity), int(stats_rows))
+        _check("mi355_ccl_gray8_dev", rc, self._h)
 
     def hist_gray8_dev(self, d_in, d_hist, w, h, nframes):
         """mi355_hist_gray8_dev: nframes x 256 uint32 counts to d_hist (overwritten), no synchronisation."""
