@@ -159,6 +159,57 @@ def test_a_batch_equals_one_call_per_frame(arena, w, h):
                 assert np.array_equal(one[0], got[f]), (layout, f)
 
 
+# ---- more frames than the grid has rows ------------------------------------------------------------------------------
+BIG_N, BIG_K = 65537, 251      # gridDim.y holds 65535 frames; 65535 % 251 == 24: frame f - 65535 has other content than f
+
+
+@functools.lru_cache(maxsize=None)
+def _big_decode_table(packed):
+    """251 distinct 2 x 2 frames as (Y, U, V): the three kinds of decode content in turn, each under a seed of its own"""
+    kinds = (yc.noise_planes, yc.legal_planes, yc.extreme_planes)
+    planes = [kinds[k % 3](2, 2, packed, 7000 + k) for k in range(BIG_K)]
+    assert len({b"".join(a.tobytes() for a in p) for p in planes}) == BIG_K
+    return planes
+
+
+@functools.lru_cache(maxsize=None)
+def _big_encode_table():
+    """251 distinct 2 x 2 RGBA frames: the two kinds of encode content in turn"""
+    rgba = np.stack([(yc.cube_rgba, yc.blocks_rgba)[k % 2](2, 2, 9000 + k) for k in range(BIG_K)])
+    assert len({f.tobytes() for f in rgba}) == BIG_K
+    rgba.setflags(write=False)
+    return rgba
+
+
+def _check_big(arena, call, table, want_table, tag):
+    """frame f of the batch is table[f % 251]; the output starts as the complement of a part of every expected byte"""
+    idx = np.arange(BIG_N) % BIG_K
+    want = np.asarray(want_table)[idx]
+    got = _run(arena, call, np.asarray(table)[idx], want ^ 0xA5)
+    bad = np.flatnonzero((got != want).reshape(BIG_N, -1).any(axis=1))
+    assert bad.size == 0, (tag, bad.size, bad[:8].tolist())
+
+
+def test_a_batch_of_more_frames_than_the_grid_has_rows(arena):
+    """65537 tight 2 x 2 frames: the kernels' frame loop takes its second trip for frames 65535 and 65536.  The reference
+    is computed for the 251 distinct frames only; a loop that stops after one trip leaves the prefill in the last two
+    frames, and one that serves frame f from frame f - 65535 returns content 24 places off."""
+    ctx, w, h = arena.ctx, 2, 2
+    for layout, std in ((yr.NV12, yr.BT709), (yr.I420, yr.BT601), (yr.YUY2, yr.BT601_FULL)):
+        planes = _big_decode_table(yr.is_packed(layout))
+        _check_big(arena, lambda a, b: ctx.yuv_to_rgba8_dev(a, b, w, h, BIG_N, layout, std, 0, 0),
+                   [yr.pack(p, layout) for p in planes], [yr.decode_planes(*p, std) for p in planes],
+                   "decode " + yr.LAYOUT_NAMES[layout])
+    for layout in (yr.NV12, yr.UYVY):
+        planes = _big_decode_table(yr.is_packed(layout))
+        _check_big(arena, lambda a, b: ctx.yuv_to_gray8_dev(a, b, w, h, BIG_N, layout, 0, 0),
+                   [yr.pack(p, layout) for p in planes], [p[0] for p in planes], "luma " + yr.LAYOUT_NAMES[layout])
+    rgba = _big_encode_table()
+    for layout, std in ((yr.NV12, yr.BT601), (yr.I420, yr.BT709)):
+        _check_big(arena, lambda a, b: ctx.rgba8_to_yuv_dev(a, b, w, h, BIG_N, layout, std, 0, 0), rgba,
+                   [yr.pack(yr.encode_planes(f, std), layout) for f in rgba], "encode " + yr.LAYOUT_NAMES[layout])
+
+
 # ---- guarded arena ---------------------------------------------------------------------------------------------------
 def _guard_geometries(layout, w, h):
     g = yc.geometries(layout, w, h)
