@@ -697,6 +697,76 @@ int mi355_ccl_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t* labels, 
                             uint64_t* sums, int w, int h, int nframes, int connectivity, int stats_rows,
                             uint64_t prof_ns[6]);
 
+/* ---- from gradients to edges: hysteresis thresholding, and cv::Canny(image, edges, threshold1, threshold2, 3, L2gradient) --
+ * The step between "gradient magnitude" and "mask": one-pixel-wide, connected edges without leaving the device.  gray8
+ * frames only, in and out (the single-channel rules: tightly packed, any byte alignment of input and output, any width
+ * >= 1, frames are independent, MI355_ERR_UNSUPPORTED under MI355_INPUT_BGR in the host form).  Entry points of their
+ * own, not filter ids: the parameters do not fit (k, sigma).  OpenCV is not installed where this library is built and
+ * tested: the rules below are restated from memory of OpenCV's code; nobody has compared it with an OpenCV build here;
+ * the rules below are the contract.  All arithmetic is integer; every byte of the output is written; there is one right
+ * answer per input, the same bits on every run.
+ *
+ * 1. Hysteresis threshold of a response map (this library's SOBEL_GRAY8 or CLAHE output, any gray8 frame).
+ *     candidate   a pixel whose byte > low
+ *     strong      a pixel whose byte > high
+ *     out         255 where the pixel is a candidate and its connected component of candidates holds at least one
+ *                 strong pixel, else 0
+ *   Connectivity is 4 or 8, the component rule of mi355_ccl_*: row ends do not wrap, frames do not link.
+ *   MI355_ERR_BAD_ARG, before any device work: a null context or pointer; sizes the labelling call rejects (w * h >= 2^31
+ *   among them); a connectivity other than 4 or 8; low or high outside 0..255; low > high; a d_out range that overlaps
+ *   d_in.  high = 255 is accepted: nothing is strong and the output is all zero.
+ *
+ * 2. Canny, aperture 3.  No colour step and no blur of its own: chain MI355_FILTER_GAUSS_GRAY8 in front, as a
+ *    cv::GaussianBlur + cv::Canny user does.
+ *   thresholds  lo = min(threshold1, threshold2), hi = max(threshold1, threshold2), in double.  With
+ *               MI355_CANNY_L2GRADIENT: lo = min(lo, 32767.0), hi = min(hi, 32767.0), then each one that is > 0 is
+ *               squared.  low = (int)floor(lo), high = (int)floor(hi).
+ *   gradient    the 3x3 Sobel pair with coordinates clamped to the frame (BORDER_REPLICATE), p[y][x] the source byte:
+ *                   dx = (p[y-1][x+1] + 2 p[y][x+1] + p[y+1][x+1]) - (p[y-1][x-1] + 2 p[y][x-1] + p[y+1][x-1])
+ *                   dy = (p[y+1][x-1] + 2 p[y+1][x] + p[y+1][x+1]) - (p[y-1][x-1] + 2 p[y-1][x] + p[y-1][x+1])
+ *               This is NOT the Sobel of MI355_FILTER_SOBEL_GRAY8: that one is the reference program's reflect-101
+ *               magnitude.
+ *   magnitude   m = |dx| + |dy|, or dx * dx + dy * dy with MI355_CANNY_L2GRADIENT; both fit an int32 (|dx|, |dy| <=
+ *               1020).  The magnitude of a position outside the frame is 0.
+ *   non-maximum suppression   a pixel with m > low is a candidate iff it is a local maximum along its quantised
+ *               direction.  With x = |dx|, y = |dy| << 15, tg22x = x * 13573, tg67x = tg22x + (x << 16) (all below 2^27):
+ *                   y < tg22x            m > m(x-1, y)    and  m >= m(x+1, y)
+ *                   else y > tg67x       m > m(x, y-1)    and  m >= m(x, y+1)
+ *                   else                 m > m(x-s, y-1)  and  m >  m(x+s, y+1),   s = ((dx ^ dy) < 0) ? -1 : 1
+ *               The > / >= asymmetry is part of the contract: it decides which column of a two-pixel plateau survives
+ *               (the one on the left, the one above), so the mirror image of a frame need not give the mirrored edges.
+ *   hysteresis  a candidate is strong iff m > high; out = 255 where the pixel is a candidate and its 8-connected
+ *               component of candidates holds a strong one, else 0: rule 1 on the candidates.
+ *   MI355_ERR_BAD_ARG, before any device work: a null context or pointer; sizes the labelling call rejects; a threshold
+ *   that is not finite, is negative or exceeds 1e9; flag bits other than MI355_CANNY_L2GRADIENT; a d_out range that
+ *   overlaps d_in.
+ *
+ *   mi355_hysteresis_check, mi355_canny_check   pure host functions returning the code a call with these values returns
+ *                            before any device work.
+ *   mi355_hysteresis_gray8_dev   the rules of mi355_filter_dev: up to five launches on the context's stream (the three
+ *                            union launches of mi355_ccl_gray8_dev with "byte > low" as foreground, mark, emit), no
+ *                            synchronisation.  The union-find parent array, 4 BYTES PER PIXEL, is pooled in the context:
+ *                            after the first call for a given (w, h, nframes) a call allocates nothing and waits for
+ *                            nothing, so it can be captured into a hipGraph.
+ *   mi355_canny_gray8_dev    the same with one launch in front: source bytes -> a class byte per pixel (0 none,
+ *                            1 candidate, 2 strong) in d_out itself, which the hysteresis then rewrites in place.  Up to
+ *                            six launches; the same pooled 4 bytes per pixel and nothing else; the same graph rule.
+ *   mi355_*_gray8_batched    host buffers: H2D, the launches, D2H through the context's pooled buffers; prof_ns (may be
+ *                            NULL) gets the six timestamps of mi355_filter_batched.
+ * Not offered: apertures 5 and 7, RGBA input, the (dx, dy) overload of cv::Canny, 16-bit responses, the streamed, group
+ * and mi355_pool_alloc forms, row pitch and ROI. */
+#define MI355_CANNY_L2GRADIENT 1
+int mi355_hysteresis_check(int w, int h, int nframes, int low, int high, int connectivity);
+int mi355_hysteresis_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes, int low,
+                               int high, int connectivity);
+int mi355_hysteresis_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes, int low,
+                                   int high, int connectivity, uint64_t prof_ns[6]);
+int mi355_canny_check(int w, int h, int nframes, double threshold1, double threshold2, int flags);
+int mi355_canny_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes, double threshold1,
+                          double threshold2, int flags);
+int mi355_canny_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
+                              double threshold1, double threshold2, int flags, uint64_t prof_ns[6]);
+
 /* ---- frames from a decoder or a camera: 8-bit YUV <-> RGBA, cv::cvtColor(COLOR_YUV2RGBA_* / COLOR_RGBA2YUV_*) --------
  * The video decoder writes NV12 surfaces with a pitch, software decoders write I420, webcams deliver YUY2, and an
  * encoder wants NV12 or I420 back.  These calls are the first and the last step of a chain that stays on the device:

@@ -55,6 +55,7 @@ struct mi355_ctx {
     DevBuf d_hist = {};   // per-frame 256-bin histograms of EQUALIZE_GRAY8 / OTSU_GRAY8 (hist.hip)
     DevBuf d_lut = {};    // their per-frame 256-byte tables
     DevBuf d_ccl = {};    // per-block component counts, then offsets, of the labelling calls (ccl.hip)
+    DevBuf d_parent = {};  // the union-find parent array, 4 bytes per pixel, of the hysteresis and Canny calls (canny.hip)
     DevBuf d_map1 = {}, d_map2 = {};  // the maps of mi355_remap_batched
     unsigned long long* d_acc = nullptr;
     float* d_img_table = nullptr;  // image2d-mode Gaussian table (k*k floats, MI355_MAX_GAUSS_K^2 capacity)
@@ -845,7 +846,7 @@ MI355_API int mi355_ctx_destroy(mi355_ctx* ctx)
     for (void* p : ctx->pinned)
         (void)hipHostFree(p);
     for (void* p : {(void*)ctx->d_acc, (void*)ctx->d_img_table, ctx->d_in.p, ctx->d_out.p, ctx->d_raw.p, ctx->d_flags.p,
-                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_ccl.p, ctx->d_map1.p, ctx->d_map2.p})
+                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_ccl.p, ctx->d_parent.p, ctx->d_map1.p, ctx->d_map2.p})
         if (p)
             (void)hipFree(p);
     for (int i = 0; i < mi355_ctx::kSlots; i++) {
@@ -1714,6 +1715,134 @@ MI355_API int mi355_ccl_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t
             HIP_TRY(ctx, hipMemcpyAsync(sums, d_out + at_sums, nb.sums, hipMemcpyDeviceToHost, ctx->stream));
         }
         return (int)MI355_OK;
+    });
+}
+
+// ---- from gradients to edges -----------------------------------------------------------------------------------------
+// The value checks of every hysteresis call (include/mi355_imgfilter.h, "from gradients to edges")
+static int hysteresis_values(int w, int h, int nframes, int low, int high, int connectivity)
+{
+    const int rc = ccl_values(w, h, nframes, connectivity, 0, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    return low < 0 || high > 255 || low > high ? MI355_ERR_BAD_ARG : MI355_OK;
+}
+
+// The value checks of every Canny call and, when they pass, the two integer thresholds on the magnitude
+static int canny_values(int w, int h, int nframes, double threshold1, double threshold2, int flags, int* low, int* high)
+{
+    const int rc = ccl_values(w, h, nframes, 8, 0, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    if (!std::isfinite(threshold1) || !std::isfinite(threshold2) || threshold1 < 0.0 || threshold2 < 0.0 ||
+        threshold1 > 1.0e9 || threshold2 > 1.0e9 || (flags & ~MI355_CANNY_L2GRADIENT))
+        return MI355_ERR_BAD_ARG;
+    double lo = threshold1 < threshold2 ? threshold1 : threshold2, hi = threshold1 < threshold2 ? threshold2 : threshold1;
+    if (flags & MI355_CANNY_L2GRADIENT) {
+        lo = lo < 32767.0 ? lo : 32767.0;
+        hi = hi < 32767.0 ? hi : 32767.0;
+        if (lo > 0.0)
+            lo *= lo;
+        if (hi > 0.0)
+            hi *= hi;
+    }
+    if (low)
+        *low = (int)std::floor(lo);  // at most 32767^2 or 10^9: an int
+    if (high)
+        *high = (int)std::floor(hi);
+    return MI355_OK;
+}
+
+// the one pointer check of the device-resident hysteresis and Canny calls, and the pooled parent array
+static int edges_check_dev(mi355_ctx* ctx, const void* d_in, const void* d_out, int w, int h, int nframes)
+{
+    const size_t nbytes = frame_bytes(w, h, nframes, 1);
+    if (overlap(d_in, nbytes, d_out, nbytes))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ensure(ctx, ctx->d_parent, nbytes * sizeof(int32_t));
+}
+
+MI355_API int mi355_hysteresis_check(int w, int h, int nframes, int low, int high, int connectivity)
+{
+    return hysteresis_values(w, h, nframes, low, high, connectivity);
+}
+
+MI355_API int mi355_hysteresis_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes, int low,
+                                         int high, int connectivity)
+{
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    int rc = hysteresis_values(w, h, nframes, low, high, connectivity);
+    if (rc == MI355_OK)
+        rc = edges_check_dev(ctx, d_in, d_out, w, h, nframes);
+    if (rc != MI355_OK)
+        return rc;
+    HIP_TRY(ctx, launch_hysteresis(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                                   static_cast<int32_t*>(ctx->d_parent.p), w, h, nframes, low, high, connectivity == 8));
+    return MI355_OK;
+}
+
+MI355_API int mi355_hysteresis_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
+                                             int low, int high, int connectivity, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = hysteresis_values(w, h, nframes, low, high, connectivity);
+    if (rc != MI355_OK)
+        return rc;
+    HostIO io;
+    rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_parent, frame_bytes(w, h, nframes, 4));  // outside the timed window
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+        return mi355_hysteresis_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, low, high, connectivity);
+    });
+}
+
+MI355_API int mi355_canny_check(int w, int h, int nframes, double threshold1, double threshold2, int flags)
+{
+    return canny_values(w, h, nframes, threshold1, threshold2, flags, nullptr, nullptr);
+}
+
+MI355_API int mi355_canny_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes,
+                                    double threshold1, double threshold2, int flags)
+{
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    int low = 0, high = 0;
+    int rc = canny_values(w, h, nframes, threshold1, threshold2, flags, &low, &high);
+    if (rc == MI355_OK)
+        rc = edges_check_dev(ctx, d_in, d_out, w, h, nframes);
+    if (rc != MI355_OK)
+        return rc;
+    uint8_t* out = static_cast<uint8_t*>(d_out);
+    HIP_TRY(ctx, launch_canny_nms(ctx->stream, static_cast<const uint8_t*>(d_in), out, w, h, nframes, low, high,
+                                  (flags & MI355_CANNY_L2GRADIENT) != 0));
+    // the class bytes (0 none, 1 candidate, 2 strong) become the edge map in place: candidate = class > 0, strong = class > 1
+    HIP_TRY(ctx, launch_hysteresis(ctx->stream, out, out, static_cast<int32_t*>(ctx->d_parent.p), w, h, nframes, 0, 1,
+                                   true));
+    return MI355_OK;
+}
+
+MI355_API int mi355_canny_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
+                                        double threshold1, double threshold2, int flags, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    int rc = canny_values(w, h, nframes, threshold1, threshold2, flags, nullptr, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    HostIO io;
+    rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_parent, frame_bytes(w, h, nframes, 4));  // outside the timed window
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+        return mi355_canny_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, threshold1, threshold2, flags);
     });
 }
 

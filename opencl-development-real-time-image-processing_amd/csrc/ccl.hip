@@ -23,6 +23,8 @@
 //                        runs in a 64-slot LDS table and adds each occupied slot once to the global row;
 //   ccl_stats_init / _finish   the accumulators' identities before, {left, top, width, height, area} and the empty rows
 //                        after.
+// The first three take a wave-uniform `low`: a pixel is foreground iff its byte > low.  The labelling call passes 0
+// ("not zero"); the hysteresis of canny.hip runs just these three (launch_ccl_unite) with its lower threshold.
 #include "common.hpp"
 #include "hist_common.hpp"
 #include "kernels.hpp"
@@ -88,7 +90,7 @@ __device__ __forceinline__ uint64_t row_mask(const uint32_t* smask, int r)
 }
 
 __global__ __launch_bounds__(kThreads) void ccl_local_kernel(const uint8_t* __restrict__ in, int32_t* __restrict__ labels,
-                                                             CclGeom g, int conn8)
+                                                             CclGeom g, int conn8, uint32_t low)
 {
     __shared__ uint32_t smask[kTileH * 2];
     __shared__ uint32_t lab[kTileH * kTileW];
@@ -111,17 +113,17 @@ __global__ __launch_bounds__(kThreads) void ccl_local_kernel(const uint8_t* __re
             const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15u);
             const int c0 = 16 * s - mis;  // the chunk is bytes c0 .. c0 + 15 of the row's n bytes
             const int b0 = c0 > 0 ? c0 : 0, b1 = c0 + 16 < n ? c0 + 16 : n;
-            uint32_t bits = 0;  // bit i: byte b0 + i is not zero
+            uint32_t bits = 0;  // bit i: byte b0 + i is foreground (> low)
             if (b1 - b0 == 16) {
                 const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + c0));
 #pragma unroll
                 for (int d = 0; d < 4; d++)
 #pragma unroll
                     for (int e = 0; e < 4; e++)
-                        bits |= (((v[d] >> (8 * e)) & 0xFFu) ? 1u : 0u) << (4 * d + e);
+                        bits |= (((v[d] >> (8 * e)) & 0xFFu) > low ? 1u : 0u) << (4 * d + e);
             } else {
                 for (int b = b0; b < b1; b++)  // bound: fewer than 16 bytes
-                    bits |= (row[b] ? 1u : 0u) << (b - b0);
+                    bits |= (row[b] > low ? 1u : 0u) << (b - b0);
             }
             if (bits) {
                 const uint64_t m = (uint64_t)bits << b0;
@@ -231,7 +233,7 @@ __device__ __forceinline__ void seam_pixel(const CclGeom& g, uint32_t i, bool* h
 }
 
 __global__ __launch_bounds__(kThreads) void ccl_seam_kernel(const uint8_t* __restrict__ in, int32_t* labels, CclGeom g,
-                                                            uint32_t bpf, int conn8)
+                                                            uint32_t bpf, int conn8, uint32_t low)
 {
     const uint32_t f = blockIdx.x / bpf, i = (blockIdx.x - f * bpf) * kThreads + threadIdx.x;
     if (i >= g.seam)
@@ -242,14 +244,15 @@ __global__ __launch_bounds__(kThreads) void ccl_seam_kernel(const uint8_t* __res
     const uint8_t* p = in + (size_t)f * g.npx;
     int32_t* lab = labels + (size_t)f * g.npx;
     const uint32_t w = g.w, at = y * w + x;
-    if (!p[at])
+    auto fg = [&](uint32_t q) { return p[q] > low; };  // foreground, as the local kernel saw it
+    if (!fg(at))
         return;
     const int32_t me = (int32_t)at + 1;
     if (hor) {
         // the row above belongs to another tile: the local kernel's rule, on the frame's rows
-        const bool c_l = x > 0 && p[at - 1], c_r = x + 1 < w && p[at + 1];
-        const bool u_l = x > 0 && p[at - w - 1], u_r = x + 1 < w && p[at - w + 1];
-        if (p[at - w]) {
+        const bool c_l = x > 0 && fg(at - 1), c_r = x + 1 < w && fg(at + 1);
+        const bool u_l = x > 0 && fg(at - w - 1), u_r = x + 1 < w && fg(at - w + 1);
+        if (fg(at - w)) {
             if (!(c_l && u_l))
                 agent_union(lab, me, me - (int32_t)w);
         } else if (conn8) {
@@ -262,13 +265,13 @@ __global__ __launch_bounds__(kThreads) void ccl_seam_kernel(const uint8_t* __res
         // the column on the left belongs to another tile; the pair one row up does it when both its pixels are set and
         // the local kernel has united this pixel with the one above it (a tile's top row is united with the row above
         // by the branch above, which may itself count on this union: no skipping there)
-        if (p[at - 1]) {
-            if (!(y % kTileH != 0 && p[at - w] && p[at - w - 1]))
+        if (fg(at - 1)) {
+            if (!(y % kTileH != 0 && fg(at - w) && fg(at - w - 1)))
                 agent_union(lab, me, me - 1);
         } else if (conn8) {
-            if (y > 0 && p[at - w - 1] && !p[at - w])
+            if (y > 0 && fg(at - w - 1) && !fg(at - w))
                 agent_union(lab, me, me - (int32_t)w - 1);
-            if (y + 1 < g.h && p[at + w - 1] && !p[at + w])
+            if (y + 1 < g.h && fg(at + w - 1) && !fg(at + w))
                 agent_union(lab, me, me + (int32_t)w - 1);
         }
     }
@@ -287,7 +290,7 @@ __device__ __forceinline__ void compress_pixel(int32_t* lab, uint32_t q)
 }
 
 __global__ __launch_bounds__(kThreads) void ccl_compress_kernel(const uint8_t* __restrict__ in, int32_t* labels,
-                                                                CclGeom g, uint32_t bpf)
+                                                                CclGeom g, uint32_t bpf, uint32_t low)
 {
     const uint32_t f = blockIdx.x / bpf, i = (blockIdx.x - f * bpf) * kThreads + threadIdx.x;
     if (i >= g.seam)
@@ -298,9 +301,9 @@ __global__ __launch_bounds__(kThreads) void ccl_compress_kernel(const uint8_t* _
     const uint8_t* p = in + (size_t)f * g.npx;
     int32_t* lab = labels + (size_t)f * g.npx;
     const uint32_t at = y * g.w + x, opposite = hor ? at - g.w : at - 1;
-    if (p[at])
+    if (p[at] > low)
         compress_pixel(lab, at);
-    if (p[opposite])
+    if (p[opposite] > low)
         compress_pixel(lab, opposite);
 }
 
@@ -545,7 +548,38 @@ bool ccl_geom(int w, int h, int nframes, CclGeom* g)
     return true;
 }
 
+// The union launches: local, and where the frame has more than one tile, seam and compress.  Afterwards a foreground
+// pixel q reaches its root in two loads: labels[q] is a tile root's value (or already the root's), and a tile root's
+// entry holds its root's value
+hipError_t enqueue_unite(hipStream_t stream, const uint8_t* d_in, int32_t* d_labels, const CclGeom& g, int nframes,
+                         bool conn8, uint32_t low)
+{
+    const uint64_t tiles = (uint64_t)nframes * g.ntx * g.nty;
+    const uint32_t seam_bpf = (g.seam + kThreads - 1) / kThreads;
+    const uint64_t seam_blocks = (uint64_t)nframes * seam_bpf;
+    if (!grid_fits(tiles) || !grid_fits(seam_blocks))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ccl_local_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, stream, d_in, d_labels, g,
+                       conn8 ? 1 : 0, low);
+    if (g.seam) {
+        hipLaunchKernelGGL(ccl_seam_kernel, dim3((uint32_t)seam_blocks), dim3(kThreads), 0, stream, d_in, d_labels, g,
+                           seam_bpf, conn8 ? 1 : 0, low);
+        hipLaunchKernelGGL(ccl_compress_kernel, dim3((uint32_t)seam_blocks), dim3(kThreads), 0, stream, d_in, d_labels, g,
+                           seam_bpf, low);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_ccl_unite(hipStream_t stream, const uint8_t* d_in, int32_t* d_parent, int w, int h, int nframes,
+                            bool conn8, int low)
+{
+    CclGeom g;
+    if (!ccl_geom(w, h, nframes, &g) || low < 0 || low > 255)
+        return hipErrorInvalidValue;
+    return enqueue_unite(stream, d_in, d_parent, g, nframes, conn8, (uint32_t)low);
+}
 
 size_t ccl_scratch_bytes(int w, int h, int nframes)
 {
@@ -560,23 +594,18 @@ hipError_t launch_ccl(hipStream_t stream, const uint8_t* d_in, int32_t* d_labels
     if (!ccl_geom(w, h, nframes, &g) || stats_rows < 0 || stats_rows > kCclMaxStatsRows)
         return hipErrorInvalidValue;
     const uint64_t tiles = (uint64_t)nframes * g.ntx * g.nty;
-    const uint32_t seam_bpf = (g.seam + kThreads - 1) / kThreads;
-    const uint64_t seam_blocks = (uint64_t)nframes * seam_bpf, flat_blocks = (uint64_t)nframes * g.nflat;
+    const uint64_t seam_blocks = (uint64_t)nframes * ((g.seam + kThreads - 1) / kThreads);
+    const uint64_t flat_blocks = (uint64_t)nframes * g.nflat;
     const uint64_t rows = (uint64_t)nframes * (uint64_t)stats_rows, row_blocks = (rows + kThreads - 1) / kThreads;
     if (!grid_fits(tiles) || !grid_fits(seam_blocks) || !grid_fits(flat_blocks) || !grid_fits(row_blocks))
-        return hipErrorInvalidValue;
+        return hipErrorInvalidValue;  // before the first launch
     unsigned long long* sums = reinterpret_cast<unsigned long long*>(d_sums);
     if (rows)
         hipLaunchKernelGGL(ccl_stats_init_kernel, dim3((uint32_t)row_blocks), dim3(kThreads), 0, stream, d_stats, sums,
                            rows);
-    hipLaunchKernelGGL(ccl_local_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, stream, d_in, d_labels, g,
-                       conn8 ? 1 : 0);
-    if (g.seam) {
-        hipLaunchKernelGGL(ccl_seam_kernel, dim3((uint32_t)seam_blocks), dim3(kThreads), 0, stream, d_in, d_labels, g,
-                           seam_bpf, conn8 ? 1 : 0);
-        hipLaunchKernelGGL(ccl_compress_kernel, dim3((uint32_t)seam_blocks), dim3(kThreads), 0, stream, d_in, d_labels, g,
-                           seam_bpf);
-    }
+    const hipError_t ue = enqueue_unite(stream, d_in, d_labels, g, nframes, conn8, 0u);  // foreground: not zero
+    if (ue != hipSuccess)
+        return ue;
     hipLaunchKernelGGL(ccl_flatten_kernel, dim3((uint32_t)flat_blocks), dim3(kThreads), 0, stream, d_labels, d_scratch, g);
     hipLaunchKernelGGL(ccl_scan_kernel, dim3((uint32_t)nframes), dim3(kThreads), 0, stream, d_scratch, d_count, g.nflat);
     if (rows) {

@@ -160,6 +160,25 @@ constexpr int kCclMaxStatsRows = 1 << 24;
 size_t ccl_scratch_bytes(int w, int h, int nframes);  // 0 for sizes launch_ccl rejects
 hipError_t launch_ccl(hipStream_t stream, const uint8_t* d_in, int32_t* d_labels, int32_t* d_count, int32_t* d_stats,
                       uint64_t* d_sums, uint32_t* d_scratch, int w, int h, int nframes, bool conn8, int stats_rows);
+// The union launches of launch_ccl alone (local, seam, compress: up to three), with foreground = byte > low, 0 <= low <=
+// 255 (launch_ccl itself runs them with low = 0).  Afterwards d_parent (int32 per pixel, 4-byte aligned) holds 0 for
+// background and, for a foreground pixel q, a value a = (a pixel index of q's component) + 1 such that d_parent[a - 1] is
+// q's root value; a root's entry is its own index + 1.  Every pixel reaches its root in two loads.
+hipError_t launch_ccl_unite(hipStream_t stream, const uint8_t* d_in, int32_t* d_parent, int w, int h, int nframes,
+                            bool conn8, int low);
+
+// cv::Canny(aperture 3) and hysteresis thresholding of single-channel frames (canny.hip; semantics:
+// include/mi355_imgfilter.h, "from gradients to edges"): frames of w * h < 2^31 pixels at any byte alignment.
+//   launch_canny_nms   one launch: source bytes -> a class byte per pixel (0 none, 1 candidate, 2 strong); low and high
+//                      are the integer thresholds on the magnitude (|dx| + |dy|, or dx^2 + dy^2 with l2)
+//   launch_hysteresis  out = 255 where in > low and the pixel's component of such pixels holds one > high, else 0;
+//                      0 <= low <= high <= 255.  Up to five launches: launch_ccl_unite into d_parent (4 B/px), mark,
+//                      emit.  d_out may be d_in itself (every thread reads only the bytes it writes), and must not
+//                      overlap it in any other way.  No allocation, no wait, nothing the host reads.
+hipError_t launch_canny_nms(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int w, int h, int nframes, int low,
+                            int high, bool l2);
+hipError_t launch_hysteresis(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int32_t* d_parent, int w, int h,
+                             int nframes, int low, int high, bool conn8);
 
 // cv::resize of tightly packed 8-bit frames (resize.hip): bpp 4 (RGBA, dword-aligned) or 1 (gray8, any byte alignment);
 // interp 0 nearest, 1 linear (11-bit fixed point; AREA's result at exactly half size), 3 area with integer factors

@@ -41,6 +41,8 @@ ADAPTIVE_BINARY, ADAPTIVE_BINARY_INV = 0, 1
 MAX_CLAHE_TILES = 16
 # connected components (mi355_ccl_*): connectivity 4 or 8, 0 <= stats_rows <= MAX_CCL_STATS_ROWS
 MAX_CCL_STATS_ROWS = 1 << 24
+# cv::Canny (mi355_canny_*): flags = 0 or CANNY_L2GRADIENT (magnitude dx^2 + dy^2 instead of |dx| + |dy|)
+CANNY_L2GRADIENT = 1
 # cv::resize (mi355_resize_*): OpenCV's enum values; AREA only with integer factors 1 .. MAX_AREA_FACTOR
 INTERP_NEAREST, INTERP_LINEAR, INTERP_AREA = 0, 1, 3
 MAX_AREA_FACTOR = 16
@@ -185,6 +187,12 @@ def load_library(path=None):
         "mi355_ccl_check": [_ci, _ci, _ci, _ci, _ci],
         "mi355_ccl_gray8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci],
         "mi355_ccl_gray8_batched": [_vp, _u8p, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _u64p],
+        "mi355_hysteresis_check": [_ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_hysteresis_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci],
+        "mi355_hysteresis_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _u64p],
+        "mi355_canny_check": [_ci, _ci, _ci, _cd, _cd, _ci],
+        "mi355_canny_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _cd, _cd, _ci],
+        "mi355_canny_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _cd, _cd, _ci, _u64p],
         "mi355_yuv_check": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_yuv_to_rgba8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_rgba8_to_yuv_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
@@ -381,6 +389,18 @@ def ccl_check(w, h, nframes=1, connectivity=8, stats_rows=0):
     """mi355_ccl_check, a pure host function: the code (0 ok, -1 bad argument) a labelling call with these values returns
     before any device work."""
     return load_library().mi355_ccl_check(int(w), int(h), int(nframes), int(connectivity), int(stats_rows))
+
+
+def hysteresis_check(w, h, nframes=1, low=0, high=0, connectivity=8):
+    """mi355_hysteresis_check, a pure host function: the code (0 ok, -1 bad argument) a hysteresis call with these values
+    returns before any device work."""
+    return load_library().mi355_hysteresis_check(int(w), int(h), int(nframes), int(low), int(high), int(connectivity))
+
+
+def canny_check(w, h, nframes=1, threshold1=50.0, threshold2=150.0, flags=0):
+    """mi355_canny_check, a pure host function: the code (0 ok, -1 bad argument) a Canny call with these values returns
+    before any device work."""
+    return load_library().mi355_canny_check(int(w), int(h), int(nframes), float(threshold1), float(threshold2), int(flags))
 
 
 def yuv_frame_bytes(layout, w, h, pitch=0, rows=0):
@@ -642,6 +662,34 @@ class Context:
                 centroids = sums.astype(np.float64) / stats[:, :, 4:5].astype(np.float64)
             out += (stats[0], centroids[0]) if one else (stats, centroids)
         return out + (list(prof),) if profile else out
+
+    def hysteresis_gray8(self, y, low, high, connectivity=8, profile=False):
+        """Hysteresis threshold of (h, w) / (n, h, w) single-channel response maps (mi355_hysteresis_gray8_batched): 255
+        where the byte > low and the pixel's component of such pixels holds a byte > high, else 0."""
+        frames, one = self._frames("hysteresis_gray8", y, 1)
+        n, h, w = frames.shape
+        out = np.empty((n, h, w), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_hysteresis_gray8_batched(
+            self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, int(low), int(high),
+            int(connectivity), prof if profile else None)
+        _check("mi355_hysteresis_gray8_batched", rc, self._h)
+        out = out[0] if one else out
+        return (out, list(prof)) if profile else out
+
+    def canny_gray8(self, y, threshold1, threshold2, flags=0, profile=False):
+        """cv::Canny(y, edges, threshold1, threshold2, 3, flags & CANNY_L2GRADIENT) of (h, w) / (n, h, w) single-channel
+        frames (mi355_canny_gray8_batched): 255 on edges, else 0.  No blur of its own: chain gauss_gray8 in front."""
+        frames, one = self._frames("canny_gray8", y, 1)
+        n, h, w = frames.shape
+        out = np.empty((n, h, w), np.uint8)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_canny_gray8_batched(
+            self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, float(threshold1),
+            float(threshold2), int(flags), prof if profile else None)
+        _check("mi355_canny_gray8_batched", rc, self._h)
+        out = out[0] if one else out
+        return (out, list(prof)) if profile else out
 
     # -- frames from a decoder or a camera (mi355_yuv_to_rgba8_batched / mi355_rgba8_to_yuv_batched) -----
     def yuv_to_rgba8(self, yuv, w, h, layout, standard=YUV_BT601, pitch=0, rows=0, profile=False):
@@ -927,6 +975,20 @@ class Context:
                                            _vp(int(d_stats or 0)), _vp(int(d_sums or 0)), int(w), int(h), int(nframes),
                                            int(connectivity), int(stats_rows))
         _check("mi355_ccl_gray8_dev", rc, self._h)
+
+    def hysteresis_gray8_dev(self, d_in, d_out, w, h, nframes, low, high, connectivity=8):
+        """mi355_hysteresis_gray8_dev: the hysteresis threshold of nframes gray8 response maps at d_in to d_out; up to
+        five launches, no synchronisation; the parent array (4 bytes per pixel) is pooled in the context."""
+        rc = self._lib.mi355_hysteresis_gray8_dev(self._h, _vp(int(d_in or 0)), _vp(int(d_out or 0)), int(w), int(h),
+                                                  int(nframes), int(low), int(high), int(connectivity))
+        _check("mi355_hysteresis_gray8_dev", rc, self._h)
+
+    def canny_gray8_dev(self, d_in, d_out, w, h, nframes, threshold1, threshold2, flags=0):
+        """mi355_canny_gray8_dev: cv::Canny (aperture 3) of nframes gray8 frames at d_in to d_out; up to six launches,
+        no synchronisation; the parent array (4 bytes per pixel) is pooled in the context."""
+        rc = self._lib.mi355_canny_gray8_dev(self._h, _vp(int(d_in or 0)), _vp(int(d_out or 0)), int(w), int(h),
+                                             int(nframes), float(threshold1), float(threshold2), int(flags))
+        _check("mi355_canny_gray8_dev", rc, self._h)
 
     def hist_gray8_dev(self, d_in, d_hist, w, h, nframes):
         """mi355_hist_gray8_dev: nframes x 256 uint32 counts to d_hist (overwritten), no synchronisation."""
