@@ -767,6 +767,93 @@ int mi355_canny_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, 
 int mi355_canny_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
                               double threshold1, double threshold2, int flags, uint64_t prof_ns[6]);
 
+/* ---- from edges to lines: cv::HoughLines(edges, lines, rho, theta, threshold, 0, 0, min_theta, max_theta) ------------------
+ * The standard Hough transform of gray8 edge maps (this library's Canny or hysteresis output, any mask): one byte per
+ * pixel in, a few hundred bytes of (rho, theta) pairs per frame out.  gray8 frames only (the single-channel rules: tightly
+ * packed, any byte alignment of the input, frames are independent, MI355_ERR_UNSUPPORTED under MI355_INPUT_BGR in the
+ * host form).  Entry points of their own, not filter ids: the parameters do not fit (k, sigma).  OpenCV is not installed
+ * where this library is built and tested: the rules below are restated from memory of OpenCV's HoughLinesStandard; nobody
+ * has compared it with an OpenCV build here; the rules below are the contract.
+ *   parameters  rho_f = (float)rho;  theta_f = (float)theta;  irho = 1.0f / rho_f, in fp32.
+ *   numangle    in double: floor((max_theta - min_theta) / theta) + 1; if that is greater than 1 and
+ *               |pi - (numangle - 1) * theta| < theta / 2, one less.  pi is M_PI.
+ *   numrho      cvRound((float)(2 * (w + h) + 1) / rho_f): the division in fp32, the rounding half to even.
+ *   trig table  ang is an fp32 variable that starts at (float)min_theta and grows by theta_f per entry (an fp32 add):
+ *                 tab_cos[n] = (float)(cos((double)ang) * (double)irho),  tab_sin[n] likewise with sin.
+ *               The table is made on the host (mi355_hough_trig_table returns it) and handed to the kernels: whatever the
+ *               platform's cos and sin return is part of the contract.
+ *   votes       every pixel (x, y) whose byte is not zero votes once for every angle n, in the cell
+ *                 r = rne(fl32(fl32(x * tab_cos[n]) + fl32(y * tab_sin[n]))) + (numrho - 1) / 2      (integer division)
+ *               counted in accum[(n + 1) * (numrho + 2) + r + 1].  The two products and the sum are three separately
+ *               rounded fp32 operations (no fused multiply-add); rne converts to the nearest integer, ties to even.  The
+ *               accumulator is int32, (numangle + 2) x (numrho + 2) per frame, frames back to back; its border ring (row 0,
+ *               row numangle + 1, column 0, column numrho + 1) is zero and IS written.  A vote whose r falls outside
+ *               0 .. numrho - 1 is dropped: that can happen only when rho is of the order of the frame size (rows of a handful
+ *               of cells; never while (w + h + 0.5 - sqrt(w^2 + h^2)) / rho >= 1.75), where OpenCV itself would count it in
+ *               the ring or beside the row.  Counters are 32-bit throughout.
+ *   peaks       a cell b inside the ring is a peak iff a[b] > threshold and a[b] > a[b - 1] and a[b] >= a[b + 1] and
+ *               a[b] > a[b - (numrho + 2)] and a[b] >= a[b + (numrho + 2)].  The > / >= asymmetry is part of the
+ *               contract (of a plateau of two the left or upper cell survives), so a frame and its transpose need not give
+ *               mirrored peaks.  The angle axis does not wrap: row 1 and row numangle see the zero ring.
+ *   order       peaks are ordered by votes descending, then by cell index b ascending: a total order, one right answer.
+ *               (OpenCV's own std::sort leaves the order of equal votes to the implementation.)
+ *   outputs     int32 d_count[f] = the number of peaks of frame f; it may exceed max_lines.
+ *               float d_lines[f][max_lines][2]: the first min(count, max_lines) rows hold, for cell (n, r),
+ *                 rho   = fl32(fl32((float)r - fl32((float)(numrho - 1) * 0.5f)) * rho_f)
+ *                 theta = fl32((float)min_theta + fl32((float)n * theta_f))
+ *               int32 d_votes[f][max_lines] (may be NULL): the votes of those rows.  Every remaining row of both, up to
+ *               max_lines, is written as zero: the output is a function of the input alone.
+ *   MI355_ERR_BAD_ARG, before any device work: a null context or pointer (d_votes and d_accum excepted); w or h outside
+ *   1 .. MI355_MAX_WARP_SIZE, nframes < 1; rho or theta that is not finite or not positive (as a double or as a float);
+ *   min_theta < 0, max_theta > M_PI (the double; OpenCV's own check has no slack here either, and none is given),
+ *   max_theta < min_theta, either not finite; numangle > MI355_MAX_HOUGH_ANGLES; numrho < 1 (rho of 2 (2 (w + h) + 1) or more); an
+ *   accumulator of 2^31 bytes or more per frame (or more than 2.4e11 bytes per call); threshold < 0; max_lines outside
+ *   1 .. MI355_MAX_HOUGH_LINES; an output pointer that is not 4-byte aligned; ranges that overlap (the input and every
+ *   output of the call, each with its own bytes).
+ *   mi355_hough_check       pure host function returning the code a lines call with these values returns before any
+ *                           device work.
+ *   mi355_hough_shape       pure host function: numangle and numrho (either pointer may be NULL).
+ *   mi355_hough_trig_table  pure host function: numangle floats each.
+ *   mi355_hough_accum_bytes pure host function: nframes * (numangle + 2) * (numrho + 2) * 4, or 0 for rejected values.
+ *   mi355_hough_plan        pure host function: how the voting launch cuts these values up — the angle rows a workgroup
+ *                           holds in LDS at once, the number of rho ranges a row is split into (1: the row fits), and the
+ *                           LDS budget in cells that decides both.  Tests read the limits here instead of restating them.
+ *   mi355_hough_accum_gray8_dev   the rules of mi355_filter_dev: the accumulator alone, two launches (point list, votes)
+ *                           behind one in-stream memset, no synchronisation.
+ *   mi355_hough_lines_gray8_dev   the same and two more launches (peaks, selection) behind a second memset.  d_accum may be
+ *                           NULL: the accumulator is then pooled in the context like Canny's parent array; otherwise the
+ *                           caller's receives it.  The scratch (4 bytes per frame, then the larger of 4 bytes per pixel
+ *                           for the point lists and 8 bytes per numangle * ceil(numrho / 2) for the peak candidates, an
+ *                           exact upper bound, not a guess) and the trig table are pooled too: after the first call with
+ *                           a given shape and (rho, theta, min_theta, max_theta) — which may allocate and which uploads the
+ *                           table, synchronising the stream — a call allocates nothing, waits for nothing and can be
+ *                           captured into a hipGraph.  No host round trip between the launches; kernel boundaries are the
+ *                           only ordering between workgroups; every loop is bounded.
+ *   mi355_hough_lines_gray8_batched   host buffers: H2D, the launches, D2H through the context's pooled buffers; votes may
+ *                           be NULL; prof_ns (may be NULL) gets the six timestamps of mi355_filter_batched.  The copies
+ *                           of count and votes are enqueued ahead of the lines' and fall into the kernel interval.
+ * Not offered: HoughLinesP, the multi-scale form (srn / stn), HoughLinesPointSet, the use_edgeval weighted votes of newer
+ * OpenCV, row pitch and ROI, the streamed, group and mi355_pool_alloc forms. */
+#define MI355_MAX_HOUGH_ANGLES 1024
+#define MI355_MAX_HOUGH_LINES 4096
+int mi355_hough_check(int w, int h, int nframes, double rho, double theta, int threshold, int max_lines, double min_theta,
+                      double max_theta);
+int mi355_hough_shape(int w, int h, double rho, double theta, double min_theta, double max_theta, int* numangle,
+                      int* numrho);
+int mi355_hough_trig_table(int w, int h, double rho, double theta, double min_theta, double max_theta, float* tab_cos,
+                           float* tab_sin);
+size_t mi355_hough_accum_bytes(int w, int h, int nframes, double rho, double theta, double min_theta, double max_theta);
+int mi355_hough_plan(int w, int h, double rho, double theta, double min_theta, double max_theta, int* angles_per_block,
+                     int* rho_splits, int* lds_cells);
+int mi355_hough_accum_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_accum, int w, int h, int nframes, double rho,
+                                double theta, double min_theta, double max_theta);
+int mi355_hough_lines_gray8_dev(mi355_ctx* ctx, const void* d_in, float* d_lines, int32_t* d_votes, int32_t* d_count,
+                                int32_t* d_accum, int w, int h, int nframes, double rho, double theta, int threshold,
+                                int max_lines, double min_theta, double max_theta);
+int mi355_hough_lines_gray8_batched(mi355_ctx* ctx, const uint8_t* in, float* lines, int32_t* votes, int32_t* count, int w,
+                                    int h, int nframes, double rho, double theta, int threshold, int max_lines,
+                                    double min_theta, double max_theta, uint64_t prof_ns[6]);
+
 /* ---- frames from a decoder or a camera: 8-bit YUV <-> RGBA, cv::cvtColor(COLOR_YUV2RGBA_* / COLOR_RGBA2YUV_*) --------
  * The video decoder writes NV12 surfaces with a pitch, software decoders write I420, webcams deliver YUY2, and an
  * encoder wants NV12 or I420 back.  These calls are the first and the last step of a chain that stays on the device:

@@ -56,6 +56,10 @@ struct mi355_ctx {
     DevBuf d_lut = {};    // their per-frame 256-byte tables
     DevBuf d_ccl = {};    // per-block component counts, then offsets, of the labelling calls (ccl.hip)
     DevBuf d_parent = {};  // the union-find parent array, 4 bytes per pixel, of the hysteresis and Canny calls (canny.hip)
+    DevBuf d_hough = {};      // counters, point lists and candidate lists of the Hough calls (hough.hip)
+    DevBuf d_hough_acc = {};  // their accumulator when the caller passes none
+    float* d_hough_tab = nullptr;  // the trig table on the device (2 * MI355_MAX_HOUGH_ANGLES floats) ...
+    double hough_key[4] = {};      // ... and the (rho, theta, min_theta, numangle) it was made for; numangle 0: none yet
     DevBuf d_map1 = {}, d_map2 = {};  // the maps of mi355_remap_batched
     unsigned long long* d_acc = nullptr;
     float* d_img_table = nullptr;  // image2d-mode Gaussian table (k*k floats, MI355_MAX_GAUSS_K^2 capacity)
@@ -846,7 +850,8 @@ MI355_API int mi355_ctx_destroy(mi355_ctx* ctx)
     for (void* p : ctx->pinned)
         (void)hipHostFree(p);
     for (void* p : {(void*)ctx->d_acc, (void*)ctx->d_img_table, ctx->d_in.p, ctx->d_out.p, ctx->d_raw.p, ctx->d_flags.p,
-                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_ccl.p, ctx->d_parent.p, ctx->d_map1.p, ctx->d_map2.p})
+                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_ccl.p, ctx->d_parent.p, ctx->d_hough.p, ctx->d_hough_acc.p,
+                    (void*)ctx->d_hough_tab, ctx->d_map1.p, ctx->d_map2.p})
         if (p)
             (void)hipFree(p);
     for (int i = 0; i < mi355_ctx::kSlots; i++) {
@@ -1843,6 +1848,247 @@ MI355_API int mi355_canny_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8
         return rc;
     return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
         return mi355_canny_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, threshold1, threshold2, flags);
+    });
+}
+
+// ---- from edges to lines ---------------------------------------------------------------------------------------------
+// What the value checks of a Hough call leave behind: the kernels' geometry and the byte counts of a call
+struct HoughCall {
+    HoughGeom g;
+    float irho;
+    size_t in, accum_frame, accum, lines, votes, count;
+};
+
+// The value checks of every Hough call (include/mi355_imgfilter.h, "from edges to lines"), numangle and numrho as the
+// header derives them.  threshold and max_lines are checked only when lines is set (the accumulator calls have neither).
+static int hough_values(int w, int h, int nframes, double rho, double theta, double min_theta, double max_theta, bool lines,
+                        int threshold, int max_lines, HoughCall* out)
+{
+    static_assert(MI355_MAX_HOUGH_ANGLES == kHoughMaxAngles && MI355_MAX_HOUGH_LINES == kHoughMaxLines,
+                  "the header's limits are the kernels' limits");
+    if (!valid_sizes(w, h, nframes) || w > MI355_MAX_WARP_SIZE || h > MI355_MAX_WARP_SIZE)
+        return MI355_ERR_BAD_ARG;
+    if (!std::isfinite(rho) || !std::isfinite(theta) || rho <= 0.0 || theta <= 0.0 || !std::isfinite(min_theta) ||
+        !std::isfinite(max_theta) || min_theta < 0.0 || max_theta > M_PI || max_theta < min_theta)
+        return MI355_ERR_BAD_ARG;
+    const float rho_f = (float)rho, theta_f = (float)theta;
+    if (!(rho_f > 0.0f) || !(theta_f > 0.0f) || !std::isfinite(rho_f))  // a double below the smallest float, or above the largest
+        return MI355_ERR_BAD_ARG;
+    const double steps = std::floor((max_theta - min_theta) / theta);
+    if (!(steps <= (double)MI355_MAX_HOUGH_ANGLES))  // numangle - 1 may pass the limit by one only through the correction below
+        return MI355_ERR_BAD_ARG;
+    int numangle = (int)steps + 1;
+    if (numangle > 1 && std::fabs(M_PI - (numangle - 1) * theta) < theta / 2)
+        numangle--;
+    const float cells = (float)(2 * (w + h) + 1) / rho_f;  // fp32 division; at most 131 065 / rho_f
+    if (!(cells < 1.0e9f))
+        return MI355_ERR_BAD_ARG;
+    const int numrho = (int)std::nearbyintf(cells);  // cvRound: half to even under the default rounding mode
+    if (numangle > MI355_MAX_HOUGH_ANGLES || numrho < 1)
+        return MI355_ERR_BAD_ARG;
+    const uint64_t accum_frame = (uint64_t)(numangle + 2) * (uint64_t)(numrho + 2) * sizeof(int32_t);
+    if (accum_frame >= (1ull << 31) || (double)accum_frame * (double)nframes > 2.4e11)
+        return MI355_ERR_BAD_ARG;
+    if (lines && (threshold < 0 || max_lines < 1 || max_lines > MI355_MAX_HOUGH_LINES))
+        return MI355_ERR_BAD_ARG;
+    if (out) {
+        out->g = {w, h, nframes, numangle, numrho, rho_f, theta_f, (float)min_theta};
+        out->irho = 1.0f / rho_f;
+        out->in = frame_bytes(w, h, nframes, 1);
+        out->accum_frame = (size_t)accum_frame;
+        out->accum = (size_t)accum_frame * (size_t)nframes;
+        out->lines = (size_t)nframes * (size_t)(lines ? max_lines : 0) * 2 * sizeof(float);
+        out->votes = (size_t)nframes * (size_t)(lines ? max_lines : 0) * sizeof(int32_t);
+        out->count = (size_t)nframes * sizeof(int32_t);
+    }
+    return MI355_OK;
+}
+
+// The header's trig table: ang is an fp32 variable that grows by theta_f; the products are taken in double
+static void hough_table(const HoughCall& c, float* tab_cos, float* tab_sin)
+{
+    float ang = c.g.min_theta_f;
+    for (int n = 0; n < c.g.numangle; ang += c.g.theta_f, n++) {
+        tab_cos[n] = (float)(std::cos((double)ang) * (double)c.irho);
+        tab_sin[n] = (float)(std::sin((double)ang) * (double)c.irho);
+    }
+}
+
+// The table on the device.  It is uploaded only when (rho, theta, min_theta, numangle) differ from the last call's: that
+// call waits for the stream (the kernels of the call before may still read the old table) and copies synchronously, like
+// the first call with a new Gaussian (k, sigma); every other call touches nothing.
+static int hough_table_dev(mi355_ctx* ctx, const HoughCall& c)
+{
+    const double key[4] = {(double)c.g.rho_f, (double)c.g.theta_f, (double)c.g.min_theta_f, (double)c.g.numangle};
+    if (ctx->d_hough_tab && std::memcmp(key, ctx->hough_key, sizeof(key)) == 0)
+        return MI355_OK;
+    if (!ctx->d_hough_tab)
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_hough_tab), 2 * MI355_MAX_HOUGH_ANGLES * sizeof(float)));
+    std::vector<float> tab(2 * (size_t)c.g.numangle);
+    hough_table(c, tab.data(), tab.data() + c.g.numangle);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->hough_key[3] = 0.0;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_hough_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    std::memcpy(ctx->hough_key, key, sizeof(key));
+    return MI355_OK;
+}
+
+MI355_API int mi355_hough_check(int w, int h, int nframes, double rho, double theta, int threshold, int max_lines,
+                                double min_theta, double max_theta)
+{
+    return hough_values(w, h, nframes, rho, theta, min_theta, max_theta, true, threshold, max_lines, nullptr);
+}
+
+MI355_API int mi355_hough_shape(int w, int h, double rho, double theta, double min_theta, double max_theta, int* numangle,
+                                int* numrho)
+{
+    HoughCall c;
+    const int rc = hough_values(w, h, 1, rho, theta, min_theta, max_theta, false, 0, 0, &c);
+    if (rc != MI355_OK)
+        return rc;
+    if (numangle)
+        *numangle = c.g.numangle;
+    if (numrho)
+        *numrho = c.g.numrho;
+    return MI355_OK;
+}
+
+MI355_API int mi355_hough_plan(int w, int h, double rho, double theta, double min_theta, double max_theta,
+                               int* angles_per_block, int* rho_splits, int* lds_cells)
+{
+    HoughCall c;
+    const int rc = hough_values(w, h, 1, rho, theta, min_theta, max_theta, false, 0, 0, &c);
+    if (rc != MI355_OK)
+        return rc;
+    const HoughPlan p = hough_plan(c.g.numangle, c.g.numrho);
+    if (angles_per_block)
+        *angles_per_block = p.angles_per_block;
+    if (rho_splits)
+        *rho_splits = p.rho_splits;
+    if (lds_cells)
+        *lds_cells = p.lds_cells;
+    return MI355_OK;
+}
+
+MI355_API int mi355_hough_trig_table(int w, int h, double rho, double theta, double min_theta, double max_theta,
+                                     float* tab_cos, float* tab_sin)
+{
+    if (!tab_cos || !tab_sin)
+        return MI355_ERR_BAD_ARG;
+    HoughCall c;
+    const int rc = hough_values(w, h, 1, rho, theta, min_theta, max_theta, false, 0, 0, &c);
+    if (rc != MI355_OK)
+        return rc;
+    hough_table(c, tab_cos, tab_sin);
+    return MI355_OK;
+}
+
+MI355_API size_t mi355_hough_accum_bytes(int w, int h, int nframes, double rho, double theta, double min_theta,
+                                         double max_theta)
+{
+    HoughCall c;
+    return hough_values(w, h, nframes, rho, theta, min_theta, max_theta, false, 0, 0, &c) == MI355_OK ? c.accum : 0;
+}
+
+// the pointer rules of the device-resident Hough calls (n ranges: the input first; null entries are absent outputs), then
+// the device, the pooled scratch and the table
+static int hough_check_dev(mi355_ctx* ctx, const HoughCall& c, const void* const* ptr, const size_t* len, int n)
+{
+    for (int i = 0; i < n; i++) {
+        if (!ptr[i])
+            continue;
+        if (i > 0 && (reinterpret_cast<uintptr_t>(ptr[i]) & 3u))
+            return MI355_ERR_BAD_ARG;
+        for (int j = 0; j < i; j++)
+            if (ptr[j] && overlap(ptr[i], len[i], ptr[j], len[j]))
+                return MI355_ERR_BAD_ARG;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = ensure(ctx, ctx->d_hough, hough_scratch_bytes(c.g));
+    return rc == MI355_OK ? hough_table_dev(ctx, c) : rc;
+}
+
+MI355_API int mi355_hough_accum_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_accum, int w, int h, int nframes,
+                                          double rho, double theta, double min_theta, double max_theta)
+{
+    if (!ctx || !d_in || !d_accum)
+        return MI355_ERR_BAD_ARG;
+    HoughCall c;
+    int rc = hough_values(w, h, nframes, rho, theta, min_theta, max_theta, false, 0, 0, &c);
+    if (rc != MI355_OK)
+        return rc;
+    const void* ptr[2] = {d_in, d_accum};
+    const size_t len[2] = {c.in, c.accum};
+    rc = hough_check_dev(ctx, c, ptr, len, 2);
+    if (rc != MI355_OK)
+        return rc;
+    HIP_TRY(ctx, launch_hough_accum(ctx->stream, static_cast<const uint8_t*>(d_in), d_accum, ctx->d_hough_tab,
+                                    ctx->d_hough.p, c.g));
+    return MI355_OK;
+}
+
+MI355_API int mi355_hough_lines_gray8_dev(mi355_ctx* ctx, const void* d_in, float* d_lines, int32_t* d_votes,
+                                          int32_t* d_count, int32_t* d_accum, int w, int h, int nframes, double rho,
+                                          double theta, int threshold, int max_lines, double min_theta, double max_theta)
+{
+    if (!ctx || !d_in || !d_lines || !d_count)
+        return MI355_ERR_BAD_ARG;
+    HoughCall c;
+    int rc = hough_values(w, h, nframes, rho, theta, min_theta, max_theta, true, threshold, max_lines, &c);
+    if (rc != MI355_OK)
+        return rc;
+    const void* ptr[5] = {d_in, d_lines, d_votes, d_count, d_accum};
+    const size_t len[5] = {c.in, c.lines, c.votes, c.count, c.accum};
+    rc = hough_check_dev(ctx, c, ptr, len, 5);
+    if (rc == MI355_OK && !d_accum) {
+        rc = ensure(ctx, ctx->d_hough_acc, c.accum);
+        d_accum = static_cast<int32_t*>(ctx->d_hough_acc.p);
+    }
+    if (rc != MI355_OK)
+        return rc;
+    HIP_TRY(ctx, launch_hough_accum(ctx->stream, static_cast<const uint8_t*>(d_in), d_accum, ctx->d_hough_tab,
+                                    ctx->d_hough.p, c.g));
+    HIP_TRY(ctx, launch_hough_lines(ctx->stream, d_accum, d_lines, d_votes, d_count, ctx->d_hough.p, c.g, threshold,
+                                    max_lines));
+    return MI355_OK;
+}
+
+MI355_API int mi355_hough_lines_gray8_batched(mi355_ctx* ctx, const uint8_t* in, float* lines, int32_t* votes,
+                                              int32_t* count, int w, int h, int nframes, double rho, double theta,
+                                              int threshold, int max_lines, double min_theta, double max_theta,
+                                              uint64_t prof_ns[6])
+{
+    if (!ctx || !in || !lines || !count)
+        return MI355_ERR_BAD_ARG;
+    HoughCall c;
+    int rc = hough_values(w, h, nframes, rho, theta, min_theta, max_theta, true, threshold, max_lines, &c);
+    if (rc != MI355_OK)
+        return rc;
+    // the three outputs side by side in the pooled output buffer; the accumulator is the pooled one
+    const size_t at_votes = c.lines, at_count = at_votes + c.votes;
+    HostIO io;
+    rc = stage_host(ctx, c.in, 1, at_count + c.count, &io);  // BGR input: unsupported
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_hough, hough_scratch_bytes(c.g));  // outside the timed window, like the table and ...
+    if (rc == MI355_OK)
+        rc = hough_table_dev(ctx, c);
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_hough_acc, c.accum);  // ... the accumulator
+    if (rc != MI355_OK)
+        return rc;
+    io.out_bytes = c.lines;  // what the round trip reads back behind the kernels; the small outputs go ahead of it
+    uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out.p);
+    return timed_roundtrip(ctx, io, in, reinterpret_cast<uint8_t*>(lines), prof_ns, [&] {
+        const int lrc = mi355_hough_lines_gray8_dev(ctx, ctx->d_in.p, reinterpret_cast<float*>(d_out),
+                                                    reinterpret_cast<int32_t*>(d_out + at_votes),
+                                                    reinterpret_cast<int32_t*>(d_out + at_count), nullptr, w, h, nframes, rho,
+                                                    theta, threshold, max_lines, min_theta, max_theta);
+        if (lrc != MI355_OK)
+            return lrc;
+        HIP_TRY(ctx, hipMemcpyAsync(count, d_out + at_count, c.count, hipMemcpyDeviceToHost, ctx->stream));
+        if (votes)
+            HIP_TRY(ctx, hipMemcpyAsync(votes, d_out + at_votes, c.votes, hipMemcpyDeviceToHost, ctx->stream));
+        return (int)MI355_OK;
     });
 }
 

@@ -180,6 +180,36 @@ hipError_t launch_canny_nms(hipStream_t stream, const uint8_t* d_in, uint8_t* d_
 hipError_t launch_hysteresis(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, int32_t* d_parent, int w, int h,
                              int nframes, int low, int high, bool conn8);
 
+// cv::HoughLines of single-channel edge maps (hough.hip; semantics: include/mi355_imgfilter.h, "from edges to lines").
+// The caller (capi.hip) derives numangle, numrho and the trig table on the host; d_tab holds numangle cosines * irho, then
+// numangle sines * irho.  d_scratch: hough_scratch_bytes(g) bytes, 16-byte aligned (per-frame counters, then the point
+// lists of the voting launch and the candidate lists of the selection, which share their bytes).
+//   hough_plan          how a row of numrho cells is voted: up to kHoughBlockAngles whole rows per block while they fit
+//                       kHoughLdsCells cells of LDS, else one angle per block and ceil(numrho / kHoughLdsCells) rho ranges
+//                       of kHoughLdsCells cells; the fields are 0 for arguments no call accepts
+//   launch_hough_accum  one memset node and two launches: the (numangle + 2) x (numrho + 2) int32 accumulator of every
+//                       frame, the zero ring included
+//   launch_hough_lines  one memset node and two launches: d_count = the peaks of d_accum above threshold, d_lines / d_votes
+//                       (d_votes may be null) the first max_lines of them by votes descending, cell ascending, zero filled
+// No allocation, no wait, nothing the host reads.
+constexpr int kHoughMaxAngles = 1024;
+constexpr int kHoughMaxLines = 4096;
+constexpr int kHoughLdsCells = 36864;  // 144 KiB of the CU's 160: three rows of a 4K frame at rho = 1 (12 001 cells each)
+constexpr int kHoughBlockAngles = 8;
+struct HoughGeom {
+    int w, h, nframes, numangle, numrho;
+    float rho_f, theta_f, min_theta_f;
+};
+struct HoughPlan {
+    int angles_per_block, rho_splits, span, lds_cells;
+};
+HoughPlan hough_plan(int numangle, int numrho);
+size_t hough_scratch_bytes(const HoughGeom& g);  // 0 for a geometry the launches reject
+hipError_t launch_hough_accum(hipStream_t stream, const uint8_t* d_in, int32_t* d_accum, const float* d_tab, void* d_scratch,
+                              const HoughGeom& g);
+hipError_t launch_hough_lines(hipStream_t stream, const int32_t* d_accum, float* d_lines, int32_t* d_votes, int32_t* d_count,
+                              void* d_scratch, const HoughGeom& g, int threshold, int max_lines);
+
 // cv::resize of tightly packed 8-bit frames (resize.hip): bpp 4 (RGBA, dword-aligned) or 1 (gray8, any byte alignment);
 // interp 0 nearest, 1 linear (11-bit fixed point; AREA's result at exactly half size), 3 area with integer factors
 // 1 .. kResizeMaxAreaFactor (resize_area_factors says whether a size pair has them; anything else is

@@ -43,6 +43,9 @@ MAX_CLAHE_TILES = 16
 MAX_CCL_STATS_ROWS = 1 << 24
 # cv::Canny (mi355_canny_*): flags = 0 or CANNY_L2GRADIENT (magnitude dx^2 + dy^2 instead of |dx| + |dy|)
 CANNY_L2GRADIENT = 1
+# cv::HoughLines (mi355_hough_*): at most MAX_HOUGH_ANGLES angle rows and 1 .. MAX_HOUGH_LINES lines per frame
+MAX_HOUGH_ANGLES = 1024
+MAX_HOUGH_LINES = 4096
 # cv::resize (mi355_resize_*): OpenCV's enum values; AREA only with integer factors 1 .. MAX_AREA_FACTOR
 INTERP_NEAREST, INTERP_LINEAR, INTERP_AREA = 0, 1, 3
 MAX_AREA_FACTOR = 16
@@ -193,6 +196,13 @@ def load_library(path=None):
         "mi355_canny_check": [_ci, _ci, _ci, _cd, _cd, _ci],
         "mi355_canny_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _cd, _cd, _ci],
         "mi355_canny_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _cd, _cd, _ci, _u64p],
+        "mi355_hough_check": [_ci, _ci, _ci, _cd, _cd, _ci, _ci, _cd, _cd],
+        "mi355_hough_shape": [_ci, _ci, _cd, _cd, _cd, _cd, ctypes.POINTER(_ci), ctypes.POINTER(_ci)],
+        "mi355_hough_trig_table": [_ci, _ci, _cd, _cd, _cd, _cd, _f32p, _f32p],
+        "mi355_hough_plan": [_ci, _ci, _cd, _cd, _cd, _cd, ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_ci)],
+        "mi355_hough_accum_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _cd, _cd, _cd, _cd],
+        "mi355_hough_lines_gray8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cd, _cd, _ci, _ci, _cd, _cd],
+        "mi355_hough_lines_gray8_batched": [_vp, _u8p, _vp, _vp, _vp, _ci, _ci, _ci, _cd, _cd, _ci, _ci, _cd, _cd, _u64p],
         "mi355_yuv_check": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_yuv_to_rgba8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_rgba8_to_yuv_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci],
@@ -239,6 +249,9 @@ def load_library(path=None):
     if hasattr(lib, "mi355_yuv_frame_bytes") or path == _LIB:
         lib.mi355_yuv_frame_bytes.argtypes = [_ci, _ci, _ci, _ci, _ci]
         lib.mi355_yuv_frame_bytes.restype = ctypes.c_size_t
+    if hasattr(lib, "mi355_hough_accum_bytes") or path == _LIB:
+        lib.mi355_hough_accum_bytes.argtypes = [_ci, _ci, _ci, _cd, _cd, _cd, _cd]
+        lib.mi355_hough_accum_bytes.restype = ctypes.c_size_t
     lib.mi355_strerror.argtypes = [_ci]
     lib.mi355_strerror.restype = ctypes.c_char_p
     lib.mi355_build_info.argtypes = []
@@ -401,6 +414,49 @@ def canny_check(w, h, nframes=1, threshold1=50.0, threshold2=150.0, flags=0):
     """mi355_canny_check, a pure host function: the code (0 ok, -1 bad argument) a Canny call with these values returns
     before any device work."""
     return load_library().mi355_canny_check(int(w), int(h), int(nframes), float(threshold1), float(threshold2), int(flags))
+
+
+def hough_check(w, h, nframes=1, rho=1.0, theta=np.pi / 180, threshold=0, max_lines=1, min_theta=0.0, max_theta=np.pi):
+    """mi355_hough_check, a pure host function: the code (0 ok, -1 bad argument) a Hough lines call with these values
+    returns before any device work."""
+    return load_library().mi355_hough_check(int(w), int(h), int(nframes), float(rho), float(theta), int(threshold),
+                                            int(max_lines), float(min_theta), float(max_theta))
+
+
+def hough_shape(w, h, rho=1.0, theta=np.pi / 180, min_theta=0.0, max_theta=np.pi):
+    """mi355_hough_shape, a pure host function: (numangle, numrho) of the accumulator, whose frames are
+    (numangle + 2, numrho + 2) int32 with a zero ring."""
+    na, nr = _ci(0), _ci(0)
+    rc = load_library().mi355_hough_shape(int(w), int(h), float(rho), float(theta), float(min_theta), float(max_theta),
+                                          ctypes.byref(na), ctypes.byref(nr))
+    _check("mi355_hough_shape", rc)
+    return na.value, nr.value
+
+
+def hough_trig_table(w, h, rho=1.0, theta=np.pi / 180, min_theta=0.0, max_theta=np.pi):
+    """mi355_hough_trig_table, a pure host function: (tab_cos, tab_sin), numangle float32 each, as the kernels get them."""
+    na, _ = hough_shape(w, h, rho, theta, min_theta, max_theta)
+    tc, ts = np.empty(na, np.float32), np.empty(na, np.float32)
+    rc = load_library().mi355_hough_trig_table(int(w), int(h), float(rho), float(theta), float(min_theta), float(max_theta),
+                                               tc.ctypes.data_as(_f32p), ts.ctypes.data_as(_f32p))
+    _check("mi355_hough_trig_table", rc)
+    return tc, ts
+
+
+def hough_accum_bytes(w, h, nframes=1, rho=1.0, theta=np.pi / 180, min_theta=0.0, max_theta=np.pi):
+    """mi355_hough_accum_bytes, a pure host function: the bytes of nframes accumulators, 0 for rejected values."""
+    return int(load_library().mi355_hough_accum_bytes(int(w), int(h), int(nframes), float(rho), float(theta),
+                                                      float(min_theta), float(max_theta)))
+
+
+def hough_plan(w, h, rho=1.0, theta=np.pi / 180, min_theta=0.0, max_theta=np.pi):
+    """mi355_hough_plan, a pure host function: (angle rows per workgroup, rho ranges per row, LDS budget in cells) of the
+    voting launch for these values."""
+    a, s, c = _ci(0), _ci(0), _ci(0)
+    rc = load_library().mi355_hough_plan(int(w), int(h), float(rho), float(theta), float(min_theta), float(max_theta),
+                                         ctypes.byref(a), ctypes.byref(s), ctypes.byref(c))
+    _check("mi355_hough_plan", rc)
+    return a.value, s.value, c.value
 
 
 def yuv_frame_bytes(layout, w, h, pitch=0, rows=0):
@@ -690,6 +746,26 @@ class Context:
         _check("mi355_canny_gray8_batched", rc, self._h)
         out = out[0] if one else out
         return (out, list(prof)) if profile else out
+
+    def hough_lines_gray8(self, edges, rho, theta, threshold, max_lines=256, min_theta=0.0, max_theta=np.pi,
+                          profile=False):
+        """cv::HoughLines(edges, lines, rho, theta, threshold, 0, 0, min_theta, max_theta) of (h, w) / (n, h, w)
+        single-channel edge maps (mi355_hough_lines_gray8_batched).  Returns (lines, votes, count): float32
+        (max_lines, 2) rows of (rho, theta) by votes descending then accumulator cell ascending, their int32 votes, and the
+        number of peaks, which may exceed max_lines; rows past min(count, max_lines) are zero."""
+        frames, one = self._frames("hough_lines_gray8", edges, 1)
+        n, h, w = frames.shape
+        lines = np.empty((n, int(max_lines), 2), np.float32) if max_lines > 0 else np.empty((n, 0, 2), np.float32)
+        votes = np.empty((n, lines.shape[1]), np.int32)
+        count = np.empty(n, np.int32)
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_hough_lines_gray8_batched(
+            self._h, frames.ctypes.data_as(_u8p), _vp(lines.ctypes.data), _vp(votes.ctypes.data), _vp(count.ctypes.data),
+            w, h, n, float(rho), float(theta), int(threshold), int(max_lines), float(min_theta), float(max_theta),
+            prof if profile else None)
+        _check("mi355_hough_lines_gray8_batched", rc, self._h)
+        out = (lines[0], votes[0], int(count[0])) if one else (lines, votes, count)
+        return out + (list(prof),) if profile else out
 
     # -- frames from a decoder or a camera (mi355_yuv_to_rgba8_batched / mi355_rgba8_to_yuv_batched) -----
     def yuv_to_rgba8(self, yuv, w, h, layout, standard=YUV_BT601, pitch=0, rows=0, profile=False):
@@ -989,6 +1065,25 @@ class Context:
         rc = self._lib.mi355_canny_gray8_dev(self._h, _vp(int(d_in or 0)), _vp(int(d_out or 0)), int(w), int(h),
                                              int(nframes), float(threshold1), float(threshold2), int(flags))
         _check("mi355_canny_gray8_dev", rc, self._h)
+
+    def hough_accum_gray8_dev(self, d_in, d_accum, w, h, nframes, rho, theta, min_theta=0.0, max_theta=np.pi):
+        """mi355_hough_accum_gray8_dev: the int32 accumulators (hough_accum_bytes) of nframes gray8 edge maps at d_in to
+        d_accum; two launches behind a memset, no synchronisation."""
+        rc = self._lib.mi355_hough_accum_gray8_dev(self._h, _vp(int(d_in or 0)), _vp(int(d_accum or 0)), int(w), int(h),
+                                                   int(nframes), float(rho), float(theta), float(min_theta),
+                                                   float(max_theta))
+        _check("mi355_hough_accum_gray8_dev", rc, self._h)
+
+    def hough_lines_gray8_dev(self, d_in, d_lines, d_votes, d_count, d_accum, w, h, nframes, rho, theta, threshold,
+                              max_lines, min_theta=0.0, max_theta=np.pi):
+        """mi355_hough_lines_gray8_dev: cv::HoughLines of nframes gray8 edge maps at d_in: (max_lines, 2) float32 rows per
+        frame to d_lines, their votes to d_votes (0: not wanted), the peak counts to d_count; d_accum 0: the accumulator
+        is pooled in the context.  Four launches behind two memsets, no synchronisation."""
+        rc = self._lib.mi355_hough_lines_gray8_dev(
+            self._h, _vp(int(d_in or 0)), _vp(int(d_lines or 0)), _vp(int(d_votes or 0)), _vp(int(d_count or 0)),
+            _vp(int(d_accum or 0)), int(w), int(h), int(nframes), float(rho), float(theta), int(threshold),
+            int(max_lines), float(min_theta), float(max_theta))
+        _check("mi355_hough_lines_gray8_dev", rc, self._h)
 
     def hist_gray8_dev(self, d_in, d_hist, w, h, nframes):
         """mi355_hist_gray8_dev: nframes x 256 uint32 counts to d_hist (overwritten), no synchronisation."""
