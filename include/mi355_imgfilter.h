@@ -697,6 +697,53 @@ int mi355_ccl_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t* labels, 
                             uint64_t* sums, int w, int h, int nframes, int connectivity, int stats_rows,
                             uint64_t prof_ns[6]);
 
+/* ---- how far from the background: cv::distanceTransform(mask, dist, DIST_L2, DIST_MASK_PRECISE, CV_32F) -----------------
+ * The exact Euclidean distance transform of gray8 masks: per pixel the squared distance to the nearest zero pixel, its
+ * square root, and which zero pixel that is (the step between "mask" and "what to do with each blob": watershed seeds that
+ * split touching blobs, thickness, clearance, chamfer matching, nearest-seed lookups).  gray8 frames only (the
+ * single-channel rules: tightly packed, any byte alignment, any width >= 1, frames are independent,
+ * MI355_ERR_UNSUPPORTED under MI355_INPUT_BGR in the host form).  Entry points of their own, not filter ids: the outputs
+ * do not fit (k, sigma).  OpenCV is not installed where this library is built and tested: nobody has compared these
+ * calls with an OpenCV build; the rules below — not OpenCV — are the contract, this library's own.
+ * Polarity.  OpenCV's: a pixel whose byte is zero is a SITE.  Every pixel gets its distance to the nearest site of its
+ * frame; a site gets 0.
+ * Squared distance.  int32 d_sq[nframes][h][w] = the minimum over the frame's sites (x', y') of
+ * (x - x')^2 + (y - y')^2, exactly.  With w, h <= MI355_MAX_DIST_DIM the largest value is 2 * 16383^2 < 2^30: that is
+ * why the limit exists.
+ * Distance.  float d_dist[nframes][h][w] = sqrtf((float)sq): the int32 -> fp32 conversion rounds to nearest, ties to
+ * even (it matters above 2^24, which a side above 4096 can reach), the square root is the correctly rounded fp32 one.
+ * In numpy: np.sqrt(sq.astype(np.float32)).  It corresponds to DIST_L2 with DIST_MASK_PRECISE and CV_32F.
+ * Nearest site.  int32 d_nearest[nframes][h][w] = y' * w + x' of the nearest site, within its frame.  Among equally near
+ * sites the one with the smallest column x' is taken, and among those the one with the smallest row y' — COLUMN first,
+ * not raster order.  A site's nearest site is itself.  (DIST_LABEL_PIXEL numbers the sites instead; this is the index.)
+ * A frame without a site gets MI355_DIST_NONE, +INFINITY and -1 in every pixel; the other frames of the batch are
+ * unaffected.  A column without a site in a frame that has one is an ordinary case.
+ * Optional outputs.  Any of d_sq, d_dist, d_nearest may be NULL, not all three.  An output that is present holds the
+ * same bytes whatever the others are.
+ * MI355_ERR_BAD_ARG, before any device work: a null context or input, or all three outputs null; sizes the histogram
+ * calls reject; w or h above MI355_MAX_DIST_DIM; an output that is not 4-byte aligned; a present output range that
+ * overlaps the input or another present output.
+ *   mi355_dist_check          pure host function returning the code a call with these values returns before any device work.
+ *   mi355_dist_gray8_dev      the rules of mi355_filter_dev: two launches on the context's stream (columns, rows), no
+ *                             synchronisation.  The scratch, 2 BYTES PER PIXEL (rows padded to four pixels: the signed row
+ *                             offset to the nearest site of the pixel's own column), is pooled in the context: after the
+ *                             first call for a given (w, h, nframes) a call allocates nothing and waits for nothing, so it
+ *                             can be captured into a hipGraph.  The work of a row is bounded by its width alone
+ *                             (O(w log w)), never by the content.
+ *   mi355_dist_gray8_batched  host buffers: H2D, the launches, D2H through the context's pooled buffers; prof_ns (may be
+ *                             NULL) gets the six timestamps of mi355_filter_batched.  The first output the caller takes is
+ *                             the read that is timed; the copies of the others are enqueued ahead of it and fall into the
+ *                             kernel interval.
+ * Not offered: DIST_L1 and DIST_C, the 3x3 and 5x5 chamfer approximations, CV_8U output, DIST_LABEL_CCOMP, RGBA input,
+ * the streamed and group forms, row pitch and ROI. */
+#define MI355_MAX_DIST_DIM 16384
+#define MI355_DIST_NONE    2147483647      /* d_sq of a frame without a zero pixel */
+int mi355_dist_check(int w, int h, int nframes);
+int mi355_dist_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_sq, float* d_dist, int32_t* d_nearest, int w, int h,
+                         int nframes);
+int mi355_dist_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t* sq, float* dist, int32_t* nearest, int w, int h,
+                             int nframes, uint64_t prof_ns[6]);
+
 /* ---- from gradients to edges: hysteresis thresholding, and cv::Canny(image, edges, threshold1, threshold2, 3, L2gradient) --
  * The step between "gradient magnitude" and "mask": one-pixel-wide, connected edges without leaving the device.  gray8
  * frames only, in and out (the single-channel rules: tightly packed, any byte alignment of input and output, any width

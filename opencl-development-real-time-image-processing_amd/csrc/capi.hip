@@ -55,6 +55,7 @@ struct mi355_ctx {
     DevBuf d_hist = {};   // per-frame 256-bin histograms of EQUALIZE_GRAY8 / OTSU_GRAY8 (hist.hip)
     DevBuf d_lut = {};    // their per-frame 256-byte tables
     DevBuf d_ccl = {};    // per-block component counts, then offsets, of the labelling calls (ccl.hip)
+    DevBuf d_dist = {};   // per-pixel int16 row offsets to the column's nearest site of the distance calls (dist.hip)
     DevBuf d_parent = {};  // the union-find parent array, 4 bytes per pixel, of the hysteresis and Canny calls (canny.hip)
     DevBuf d_hough = {};      // counters, point lists and candidate lists of the Hough calls (hough.hip)
     DevBuf d_hough_acc = {};  // their accumulator when the caller passes none
@@ -850,7 +851,7 @@ MI355_API int mi355_ctx_destroy(mi355_ctx* ctx)
     for (void* p : ctx->pinned)
         (void)hipHostFree(p);
     for (void* p : {(void*)ctx->d_acc, (void*)ctx->d_img_table, ctx->d_in.p, ctx->d_out.p, ctx->d_raw.p, ctx->d_flags.p,
-                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_ccl.p, ctx->d_parent.p, ctx->d_hough.p, ctx->d_hough_acc.p,
+                    ctx->d_hist.p, ctx->d_lut.p, ctx->d_ccl.p, ctx->d_dist.p, ctx->d_parent.p, ctx->d_hough.p, ctx->d_hough_acc.p,
                     (void*)ctx->d_hough_tab, ctx->d_map1.p, ctx->d_map2.p})
         if (p)
             (void)hipFree(p);
@@ -1719,6 +1720,94 @@ MI355_API int mi355_ccl_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t
             HIP_TRY(ctx, hipMemcpyAsync(stats, d_out + at_stats, nb.stats, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipMemcpyAsync(sums, d_out + at_sums, nb.sums, hipMemcpyDeviceToHost, ctx->stream));
         }
+        return (int)MI355_OK;
+    });
+}
+
+// ---- how far from the background -------------------------------------------------------------------------------------
+// The value checks of every distance call (include/mi355_imgfilter.h, "how far from the background")
+static int dist_values(int w, int h, int nframes)
+{
+    static_assert(MI355_MAX_DIST_DIM == kDistMaxDim, "the header's limit is the kernels' limit");
+    const int rc = check_filter(MI355_FILTER_EQUALIZE_GRAY8, w, h, nframes, 0, 0.0f, nullptr);
+    if (rc != MI355_OK)
+        return rc;
+    return w > MI355_MAX_DIST_DIM || h > MI355_MAX_DIST_DIM ? MI355_ERR_BAD_ARG : MI355_OK;
+}
+
+MI355_API int mi355_dist_check(int w, int h, int nframes)
+{
+    return dist_values(w, h, nframes);
+}
+
+MI355_API int mi355_dist_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_sq, float* d_dist, int32_t* d_nearest,
+                                   int w, int h, int nframes)
+{
+    if (!ctx || !d_in || (!d_sq && !d_dist && !d_nearest))
+        return MI355_ERR_BAD_ARG;
+    const int rc = dist_values(w, h, nframes);
+    if (rc != MI355_OK)
+        return rc;
+    // the ranges in play: the input and the outputs this call writes
+    const size_t px = (size_t)w * h * nframes;
+    const void* ptr[4] = {d_in, d_sq, d_dist, d_nearest};
+    const size_t len[4] = {px, px * sizeof(int32_t), px * sizeof(float), px * sizeof(int32_t)};
+    for (int i = 1; i < 4; i++) {
+        if (!ptr[i])
+            continue;
+        if (reinterpret_cast<uintptr_t>(ptr[i]) & 3u)
+            return MI355_ERR_BAD_ARG;
+        for (int j = 0; j < i; j++)
+            if (ptr[j] && overlap(ptr[i], len[i], ptr[j], len[j]))
+                return MI355_ERR_BAD_ARG;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int erc = ensure(ctx, ctx->d_dist, dist_scratch_bytes(w, h, nframes));
+    if (erc != MI355_OK)
+        return erc;
+    HIP_TRY(ctx, launch_dist(ctx->stream, static_cast<const uint8_t*>(d_in), d_sq, d_dist, d_nearest,
+                             static_cast<int16_t*>(ctx->d_dist.p), w, h, nframes));
+    return MI355_OK;
+}
+
+MI355_API int mi355_dist_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t* sq, float* dist, int32_t* nearest,
+                                       int w, int h, int nframes, uint64_t prof_ns[6])
+{
+    if (!ctx || !in || (!sq && !dist && !nearest))
+        return MI355_ERR_BAD_ARG;
+    int rc = dist_values(w, h, nframes);
+    if (rc != MI355_OK)
+        return rc;
+    // the outputs the caller takes side by side in the pooled output buffer, 4 bytes per pixel each; the round trip reads
+    // back the first of them, the others leave the device ahead of it and fall into the kernel interval
+    const size_t px = (size_t)w * h * nframes, plane = px * sizeof(int32_t);
+    void* host[3] = {sq, dist, nearest};
+    size_t at[3], total = 0;
+    int first = -1;
+    for (int i = 0; i < 3; i++) {
+        at[i] = total;
+        if (host[i]) {
+            total += plane;
+            first = first < 0 ? i : first;
+        }
+    }
+    HostIO io;
+    rc = stage_host(ctx, px, 1, total, &io);  // BGR input: unsupported
+    if (rc == MI355_OK)
+        rc = ensure(ctx, ctx->d_dist, dist_scratch_bytes(w, h, nframes));  // outside the timed window
+    if (rc != MI355_OK)
+        return rc;
+    io.out_bytes = plane;
+    uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out.p);
+    return timed_roundtrip(ctx, io, in, static_cast<uint8_t*>(host[first]), prof_ns, [&] {
+        const int lrc = mi355_dist_gray8_dev(ctx, ctx->d_in.p, sq ? reinterpret_cast<int32_t*>(d_out + at[0]) : nullptr,
+                                             dist ? reinterpret_cast<float*>(d_out + at[1]) : nullptr,
+                                             nearest ? reinterpret_cast<int32_t*>(d_out + at[2]) : nullptr, w, h, nframes);
+        if (lrc != MI355_OK)
+            return lrc;
+        for (int i = first + 1; i < 3; i++)
+            if (host[i])
+                HIP_TRY(ctx, hipMemcpyAsync(host[i], d_out + at[i], plane, hipMemcpyDeviceToHost, ctx->stream));
         return (int)MI355_OK;
     });
 }

@@ -210,6 +210,19 @@ hipError_t launch_hough_accum(hipStream_t stream, const uint8_t* d_in, int32_t* 
 hipError_t launch_hough_lines(hipStream_t stream, const int32_t* d_accum, float* d_lines, int32_t* d_votes, int32_t* d_count,
                               void* d_scratch, const HoughGeom& g, int threshold, int max_lines);
 
+// cv::distanceTransform(DIST_L2, DIST_MASK_PRECISE) of single-channel masks (dist.hip; semantics:
+// include/mi355_imgfilter.h, "how far from the background"): frames of 1 .. kDistMaxDim pixels a side at any byte
+// alignment, a pixel is a site iff its byte is zero.  d_sq (int32), d_dist (float) and d_nearest (int32), each 4-byte
+// aligned and each optional (at least one is not null), take one entry per pixel.  d_scratch takes dist_scratch_bytes():
+// the signed row offset to the nearest site of the pixel's own column, one int16 per pixel, rows padded to four entries.
+// Two launches on the stream (columns, rows), no allocation, no wait, nothing the host reads.  dist_col_lds_bytes is the
+// LDS of the column launch for a frame of h rows (it grows with h: 144 KiB at kDistMaxDim); 0 for an h no call accepts.
+constexpr int kDistMaxDim = 16384;
+int dist_col_lds_bytes(int h);
+size_t dist_scratch_bytes(int w, int h, int nframes);  // 0 for sizes launch_dist rejects
+hipError_t launch_dist(hipStream_t stream, const uint8_t* d_in, int32_t* d_sq, float* d_dist, int32_t* d_nearest,
+                       int16_t* d_scratch, int w, int h, int nframes);
+
 // cv::resize of tightly packed 8-bit frames (resize.hip): bpp 4 (RGBA, dword-aligned) or 1 (gray8, any byte alignment);
 // interp 0 nearest, 1 linear (11-bit fixed point; AREA's result at exactly half size), 3 area with integer factors
 // 1 .. kResizeMaxAreaFactor (resize_area_factors says whether a size pair has them; anything else is

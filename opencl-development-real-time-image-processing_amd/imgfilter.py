@@ -41,6 +41,10 @@ ADAPTIVE_BINARY, ADAPTIVE_BINARY_INV = 0, 1
 MAX_CLAHE_TILES = 16
 # connected components (mi355_ccl_*): connectivity 4 or 8, 0 <= stats_rows <= MAX_CCL_STATS_ROWS
 MAX_CCL_STATS_ROWS = 1 << 24
+# cv::distanceTransform (mi355_dist_*): sides of 1 .. MAX_DIST_DIM; DIST_NONE is the squared distance of a frame without
+# a zero pixel
+MAX_DIST_DIM = 16384
+DIST_NONE = 2147483647
 # cv::Canny (mi355_canny_*): flags = 0 or CANNY_L2GRADIENT (magnitude dx^2 + dy^2 instead of |dx| + |dy|)
 CANNY_L2GRADIENT = 1
 # cv::HoughLines (mi355_hough_*): at most MAX_HOUGH_ANGLES angle rows and 1 .. MAX_HOUGH_LINES lines per frame
@@ -190,6 +194,9 @@ def load_library(path=None):
         "mi355_ccl_check": [_ci, _ci, _ci, _ci, _ci],
         "mi355_ccl_gray8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci],
         "mi355_ccl_gray8_batched": [_vp, _u8p, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _u64p],
+        "mi355_dist_check": [_ci, _ci, _ci],
+        "mi355_dist_gray8_dev": [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci],
+        "mi355_dist_gray8_batched": [_vp, _u8p, _vp, _vp, _vp, _ci, _ci, _ci, _u64p],
         "mi355_hysteresis_check": [_ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_hysteresis_gray8_dev": [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci],
         "mi355_hysteresis_gray8_batched": [_vp, _u8p, _u8p, _ci, _ci, _ci, _ci, _ci, _ci, _u64p],
@@ -402,6 +409,12 @@ def ccl_check(w, h, nframes=1, connectivity=8, stats_rows=0):
     """mi355_ccl_check, a pure host function: the code (0 ok, -1 bad argument) a labelling call with these values returns
     before any device work."""
     return load_library().mi355_ccl_check(int(w), int(h), int(nframes), int(connectivity), int(stats_rows))
+
+
+def dist_check(w, h, nframes=1):
+    """mi355_dist_check, a pure host function: the code (0 ok, -1 bad argument) a distance-transform call with these values
+    returns before any device work."""
+    return load_library().mi355_dist_check(int(w), int(h), int(nframes))
 
 
 def hysteresis_check(w, h, nframes=1, low=0, high=0, connectivity=8):
@@ -718,6 +731,26 @@ class Context:
                 centroids = sums.astype(np.float64) / stats[:, :, 4:5].astype(np.float64)
             out += (stats[0], centroids[0]) if one else (stats, centroids)
         return out + (list(prof),) if profile else out
+
+    def dist_gray8(self, masks, squared=False, nearest=False, profile=False):
+        """cv::distanceTransform(mask, DIST_L2, DIST_MASK_PRECISE, CV_32F) of (h, w) / (n, h, w) single-channel masks
+        (mi355_dist_gray8_batched): float32 distances to the nearest zero pixel.  With squared also the exact int32 squared
+        distances, with nearest also the int32 index y' * w + x' of the nearest zero pixel (smallest column, then smallest
+        row among equally near ones); a frame without a zero pixel holds +inf, DIST_NONE and -1.  Returns dist, or a tuple
+        (dist[, sq][, nearest]); with profile, the six timestamps follow."""
+        frames, one = self._frames("dist_gray8", masks, 1)
+        n, h, w = frames.shape
+        dist = np.empty((n, h, w), np.float32)
+        sq = np.empty((n, h, w), np.int32) if squared else None
+        near = np.empty((n, h, w), np.int32) if nearest else None
+        prof = (ctypes.c_uint64 * 6)()
+        rc = self._lib.mi355_dist_gray8_batched(
+            self._h, frames.ctypes.data_as(_u8p), _vp(sq.ctypes.data) if squared else None, _vp(dist.ctypes.data),
+            _vp(near.ctypes.data) if nearest else None, w, h, n, prof if profile else None)
+        _check("mi355_dist_gray8_batched", rc, self._h)
+        out = tuple(a[0] if one else a for a in (dist, sq, near) if a is not None)
+        out += (list(prof),) if profile else ()
+        return out[0] if len(out) == 1 else out
 
     def hysteresis_gray8(self, y, low, high, connectivity=8, profile=False):
         """Hysteresis threshold of (h, w) / (n, h, w) single-channel response maps (mi355_hysteresis_gray8_batched): 255
@@ -1051,6 +1084,14 @@ class Context:
                                            _vp(int(d_stats or 0)), _vp(int(d_sums or 0)), int(w), int(h), int(nframes),
                                            int(connectivity), int(stats_rows))
         _check("mi355_ccl_gray8_dev", rc, self._h)
+
+    def dist_gray8_dev(self, d_in, d_sq, d_dist, d_nearest, w, h, nframes):
+        """mi355_dist_gray8_dev: the distance transform of nframes gray8 masks at d_in: int32 squared distances to d_sq,
+        float32 distances to d_dist, int32 nearest-site indices to d_nearest (each may be 0 / None, not all three); two
+        launches, no synchronisation; the scratch (2 bytes per pixel) is pooled in the context."""
+        rc = self._lib.mi355_dist_gray8_dev(self._h, _vp(int(d_in or 0)), _vp(int(d_sq or 0)), _vp(int(d_dist or 0)),
+                                            _vp(int(d_nearest or 0)), int(w), int(h), int(nframes))
+        _check("mi355_dist_gray8_dev", rc, self._h)
 
     def hysteresis_gray8_dev(self, d_in, d_out, w, h, nframes, low, high, connectivity=8):
         """mi355_hysteresis_gray8_dev: the hysteresis threshold of nframes gray8 response maps at d_in to d_out; up to
