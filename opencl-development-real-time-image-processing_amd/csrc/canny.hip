@@ -20,11 +20,12 @@
 //   hyst_mark_kernel   every strong pixel finds its root with two loads and sets bit 31 of the root's own entry.
 //   hyst_emit_kernel   every pixel: 255 iff it is a candidate and its root's entry has bit 31, else 0; 16 pixels per thread,
 //                      one 16-byte store where the chunk lies inside the frame.  It may write over its own input.
+//                      Both walk the frame's aligned chunks (mask_common.hpp) and share root_is_marked.
 // Kernel boundaries are the only ordering between workgroups: no flag, no grid barrier, no retry.  The mark and emit
 // kernels have no loop but the 16 bytes of a chunk.
 #include "common.hpp"
-#include "hist_common.hpp"
 #include "kernels.hpp"
+#include "mask_common.hpp"
 #include "tile_common.hpp"
 
 namespace mi355 {
@@ -172,54 +173,40 @@ __global__ __launch_bounds__(kCnThreads) void canny_nms_kernel(const uint8_t* __
 constexpr uint32_t kMarked = 0x80000000u;  // bit 31 of a root's own entry: a label value is at most 2^31 - 1
 constexpr int kHystThreads = 256;
 
-#define HYST_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-// A thread owns the 16 bytes at a 16-byte aligned address of `anchor`'s frame f: chunk c covers the frame's bytes
-// [first, first + 16) with first = 16 c - (the frame's address & 15), cut to [*p0, *p1) inside the frame.  Frames are cut
-// apart, so a chunk that straddles two frames is visited once for each, with disjoint bytes.
-__device__ __forceinline__ bool hyst_chunk(const uint8_t* frame, uint32_t npx, uint32_t c, int64_t* first, int* p0, int* p1)
+// Two loads from candidate a (not 0) to its root: a's entry e is the root's value, or a's own entry if a is the root.  True
+// iff the root has bit 31, else *root is its value.  kAtomic: the mark launch, where roots' own entries gain bit 31 meanwhile.
+template <bool kAtomic>
+__device__ __forceinline__ bool root_is_marked(const uint32_t* lab, uint32_t a, uint32_t* root)
 {
-    const int mis = (int)(reinterpret_cast<uintptr_t>(frame) & 15u);
-    *first = 16 * (int64_t)c - mis;
-    const int64_t last = (int64_t)npx - *first;  // bytes of the frame from `first` on
-    *p0 = *first < 0 ? mis : 0;
-    *p1 = last < 16 ? (int)last : 16;
-    return *p0 < *p1;
+    auto entry = [&](uint32_t v) { return kAtomic ? __hip_atomic_load(lab + (v - 1), MI355_RELAXED_AGENT) : lab[v - 1]; };
+    const uint32_t e = entry(a);
+    *root = e;
+    return (e & kMarked) || (e != a && (entry(e) & kMarked));
 }
 
-__device__ __forceinline__ uint32_t chunk_byte(const u32x4& v, int j) { return (v[j >> 2] >> (8 * (j & 3))) & 0xFFu; }
-
+// A thread owns one aligned chunk (mask_common.hpp) of a frame's npx bytes, in the mark kernel of the input and in the emit
+// kernel of the output.  Frames are cut apart: a chunk that straddles two is visited once for each, with disjoint bytes.
 __global__ __launch_bounds__(kHystThreads) void hyst_mark_kernel(const uint8_t* in, uint32_t* parent, uint32_t npx,
                                                                  uint32_t bpf, uint32_t high)
 {
-    const uint32_t f = blockIdx.x / bpf, c = (blockIdx.x - f * bpf) * kHystThreads + threadIdx.x;
-    const uint8_t* fin = in + (size_t)f * npx;
-    uint32_t* lab = parent + (size_t)f * npx;
-    int64_t first;
-    int p0, p1;
-    if (!hyst_chunk(fin, npx, c, &first, &p0, &p1))
+    const FrameBlock fb = frame_block(bpf, kHystThreads);
+    const uint8_t* fin = in + (size_t)fb.frame * npx;
+    uint32_t* lab = parent + (size_t)fb.frame * npx;
+    const AlignedChunk<int64_t> c = aligned_chunk<int64_t>((int)(reinterpret_cast<uintptr_t>(fin) & 15u), fb.item, npx);
+    if (c.b0 >= c.b1)
         return;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (p1 - p0 == 16) {
-        v = *reinterpret_cast<const u32x4*>(fin + first);
-    } else {
-        for (int j = p0; j < p1; j++)  // bound: fewer than 16 bytes
-            v[j >> 2] |= (uint32_t)fin[first + j] << (8 * (j & 3));
-    }
+    const uint8_t* src = fin + c.first;
+    const u32x4 v = c.whole() ? *reinterpret_cast<const u32x4*>(src) : load_chunk_bytes(src, c.b0, c.b1);
 #pragma unroll
     for (int j = 0; j < 16; j++) {
-        if (j < p0 || j >= p1 || chunk_byte(v, j) <= high)
+        if (j < c.b0 || j >= c.b1 || chunk_byte(v, j) <= high)
             continue;
-        // two loads to the root; entries only ever gain bit 31 in this launch, and only roots' own entries do
-        const uint32_t a = __hip_atomic_load(lab + (first + j), HYST_AGENT) & ~kMarked;
+        const uint32_t a = __hip_atomic_load(lab + (c.first + j), MI355_RELAXED_AGENT) & ~kMarked;
         if (a == 0)
             continue;  // not a candidate (cannot happen while low <= high)
-        const uint32_t e = __hip_atomic_load(lab + (a - 1), HYST_AGENT);
-        if (e & kMarked)
-            continue;  // a is the root and is marked
-        if (e != a && (__hip_atomic_load(lab + (e - 1), HYST_AGENT) & kMarked))
-            continue;  // the root e is marked
-        __hip_atomic_fetch_or(lab + (e - 1), kMarked, HYST_AGENT);
+        uint32_t root;
+        if (!root_is_marked<true>(lab, a, &root))
+            __hip_atomic_fetch_or(lab + (root - 1), kMarked, MI355_RELAXED_AGENT);
     }
 }
 
@@ -227,40 +214,30 @@ __global__ __launch_bounds__(kHystThreads) void hyst_mark_kernel(const uint8_t* 
 __global__ __launch_bounds__(kHystThreads) void hyst_emit_kernel(const uint8_t* in, uint8_t* out, const uint32_t* parent,
                                                                  uint32_t npx, uint32_t bpf, uint32_t low)
 {
-    const uint32_t f = blockIdx.x / bpf, c = (blockIdx.x - f * bpf) * kHystThreads + threadIdx.x;
-    const uint8_t* fin = in + (size_t)f * npx;
-    uint8_t* fout = out + (size_t)f * npx;
-    const uint32_t* lab = parent + (size_t)f * npx;
-    int64_t first;
-    int p0, p1;
-    if (!hyst_chunk(fout, npx, c, &first, &p0, &p1))
+    const FrameBlock fb = frame_block(bpf, kHystThreads);
+    const uint8_t* fin = in + (size_t)fb.frame * npx;
+    uint8_t* fout = out + (size_t)fb.frame * npx;
+    const uint32_t* lab = parent + (size_t)fb.frame * npx;
+    const AlignedChunk<int64_t> c = aligned_chunk<int64_t>((int)(reinterpret_cast<uintptr_t>(fout) & 15u), fb.item, npx);
+    if (c.b0 >= c.b1)
         return;
-    const bool whole = p1 - p0 == 16;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (whole) {
-        v = *reinterpret_cast<const u32x4_a1*>(fin + first);
-    } else {
-        for (int j = p0; j < p1; j++)  // bound: fewer than 16 bytes
-            v[j >> 2] |= (uint32_t)fin[first + j] << (8 * (j & 3));
-    }
+    const uint8_t* src = fin + c.first;
+    const u32x4 v = c.whole() ? *reinterpret_cast<const u32x4_a1*>(src) : load_chunk_bytes(src, c.b0, c.b1);
     u32x4 o = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int j = 0; j < 16; j++) {
-        if (j < p0 || j >= p1 || chunk_byte(v, j) <= low)
+        if (j < c.b0 || j >= c.b1 || chunk_byte(v, j) <= low)
             continue;
-        const uint32_t a = lab[first + j] & ~kMarked;
+        const uint32_t a = lab[c.first + j] & ~kMarked;
         if (a == 0)
             continue;  // not foreground for the union (cannot happen: it ran on these bytes with this `low`)
-        const uint32_t e = lab[a - 1];  // the root's value, or with a the root itself its own entry
-        const bool kept = (e & kMarked) || (e != a && (lab[e - 1] & kMarked));
-        o[j >> 2] |= (kept ? 0xFFu : 0u) << (8 * (j & 3));
+        uint32_t root;
+        o[j >> 2] |= (root_is_marked<false>(lab, a, &root) ? 0xFFu : 0u) << (8 * (j & 3));
     }
-    if (whole) {
-        *reinterpret_cast<u32x4*>(fout + first) = o;
-    } else {
-        for (int j = p0; j < p1; j++)  // bound: fewer than 16 bytes
-            fout[first + j] = (uint8_t)chunk_byte(o, j);
-    }
+    if (c.whole())
+        *reinterpret_cast<u32x4*>(fout + c.first) = o;
+    else
+        store_chunk_bytes(fout + c.first, o, c.b0, c.b1);
 }
 
 }  // namespace
@@ -284,20 +261,18 @@ hipError_t launch_hysteresis(hipStream_t stream, const uint8_t* d_in, uint8_t* d
     if (!hist_frames_ok(w, h, nframes) || low < 0 || high < low || high > 255)
         return hipErrorInvalidValue;
     const uint32_t npx = (uint32_t)w * (uint32_t)h;
-    const uint32_t chunks = (npx + 15u) / 16u + 1u;  // 16-byte aligned chunks that npx bytes at any alignment can touch
-    const uint32_t bpf = (chunks + kHystThreads - 1) / kHystThreads;
-    const uint64_t blocks = (uint64_t)nframes * bpf;
-    if (!grid_fits(blocks))
+    const FrameGrid g = frame_grid(aligned_chunks_of(npx), kHystThreads, nframes);  // a thread per aligned chunk
+    if (!g.ok)
         return hipErrorInvalidValue;
     const hipError_t e = launch_ccl_unite(stream, d_in, d_parent, w, h, nframes, conn8, low);
     if (e != hipSuccess)
         return e;
     uint32_t* parent = reinterpret_cast<uint32_t*>(d_parent);
     if (high < 255)  // nothing exceeds 255: no pixel is strong, no root is marked
-        hipLaunchKernelGGL(hyst_mark_kernel, dim3((uint32_t)blocks), dim3(kHystThreads), 0, stream, d_in, parent, npx, bpf,
+        hipLaunchKernelGGL(hyst_mark_kernel, dim3(g.blocks), dim3(kHystThreads), 0, stream, d_in, parent, npx, g.bpf,
                            (uint32_t)high);
-    hipLaunchKernelGGL(hyst_emit_kernel, dim3((uint32_t)blocks), dim3(kHystThreads), 0, stream, d_in, d_out, parent, npx,
-                       bpf, (uint32_t)low);
+    hipLaunchKernelGGL(hyst_emit_kernel, dim3(g.blocks), dim3(kHystThreads), 0, stream, d_in, d_out, parent, npx, g.bpf,
+                       (uint32_t)low);
     return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 // count (then offset) per kCclFlatPx pixels.  A pixel's entry holds a LABEL VALUE v = (index of another pixel of the
 // same frame and component) + 1, never larger than the pixel's own index + 1; a root holds its own index + 1;
 // background holds 0.  Kernel boundaries are the only ordering between workgroups: no flag, no grid barrier, no ticket.
+// Grids, chunk walk and prefix sums: mask_common.hpp.  Union-find and neighbour rule: once, below.
 //   ccl_local_kernel     a block owns a 64 x 32 tile: row masks in LDS from 16-byte aligned vectors of the source (a
 //                        row is at any alignment: chunks the row does not cover whole go byte by byte), every pixel
 //                        starts at the first pixel of its row run (bit operations on the 64-bit row mask), runs of
@@ -26,8 +27,8 @@
 // The first three take a wave-uniform `low`: a pixel is foreground iff its byte > low.  The labelling call passes 0
 // ("not zero"); the hysteresis of canny.hip runs just these three (launch_ccl_unite) with its lower threshold.
 #include "common.hpp"
-#include "hist_common.hpp"
 #include "kernels.hpp"
+#include "mask_common.hpp"
 
 namespace mi355 {
 
@@ -38,13 +39,10 @@ constexpr int kTileH = 32;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kRowsPerWave = kTileH / kWaves;
-constexpr int kRowChunks = kTileW / 16 + 1;  // 16-byte aligned chunks that 64 bytes at any alignment can touch
+constexpr int kRowChunks = aligned_chunks_of(kTileW);  // of a tile row, at any alignment
 constexpr int kFlatIters = kCclFlatPx / kThreads;  // a wave owns kFlatIters x 64 consecutive pixels of a flat block
 constexpr int kSlots = 64;                         // of a block's LDS statistics table
 static_assert(kTileW == kWave && kTileH * kRowChunks <= kThreads && kCclFlatPx % kThreads == 0, "tile geometry");
-
-#define CCL_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
-#define CCL_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 struct CclGeom {
     uint32_t w, h, npx;  // npx = w h < 2^31
@@ -54,36 +52,59 @@ struct CclGeom {
     uint32_t nflat;      // flat blocks per frame
 };
 
-// ---- the tile in LDS ----------------------------------------------------------------------------------------------------
-// bound: the walk goes to strictly smaller indices, fewer than kTileW kTileH steps
-__device__ __forceinline__ uint32_t lds_find(uint32_t* lab, uint32_t a)
+// ---- lock-free union-find by fetch_min -------------------------------------------------------------------------------------
+// Element v = index + kBias; its entry lab[v - kBias] holds a member of its set that is not larger, a root itself.  Twice:
+// a tile in LDS (kWg, bias 0) and a frame's parent array while other workgroups write it (kAgent, bias 1: 0 is background).
+// bound of find: the walk goes to strictly smaller values, fewer steps than elements (kTileW kTileH, w h).  A value read
+// late or early is still an ancestor: an entry only ever decreases, and only to an ancestor of what it held.
+// bound of union: max(a, b) strictly decreases with every trip, fewer trips than elements; no CAS, nothing is retried.
+constexpr int kWg = __HIP_MEMORY_SCOPE_WORKGROUP, kAgent = __HIP_MEMORY_SCOPE_AGENT;
+template <int kScope, int kBias, class T>
+__device__ __forceinline__ T uf_find(T* lab, T v)
 {
     for (;;) {
-        const uint32_t p = __hip_atomic_load(lab + a, CCL_WG);
-        if (p == a)
-            return a;
-        a = p;
+        const T nx = __hip_atomic_load(lab + (v - kBias), __ATOMIC_RELAXED, kScope);
+        if (nx == v)
+            return v;
+        v = nx;
     }
 }
 
-// bound: max(a, b) strictly decreases with every trip, fewer than kTileW kTileH trips
-__device__ __forceinline__ void lds_union(uint32_t* lab, uint32_t a, uint32_t b)
+template <int kScope, int kBias, class T>
+__device__ __forceinline__ void uf_union(T* lab, T a, T b)
 {
-    a = lds_find(lab, a);
-    b = lds_find(lab, b);
+    a = uf_find<kScope, kBias>(lab, a);
+    b = uf_find<kScope, kBias>(lab, b);
     while (a != b) {
         if (a < b) {
-            const uint32_t t = a;
+            const T t = a;
             a = b;
             b = t;
         }
-        const uint32_t old = __hip_atomic_fetch_min(lab + a, b, CCL_WG);
+        const T old = __hip_atomic_fetch_min(lab + (a - kBias), b, __ATOMIC_RELAXED, kScope);
         if (old == a)
             break;
         a = old;
     }
 }
 
+// A foreground pixel and `up`, the pixel above it; c_l / c_r its own left and right neighbours, u_l / u_r those of `up`.
+// unite(d): with the pixel d columns from `up`.  A pair of runs is united once: the left neighbours do it if both are set.
+template <class F>
+__device__ __forceinline__ void unite_with_row_above(bool up, bool c_l, bool c_r, bool u_l, bool u_r, int conn8, F unite)
+{
+    if (up) {
+        if (!(c_l && u_l))
+            unite(0);
+    } else if (conn8) {  // the pixel above is background: the two diagonal neighbours are in runs of their own
+        if (u_l && !c_l)
+            unite(-1);
+        if (u_r && !c_r)
+            unite(1);
+    }
+}
+
+// ---- the tile in LDS ----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t row_mask(const uint32_t* smask, int r)
 {
     return (uint64_t)smask[2 * r] | ((uint64_t)smask[2 * r + 1] << 32);
@@ -95,8 +116,7 @@ __global__ __launch_bounds__(kThreads) void ccl_local_kernel(const uint8_t* __re
     __shared__ uint32_t smask[kTileH * 2];
     __shared__ uint32_t lab[kTileH * kTileW];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-    const uint32_t tiles = g.ntx * g.nty;
-    const uint32_t f = blockIdx.x / tiles, t = blockIdx.x - f * tiles;
+    const auto [f, t, item] = frame_block(g.ntx * g.nty, 1);
     const uint32_t tj = t / g.ntx, ti = t - tj * g.ntx;
     const uint32_t x0 = ti * kTileW, y0 = tj * kTileH;
     const int n = (int)(g.w - x0 < (uint32_t)kTileW ? g.w - x0 : (uint32_t)kTileW);     // columns of the frame
@@ -111,26 +131,24 @@ __global__ __launch_bounds__(kThreads) void ccl_local_kernel(const uint8_t* __re
         if (r < rows) {
             const uint8_t* row = p + (size_t)(y0 + (uint32_t)r) * g.w + x0;
             const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15u);
-            const int c0 = 16 * s - mis;  // the chunk is bytes c0 .. c0 + 15 of the row's n bytes
-            const int b0 = c0 > 0 ? c0 : 0, b1 = c0 + 16 < n ? c0 + 16 : n;
-            uint32_t bits = 0;  // bit i: byte b0 + i is foreground (> low)
-            if (b1 - b0 == 16) {
-                const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + c0));
+            const AlignedChunk<int> c = aligned_chunk<int>(mis, s, n);  // of the row's n bytes
+            const uint8_t* chunk = row + c.first;
+            uint32_t bits = 0;  // bit i: byte b0 + i of the chunk is foreground (> low)
+            if (c.whole()) {
+                const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(chunk));
 #pragma unroll
-                for (int d = 0; d < 4; d++)
-#pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        bits |= (((v[d] >> (8 * e)) & 0xFFu) > low ? 1u : 0u) << (4 * d + e);
+                for (int j = 0; j < 16; j++)
+                    bits |= (chunk_byte(v, j) > low ? 1u : 0u) << j;
             } else {
-                for (int b = b0; b < b1; b++)  // bound: fewer than 16 bytes
-                    bits |= (row[b] > low ? 1u : 0u) << (b - b0);
+                for (int j = c.b0; j < c.b1; j++)  // bound: fewer than 16 bytes
+                    bits |= (chunk[j] > low ? 1u : 0u) << (j - c.b0);
             }
             if (bits) {
-                const uint64_t m = (uint64_t)bits << b0;
+                const uint64_t m = (uint64_t)bits << (c.first + c.b0);
                 if ((uint32_t)m)
-                    __hip_atomic_fetch_or(smask + 2 * r, (uint32_t)m, CCL_WG);
+                    __hip_atomic_fetch_or(smask + 2 * r, (uint32_t)m, MI355_RELAXED_WG);
                 if ((uint32_t)(m >> 32))
-                    __hip_atomic_fetch_or(smask + 2 * r + 1, (uint32_t)(m >> 32), CCL_WG);
+                    __hip_atomic_fetch_or(smask + 2 * r + 1, (uint32_t)(m >> 32), MI355_RELAXED_WG);
             }
         }
     }
@@ -157,16 +175,8 @@ __global__ __launch_bounds__(kThreads) void ccl_local_kernel(const uint8_t* __re
         const bool c_l = lane > 0 && ((cur >> (lane - 1)) & 1u), c_r = lane < 63 && ((cur >> (lane + 1)) & 1u);
         const bool u_l = lane > 0 && ((up >> (lane - 1)) & 1u), u_r = lane < 63 && ((up >> (lane + 1)) & 1u);
         const uint32_t me = (uint32_t)(r * kTileW + lane), above = me - kTileW;
-        if ((up >> lane) & 1u) {
-            if (!(c_l && u_l))
-                lds_union(lab, me, above);
-        } else if (conn8) {
-            // the pixel above is background: the two diagonal neighbours are in runs of their own
-            if (u_l && !c_l)
-                lds_union(lab, me, above - 1);
-            if (u_r && !c_r)
-                lds_union(lab, me, above + 1);
-        }
+        unite_with_row_above((up >> lane) & 1u, c_l, c_r, u_l, u_r, conn8,
+                             [&](int d) { uf_union<kWg, 0>(lab, me, above + (uint32_t)d); });
     }
     __syncthreads();
     int32_t* out = labels + (size_t)f * g.npx;
@@ -177,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void ccl_local_kernel(const uint8_t* __re
             continue;
         int32_t v = 0;
         if ((row_mask(smask, r) >> lane) & 1u) {
-            const uint32_t root = lds_find(lab, (uint32_t)(r * kTileW + lane));
+            const uint32_t root = uf_find<kWg, 0>(lab, (uint32_t)(r * kTileW + lane));
             v = (int32_t)((y0 + root / kTileW) * g.w + x0 + (root & (kTileW - 1)) + 1u);
         }
         out[(size_t)(y0 + (uint32_t)r) * g.w + x0 + (uint32_t)lane] = v;
@@ -185,62 +195,29 @@ __global__ __launch_bounds__(kThreads) void ccl_local_kernel(const uint8_t* __re
 }
 
 // ---- the parent array in global memory while other workgroups write it ----------------------------------------------------
-// bound: the walk goes to strictly smaller values, fewer than w h steps.  A value read late or early is still an
-// ancestor: an entry only ever decreases, and only to an ancestor of what it held
-__device__ __forceinline__ int32_t agent_find(int32_t* lab, int32_t v)
-{
-    for (;;) {
-        const int32_t nx = __hip_atomic_load(lab + (v - 1), CCL_AGENT);
-        if (nx == v)
-            return v;
-        v = nx;
-    }
-}
-
-// bound: max(a, b) strictly decreases with every trip, fewer than w h trips; no compare-and-swap, nothing is retried
-__device__ __forceinline__ void agent_union(int32_t* lab, int32_t a, int32_t b)
-{
-    a = agent_find(lab, a);
-    b = agent_find(lab, b);
-    while (a != b) {
-        if (a < b) {
-            const int32_t t = a;
-            a = b;
-            b = t;
-        }
-        const int32_t old = __hip_atomic_fetch_min(lab + (a - 1), b, CCL_AGENT);
-        if (old == a)
-            break;
-        a = old;
-    }
-}
-
 // The seam pixel of item i of a frame: (x, y) in the top row of a tile (horizontal = true, y > 0) or in the left column
 // of a tile (x > 0).  A tile's corner pixel appears once as each.
-__device__ __forceinline__ void seam_pixel(const CclGeom& g, uint32_t i, bool* horizontal, uint32_t* x, uint32_t* y)
+struct SeamPixel {
+    bool horizontal;
+    uint32_t x, y;
+};
+__device__ __forceinline__ SeamPixel seam_pixel(const CclGeom& g, uint32_t i)
 {
     if (i < g.seam_h) {
         const uint32_t k = i / g.w;
-        *horizontal = true;
-        *x = i - k * g.w;
-        *y = (k + 1) * kTileH;
-    } else {
-        const uint32_t j = i - g.seam_h, k = j / g.h;
-        *horizontal = false;
-        *x = (k + 1) * kTileW;
-        *y = j - k * g.h;
+        return {true, i - k * g.w, (k + 1) * kTileH};
     }
+    const uint32_t j = i - g.seam_h, k = j / g.h;
+    return {false, (k + 1) * kTileW, j - k * g.h};
 }
 
 __global__ __launch_bounds__(kThreads) void ccl_seam_kernel(const uint8_t* __restrict__ in, int32_t* labels, CclGeom g,
                                                             uint32_t bpf, int conn8, uint32_t low)
 {
-    const uint32_t f = blockIdx.x / bpf, i = (blockIdx.x - f * bpf) * kThreads + threadIdx.x;
+    const auto [f, blk, i] = frame_block(bpf, kThreads);
     if (i >= g.seam)
         return;
-    bool hor;
-    uint32_t x, y;
-    seam_pixel(g, i, &hor, &x, &y);
+    const auto [hor, x, y] = seam_pixel(g, i);
     const uint8_t* p = in + (size_t)f * g.npx;
     int32_t* lab = labels + (size_t)f * g.npx;
     const uint32_t w = g.w, at = y * w + x;
@@ -252,27 +229,20 @@ __global__ __launch_bounds__(kThreads) void ccl_seam_kernel(const uint8_t* __res
         // the row above belongs to another tile: the local kernel's rule, on the frame's rows
         const bool c_l = x > 0 && fg(at - 1), c_r = x + 1 < w && fg(at + 1);
         const bool u_l = x > 0 && fg(at - w - 1), u_r = x + 1 < w && fg(at - w + 1);
-        if (fg(at - w)) {
-            if (!(c_l && u_l))
-                agent_union(lab, me, me - (int32_t)w);
-        } else if (conn8) {
-            if (u_l && !c_l)
-                agent_union(lab, me, me - (int32_t)w - 1);
-            if (u_r && !c_r)
-                agent_union(lab, me, me - (int32_t)w + 1);
-        }
+        unite_with_row_above(fg(at - w), c_l, c_r, u_l, u_r, conn8,
+                             [&](int d) { uf_union<kAgent, 1>(lab, me, me - (int32_t)w + d); });
     } else {
         // the column on the left belongs to another tile; the pair one row up does it when both its pixels are set and
         // the local kernel has united this pixel with the one above it (a tile's top row is united with the row above
         // by the branch above, which may itself count on this union: no skipping there)
         if (fg(at - 1)) {
             if (!(y % kTileH != 0 && fg(at - w) && fg(at - w - 1)))
-                agent_union(lab, me, me - 1);
+                uf_union<kAgent, 1>(lab, me, me - 1);
         } else if (conn8) {
             if (y > 0 && fg(at - w - 1) && !fg(at - w))
-                agent_union(lab, me, me - (int32_t)w - 1);
+                uf_union<kAgent, 1>(lab, me, me - (int32_t)w - 1);
             if (y + 1 < g.h && fg(at + w - 1) && !fg(at + w))
-                agent_union(lab, me, me + (int32_t)w - 1);
+                uf_union<kAgent, 1>(lab, me, me + (int32_t)w - 1);
         }
     }
 }
@@ -281,23 +251,21 @@ __global__ __launch_bounds__(kThreads) void ccl_seam_kernel(const uint8_t* __res
 // writes the one final value of its entry; concurrent readers see the old ancestor or the root
 __device__ __forceinline__ void compress_pixel(int32_t* lab, uint32_t q)
 {
-    const int32_t a = __hip_atomic_load(lab + q, CCL_AGENT);
-    const int32_t r = agent_find(lab, a);
+    const int32_t a = __hip_atomic_load(lab + q, MI355_RELAXED_AGENT);
+    const int32_t r = uf_find<kAgent, 1>(lab, a);
     if (a != r)
-        __hip_atomic_store(lab + (a - 1), r, CCL_AGENT);
+        __hip_atomic_store(lab + (a - 1), r, MI355_RELAXED_AGENT);
     if (a != r)
-        __hip_atomic_store(lab + q, r, CCL_AGENT);
+        __hip_atomic_store(lab + q, r, MI355_RELAXED_AGENT);
 }
 
 __global__ __launch_bounds__(kThreads) void ccl_compress_kernel(const uint8_t* __restrict__ in, int32_t* labels,
                                                                 CclGeom g, uint32_t bpf, uint32_t low)
 {
-    const uint32_t f = blockIdx.x / bpf, i = (blockIdx.x - f * bpf) * kThreads + threadIdx.x;
+    const auto [f, blk, i] = frame_block(bpf, kThreads);
     if (i >= g.seam)
         return;
-    bool hor;
-    uint32_t x, y;
-    seam_pixel(g, i, &hor, &x, &y);
+    const auto [hor, x, y] = seam_pixel(g, i);
     const uint8_t* p = in + (size_t)f * g.npx;
     int32_t* lab = labels + (size_t)f * g.npx;
     const uint32_t at = y * g.w + x, opposite = hor ? at - g.w : at - 1;
@@ -313,16 +281,11 @@ __device__ __forceinline__ uint32_t flat_pixel(uint32_t b, int wv, int i, int la
     return b * kCclFlatPx + (uint32_t)((wv * kFlatIters + i) * kWave + lane);
 }
 
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m, int lane)
-{
-    return (uint32_t)__popcll(m & ((1ull << lane) - 1));
-}
-
 __global__ __launch_bounds__(kThreads) void ccl_flatten_kernel(int32_t* labels, uint32_t* __restrict__ counts, CclGeom g)
 {
     __shared__ uint32_t s_cnt[kWaves];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-    const uint32_t f = blockIdx.x / g.nflat, b = blockIdx.x - f * g.nflat;
+    const auto [f, b, item] = frame_block(g.nflat, kCclFlatPx);
     int32_t* lab = labels + (size_t)f * g.npx;
     int rank[kFlatIters];  // of the roots among the wave's roots, -1: not a root
     uint32_t cnt = 0;
@@ -335,32 +298,25 @@ __global__ __launch_bounds__(kThreads) void ccl_flatten_kernel(int32_t* labels, 
             // itself, or already its rank (negative) if it is a root of this launch
             const int32_t a = lab[px];
             if (a > 0) {
-                const int32_t v = __hip_atomic_load(lab + (a - 1), CCL_WG);
+                const int32_t v = __hip_atomic_load(lab + (a - 1), MI355_RELAXED_WG);
                 const int32_t root = v < 0 ? a : v;
                 is_root = root == (int32_t)px + 1;
                 if (!is_root && root != a)
-                    __hip_atomic_store(lab + px, root, CCL_WG);
+                    __hip_atomic_store(lab + px, root, MI355_RELAXED_WG);
             }
         }
         const uint64_t m = __ballot(is_root);
         rank[i] = is_root ? (int)(cnt + lanes_below(m, lane)) : -1;
         cnt += (uint32_t)__popcll(m);
     }
-    if (lane == 0)
-        s_cnt[wv] = cnt;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; k++) {
-        before += k < wv ? s_cnt[k] : 0;
-        total += s_cnt[k];
-    }
+    const BlockOffsets o = block_offsets<kWaves>(cnt, s_cnt, lane, wv);  // cnt is the same in every lane
 #pragma unroll
     for (int i = 0; i < kFlatIters; i++)
         if (rank[i] >= 0)
-            __hip_atomic_store(lab + flat_pixel(b, wv, i, lane), -(int32_t)(before + (uint32_t)rank[i] + 1u), CCL_WG);
+            __hip_atomic_store(lab + flat_pixel(b, wv, i, lane), -(int32_t)(o.before + (uint32_t)rank[i] + 1u),
+                               MI355_RELAXED_WG);
     if (tid == 0)
-        counts[(size_t)f * g.nflat + b] = total;
+        counts[(size_t)f * g.nflat + b] = o.total;
 }
 
 // one block per frame: the frame's block counts become exclusive offsets in place; N = the roots + 1 (the background)
@@ -374,26 +330,12 @@ __global__ __launch_bounds__(kThreads) void ccl_scan_kernel(uint32_t* __restrict
     for (uint32_t k0 = 0; k0 < nflat; k0 += kThreads) {  // bound: nflat / 256 trips, rounded up
         const uint32_t k = k0 + tid;
         const uint32_t own = k < nflat ? c[k] : 0;
-        uint32_t inc = own;
-#pragma unroll
-        for (int d = 1; d < kWave; d *= 2) {
-            const uint32_t o = __shfl_up(inc, d);
-            if (lane >= d)
-                inc += o;
-        }
-        if (lane == kWave - 1)
-            s_sum[wv] = inc;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int j = 0; j < kWaves; j++) {
-            before += j < wv ? s_sum[j] : 0;
-            total += s_sum[j];
-        }
+        const uint32_t inc = wave_scan_inclusive(own, lane);
+        const BlockOffsets o = block_offsets<kWaves>(inc, s_sum, lane, wv);
         if (k < nflat)
-            c[k] = carry + before + inc - own;
-        carry += total;
-        __syncthreads();
+            c[k] = carry + o.before + inc - own;
+        carry += o.total;
+        __syncthreads();  // s_sum is written again in the next trip
     }
     if (tid == 0)
         count[blockIdx.x] = (int32_t)(carry + 1u);
@@ -410,13 +352,13 @@ struct RunStats {
 __device__ __forceinline__ void stats_to_global(int32_t* st, unsigned long long* sm, int minx, int miny, int maxx,
                                                 int maxy, uint32_t area, uint64_t sx, uint64_t sy)
 {
-    __hip_atomic_fetch_min(st + 0, minx, CCL_AGENT);
-    __hip_atomic_fetch_min(st + 1, miny, CCL_AGENT);
-    __hip_atomic_fetch_max(st + 2, maxx, CCL_AGENT);
-    __hip_atomic_fetch_max(st + 3, maxy, CCL_AGENT);
-    __hip_atomic_fetch_add(st + 4, (int32_t)area, CCL_AGENT);
-    __hip_atomic_fetch_add(sm + 0, (unsigned long long)sx, CCL_AGENT);
-    __hip_atomic_fetch_add(sm + 1, (unsigned long long)sy, CCL_AGENT);
+    __hip_atomic_fetch_min(st + 0, minx, MI355_RELAXED_AGENT);
+    __hip_atomic_fetch_min(st + 1, miny, MI355_RELAXED_AGENT);
+    __hip_atomic_fetch_max(st + 2, maxx, MI355_RELAXED_AGENT);
+    __hip_atomic_fetch_max(st + 3, maxy, MI355_RELAXED_AGENT);
+    __hip_atomic_fetch_add(st + 4, (int32_t)area, MI355_RELAXED_AGENT);
+    __hip_atomic_fetch_add(sm + 0, (unsigned long long)sx, MI355_RELAXED_AGENT);
+    __hip_atomic_fetch_add(sm + 1, (unsigned long long)sy, MI355_RELAXED_AGENT);
 }
 
 struct BlockStats {
@@ -433,7 +375,7 @@ __global__ __launch_bounds__(kThreads) void ccl_relabel_kernel(int32_t* labels, 
 {
     __shared__ BlockStats bs;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-    const uint32_t f = blockIdx.x / g.nflat, b = blockIdx.x - f * g.nflat;
+    const auto [f, b, item] = frame_block(g.nflat, kCclFlatPx);
     int32_t* lab = labels + (size_t)f * g.npx;
     const uint32_t* offs = offsets + (size_t)f * g.nflat;
     int32_t* st = kStats ? stats + (size_t)f * stats_rows * 5 : nullptr;
@@ -461,11 +403,11 @@ __global__ __launch_bounds__(kThreads) void ccl_relabel_kernel(int32_t* labels, 
             if (a < 0) {
                 fin = (int32_t)own_off - a;
             } else if (a > 0) {
-                const int32_t v = __hip_atomic_load(lab + (a - 1), CCL_WG);
+                const int32_t v = __hip_atomic_load(lab + (a - 1), MI355_RELAXED_WG);
                 fin = v < 0 ? (int32_t)offs[(uint32_t)(a - 1) / kCclFlatPx] - v : v;
             }
             if (a != 0)
-                __hip_atomic_store(lab + px, fin, CCL_WG);
+                __hip_atomic_store(lab + px, fin, MI355_RELAXED_WG);
         }
         if (!kStats)
             continue;
@@ -487,13 +429,13 @@ __global__ __launch_bounds__(kThreads) void ccl_relabel_kernel(int32_t* labels, 
                                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ||
                           expected == fin;
         if (mine) {
-            __hip_atomic_fetch_min(&bs.minx[s], (int32_t)x, CCL_WG);
-            __hip_atomic_fetch_min(&bs.miny[s], (int32_t)y, CCL_WG);
-            __hip_atomic_fetch_max(&bs.maxx[s], x1, CCL_WG);
-            __hip_atomic_fetch_max(&bs.maxy[s], (int32_t)y, CCL_WG);
-            __hip_atomic_fetch_add(&bs.area[s], n, CCL_WG);
-            __hip_atomic_fetch_add(&bs.sx[s], (unsigned long long)sx, CCL_WG);
-            __hip_atomic_fetch_add(&bs.sy[s], (unsigned long long)sy, CCL_WG);
+            __hip_atomic_fetch_min(&bs.minx[s], (int32_t)x, MI355_RELAXED_WG);
+            __hip_atomic_fetch_min(&bs.miny[s], (int32_t)y, MI355_RELAXED_WG);
+            __hip_atomic_fetch_max(&bs.maxx[s], x1, MI355_RELAXED_WG);
+            __hip_atomic_fetch_max(&bs.maxy[s], (int32_t)y, MI355_RELAXED_WG);
+            __hip_atomic_fetch_add(&bs.area[s], n, MI355_RELAXED_WG);
+            __hip_atomic_fetch_add(&bs.sx[s], (unsigned long long)sx, MI355_RELAXED_WG);
+            __hip_atomic_fetch_add(&bs.sy[s], (unsigned long long)sy, MI355_RELAXED_WG);
         } else {
             // the slot holds another label of this block
             stats_to_global(st + (size_t)fin * 5, sm + (size_t)fin * 2, (int)x, (int)y, x1, (int)y, n, sx, sy);
@@ -550,22 +492,23 @@ bool ccl_geom(int w, int h, int nframes, CclGeom* g)
 
 // The union launches: local, and where the frame has more than one tile, seam and compress.  Afterwards a foreground
 // pixel q reaches its root in two loads: labels[q] is a tile root's value (or already the root's), and a tile root's
-// entry holds its root's value
+// entry holds its root's value.  Their grids: a block per tile, a thread per seam pixel
+FrameGrid tile_grid(const CclGeom& g, int nframes) { return frame_grid((uint64_t)g.ntx * g.nty, 1, nframes); }
+FrameGrid seam_grid(const CclGeom& g, int nframes) { return frame_grid(g.seam, kThreads, nframes); }
+
 hipError_t enqueue_unite(hipStream_t stream, const uint8_t* d_in, int32_t* d_labels, const CclGeom& g, int nframes,
                          bool conn8, uint32_t low)
 {
-    const uint64_t tiles = (uint64_t)nframes * g.ntx * g.nty;
-    const uint32_t seam_bpf = (g.seam + kThreads - 1) / kThreads;
-    const uint64_t seam_blocks = (uint64_t)nframes * seam_bpf;
-    if (!grid_fits(tiles) || !grid_fits(seam_blocks))
+    const FrameGrid tiles = tile_grid(g, nframes), seam = seam_grid(g, nframes);
+    if (!tiles.ok || !seam.ok)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ccl_local_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, stream, d_in, d_labels, g,
-                       conn8 ? 1 : 0, low);
+    hipLaunchKernelGGL(ccl_local_kernel, dim3(tiles.blocks), dim3(kThreads), 0, stream, d_in, d_labels, g, conn8 ? 1 : 0,
+                       low);
     if (g.seam) {
-        hipLaunchKernelGGL(ccl_seam_kernel, dim3((uint32_t)seam_blocks), dim3(kThreads), 0, stream, d_in, d_labels, g,
-                           seam_bpf, conn8 ? 1 : 0, low);
-        hipLaunchKernelGGL(ccl_compress_kernel, dim3((uint32_t)seam_blocks), dim3(kThreads), 0, stream, d_in, d_labels, g,
-                           seam_bpf, low);
+        hipLaunchKernelGGL(ccl_seam_kernel, dim3(seam.blocks), dim3(kThreads), 0, stream, d_in, d_labels, g, seam.bpf,
+                           conn8 ? 1 : 0, low);
+        hipLaunchKernelGGL(ccl_compress_kernel, dim3(seam.blocks), dim3(kThreads), 0, stream, d_in, d_labels, g, seam.bpf,
+                           low);
     }
     return hipGetLastError();
 }
@@ -593,28 +536,26 @@ hipError_t launch_ccl(hipStream_t stream, const uint8_t* d_in, int32_t* d_labels
     CclGeom g;
     if (!ccl_geom(w, h, nframes, &g) || stats_rows < 0 || stats_rows > kCclMaxStatsRows)
         return hipErrorInvalidValue;
-    const uint64_t tiles = (uint64_t)nframes * g.ntx * g.nty;
-    const uint64_t seam_blocks = (uint64_t)nframes * ((g.seam + kThreads - 1) / kThreads);
-    const uint64_t flat_blocks = (uint64_t)nframes * g.nflat;
-    const uint64_t rows = (uint64_t)nframes * (uint64_t)stats_rows, row_blocks = (rows + kThreads - 1) / kThreads;
-    if (!grid_fits(tiles) || !grid_fits(seam_blocks) || !grid_fits(flat_blocks) || !grid_fits(row_blocks))
+    const FrameGrid flat = frame_grid(g.npx, kCclFlatPx, nframes);  // flat.bpf is g.nflat
+    const uint64_t rows = (uint64_t)nframes * (uint64_t)stats_rows;
+    const FrameGrid rowg = frame_grid(rows, kThreads, 1);
+    if (!tile_grid(g, nframes).ok || !seam_grid(g, nframes).ok || !flat.ok || !rowg.ok)
         return hipErrorInvalidValue;  // before the first launch
     unsigned long long* sums = reinterpret_cast<unsigned long long*>(d_sums);
     if (rows)
-        hipLaunchKernelGGL(ccl_stats_init_kernel, dim3((uint32_t)row_blocks), dim3(kThreads), 0, stream, d_stats, sums,
-                           rows);
+        hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(rowg.blocks), dim3(kThreads), 0, stream, d_stats, sums, rows);
     const hipError_t ue = enqueue_unite(stream, d_in, d_labels, g, nframes, conn8, 0u);  // foreground: not zero
     if (ue != hipSuccess)
         return ue;
-    hipLaunchKernelGGL(ccl_flatten_kernel, dim3((uint32_t)flat_blocks), dim3(kThreads), 0, stream, d_labels, d_scratch, g);
+    hipLaunchKernelGGL(ccl_flatten_kernel, dim3(flat.blocks), dim3(kThreads), 0, stream, d_labels, d_scratch, g);
     hipLaunchKernelGGL(ccl_scan_kernel, dim3((uint32_t)nframes), dim3(kThreads), 0, stream, d_scratch, d_count, g.nflat);
     if (rows) {
-        hipLaunchKernelGGL(ccl_relabel_kernel<true>, dim3((uint32_t)flat_blocks), dim3(kThreads), 0, stream, d_labels,
-                           d_scratch, d_stats, sums, g, (uint32_t)stats_rows);
-        hipLaunchKernelGGL(ccl_stats_finish_kernel, dim3((uint32_t)row_blocks), dim3(kThreads), 0, stream, d_stats, rows);
+        hipLaunchKernelGGL(ccl_relabel_kernel<true>, dim3(flat.blocks), dim3(kThreads), 0, stream, d_labels, d_scratch,
+                           d_stats, sums, g, (uint32_t)stats_rows);
+        hipLaunchKernelGGL(ccl_stats_finish_kernel, dim3(rowg.blocks), dim3(kThreads), 0, stream, d_stats, rows);
     } else {
-        hipLaunchKernelGGL(ccl_relabel_kernel<false>, dim3((uint32_t)flat_blocks), dim3(kThreads), 0, stream, d_labels,
-                           d_scratch, (int32_t*)nullptr, (unsigned long long*)nullptr, g, 0u);
+        hipLaunchKernelGGL(ccl_relabel_kernel<false>, dim3(flat.blocks), dim3(kThreads), 0, stream, d_labels, d_scratch,
+                           (int32_t*)nullptr, (unsigned long long*)nullptr, g, 0u);
     }
     return hipGetLastError();
 }

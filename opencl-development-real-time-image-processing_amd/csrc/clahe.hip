@@ -5,9 +5,9 @@
 // (BORDER_REFLECT_101); the extended frame never exists in memory.  The three launches, the block histogram frame, the
 // byte-range walk and the table scan are hist_common.hpp's (DESIGN.md sections 6d and 6d.1):
 //   clahe_hist_kernel   a block owns a band of rows of one (frame, tile).  A tile row is tw bytes of the source at
-//                       whatever alignment it has: a thread takes one 16-byte aligned chunk of one row, as a vector if
-//                       the row covers all of it and byte by byte otherwise, or the row's reflected columns (at most
-//                       tiles_x: a run of the same source row, read backwards).  Reflected rows are source rows;
+//                       whatever alignment it has: a thread takes one aligned chunk of one row (mask_common.hpp), as a
+//                       vector if the row covers all of it and byte by byte otherwise, or the row's reflected columns (at
+//                       most tiles_x: a run of the same source row, read backwards).  Reflected rows are source rows;
 //   clahe_table_kernel  one wave per (frame, tile): the clip, the closed-form redistribution, the table scan;
 //   clahe_apply_kernel  the rows of a frame fall into tiles_y + 1 groups that share one pair (r1, r2) of tile rows.  A
 //                       block owns up to kApplyBlockBytes of consecutive rows of one group as one byte range aligned on
@@ -62,8 +62,8 @@ __global__ __launch_bounds__(kHistThreads) void clahe_hist_kernel(const uint8_t*
     const uint32_t n = x0 < w ? (tw < w - x0 ? tw : w - x0) : 0;  // columns x0 .. x0 + n - 1 are source columns
     const uint32_t m = tw - n;                                    // the rest are reflected: source column 2w - 2 - x
     const uint32_t refl0 = m ? 2 * w - 1 - x0 - tw : 0;           // the lowest of them
-    // per row: the 16-byte aligned chunks n bytes at any alignment can touch, and one slot for the reflected columns
-    const uint32_t slots = (tw + 15) / 16 + 2;
+    // per row: the aligned chunks of its n <= tw source bytes, and one slot for the reflected columns
+    const uint32_t slots = aligned_chunks_of(tw) + 1;
     const uint32_t r0 = band * band_rows;
     const uint32_t r1 = r0 + band_rows < th ? r0 + band_rows : th;
     const uint32_t items = (r1 - r0) * slots;
@@ -83,14 +83,13 @@ __global__ __launch_bounds__(kHistThreads) void clahe_hist_kernel(const uint8_t*
                 hi = refl0 + m;
             } else {
                 const int mis = (int)(reinterpret_cast<uintptr_t>(row + x0) & 15u);
-                const int c0 = 16 * (int)s - mis;  // the chunk is bytes c0 .. c0 + 15 of the row's n source bytes
-                const int b0 = c0 > 0 ? c0 : 0, b1 = c0 + 16 < (int)n ? c0 + 16 : (int)n;
-                if (b1 - b0 == 16) {
+                const AlignedChunk<int> c = aligned_chunk<int>(mis, (int)s, (int)n);  // of the row's n source bytes
+                if (c.whole()) {
                     full = true;
-                    v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + x0 + c0));
-                } else if (b1 > b0) {
-                    lo = x0 + (uint32_t)b0;
-                    hi = x0 + (uint32_t)b1;
+                    v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + x0 + c.first));
+                } else if (c.b1 > c.b0) {
+                    lo = x0 + (uint32_t)(c.first + c.b0);
+                    hi = x0 + (uint32_t)(c.first + c.b1);
                 }
             }
         }
@@ -165,7 +164,7 @@ __device__ __forceinline__ u32x4 clahe_vec(const uint32_t* sq, const u32x4& v, u
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             // the value is a whole number in 0 .. 255: the conversion is exact, the pack saturates
-            ow = __builtin_amdgcn_cvt_pk_u8_f32(clahe_px(sq, (v[d] >> (8 * e)) & 0xFFu, x, inv_tw, wy, wy1), e, ow);
+            ow = __builtin_amdgcn_cvt_pk_u8_f32(clahe_px(sq, chunk_byte(v, 4 * d + e), x, inv_tw, wy, wy1), e, ow);
             x++;
             if (kWrap && x == w) {
                 x = 0;
@@ -278,10 +277,10 @@ hipError_t launch_clahe_hist(hipStream_t stream, const uint8_t* d_in, uint32_t* 
     band_rows = band_rows < 1 ? 1 : (band_rows > (uint32_t)g.th ? (uint32_t)g.th : band_rows);
     const uint32_t nbands = ((uint32_t)g.th + band_rows - 1) / band_rows;
     band_rows = ((uint32_t)g.th + nbands - 1) / nbands;  // bands of equal size
-    const uint64_t blocks = (uint64_t)nframes * (uint64_t)(g.tiles_x * g.tiles_y) * nbands;
-    if (!grid_fits(blocks))
+    const FrameGrid fg = frame_grid((uint64_t)(g.tiles_x * g.tiles_y) * nbands, 1, nframes);
+    if (!fg.ok)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(clahe_hist_kernel, dim3((uint32_t)blocks), dim3(kHistThreads), 0, stream, d_in, d_hist, g,
+    hipLaunchKernelGGL(clahe_hist_kernel, dim3(fg.blocks), dim3(kHistThreads), 0, stream, d_in, d_hist, g,
                        band_rows, nbands);
     return hipGetLastError();
 }
@@ -291,10 +290,10 @@ hipError_t launch_clahe_table(hipStream_t stream, const uint32_t* d_hist, uint8_
 {
     if (!clahe_sizes_ok(g, nframes) || g.cl < 0)
         return hipErrorInvalidValue;
-    const uint64_t blocks = (uint64_t)nframes * (uint64_t)(g.tiles_x * g.tiles_y);
-    if (!grid_fits(blocks))
+    const FrameGrid fg = frame_grid(g.tiles_x * g.tiles_y, 1, nframes);
+    if (!fg.ok)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(clahe_table_kernel, dim3((uint32_t)blocks), dim3(kWave), 0, stream, d_hist, d_luts,
+    hipLaunchKernelGGL(clahe_table_kernel, dim3(fg.blocks), dim3(kWave), 0, stream, d_hist, d_luts,
                        (uint32_t)g.cl, g.lut_scale);
     return hipGetLastError();
 }

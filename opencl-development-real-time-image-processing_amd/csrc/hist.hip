@@ -3,7 +3,7 @@
 // cv::threshold(THRESH_BINARY | THRESH_OTSU)).  Semantics: include/mi355_imgfilter.h.
 //
 // Every frame is the flat byte range [f * npx, (f + 1) * npx), npx = w * h < 2^31.  The three launches, the block
-// histogram frame, the byte-range walk and the table scan are hist_common.hpp's:
+// histogram frame, the byte-range walk and the table scan are hist_common.hpp's, the grid mask_common.hpp's:
 //   hist_kernel   256 x kHistVec vectors of a frame's body per block, aligned on the input; head and tail in its first;
 //   table_kernel  one wave per frame makes its histogram a 256-byte table (LUT).  Equalize: the table scan from the
 //                 first occupied bin.  Otsu: OpenCV's serial fp64 loop in one lane, operation by operation (no fused
@@ -27,11 +27,10 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const uint8_t* __res
     __shared__ uint32_t sh[kHistWaves * 256];
     const int tid = threadIdx.x;
     uint32_t* hw = block_hists_begin(sh);
-    const uint32_t f = blockIdx.x / tiles, tile = blockIdx.x - f * tiles;
+    const auto [f, tile, j0] = frame_block(tiles, kHistThreads * kHistVec);
     const uint8_t* p = in + (size_t)f * npx;
     const ByteRange r = byte_range(p, npx);
     const u32x4* vp = reinterpret_cast<const u32x4*>(p + r.head);
-    const uint32_t j0 = tile * (kHistThreads * kHistVec) + tid;
 #pragma unroll
     for (int u0 = 0; u0 < kHistVec; u0 += 4) {
         u32x4 v[4];
@@ -145,13 +144,12 @@ __global__ __launch_bounds__(kHistThreads) void apply_kernel(const uint8_t* __re
 {
     __shared__ uint8_t sl[256];
     const int tid = threadIdx.x;
-    const uint32_t f = blockIdx.x / tiles, tile = blockIdx.x - f * tiles;
+    const auto [f, tile, j0] = frame_block(tiles, kHistThreads * kApplyVec);
     sl[tid] = lut[(size_t)f * 256 + tid];
     __syncthreads();
     const uint8_t* p = in + (size_t)f * npx;
     uint8_t* q = out + (size_t)f * npx;
     const ByteRange r = byte_range(q, npx);
-    const uint32_t j0 = tile * (kHistThreads * kApplyVec) + tid;
     u32x4 v[kApplyVec];
 #pragma unroll
     for (int u = 0; u < kApplyVec; u++) {
@@ -171,29 +169,22 @@ __global__ __launch_bounds__(kHistThreads) void apply_kernel(const uint8_t* __re
         for_edge_byte(r, npx, tid, [&](uint32_t e) { q[e] = sl[p[e]]; });
 }
 
-// blocks of one frame for `per_block` 16-byte vectors per block, and the whole grid; false if it is too large
-bool grid_of(int w, int h, int nframes, int per_block, uint32_t* tiles, uint32_t* blocks)
+// the grid for `per_block` 16-byte vectors of a frame per block; not ok if the sizes are refused or it is too large
+FrameGrid grid_of(int w, int h, int nframes, int per_block)
 {
-    if (!hist_frames_ok(w, h, nframes))
-        return false;
-    const uint64_t t = ((uint64_t)(w * h) / 16 + (uint64_t)per_block - 1) / (uint64_t)per_block;
-    const uint64_t tt = t ? t : 1;  // a frame shorter than one vector still has its head / tail block
-    if (!grid_fits(tt * (uint64_t)nframes))
-        return false;
-    *tiles = (uint32_t)tt;
-    *blocks = (uint32_t)(tt * (uint64_t)nframes);
-    return true;
+    const uint64_t nvec = (uint64_t)w * (uint64_t)h / 16;  // a frame shorter than one has its head / tail block all the same
+    return hist_frames_ok(w, h, nframes) ? frame_grid(nvec ? nvec : 1, per_block, nframes) : FrameGrid{};
 }
 
 }  // namespace
 
 hipError_t launch_hist(hipStream_t stream, const uint8_t* d_in, uint32_t* d_hist, int w, int h, int nframes)
 {
-    uint32_t tiles = 0, blocks = 0;
-    if (!grid_of(w, h, nframes, kHistThreads * kHistVec, &tiles, &blocks))
+    const FrameGrid g = grid_of(w, h, nframes, kHistThreads * kHistVec);
+    if (!g.ok)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hist_kernel, dim3(blocks), dim3(kHistThreads), 0, stream, d_in, d_hist, (uint32_t)(w * h),
-                       tiles);
+    hipLaunchKernelGGL(hist_kernel, dim3(g.blocks), dim3(kHistThreads), 0, stream, d_in, d_hist, (uint32_t)(w * h),
+                       g.bpf);
     return hipGetLastError();
 }
 
@@ -210,11 +201,11 @@ hipError_t launch_hist_table(hipStream_t stream, const uint32_t* d_hist, uint8_t
 hipError_t launch_lut_apply(hipStream_t stream, const uint8_t* d_in, uint8_t* d_out, const uint8_t* d_lut, int w, int h,
                             int nframes)
 {
-    uint32_t tiles = 0, blocks = 0;
-    if (!grid_of(w, h, nframes, kHistThreads * kApplyVec, &tiles, &blocks))
+    const FrameGrid g = grid_of(w, h, nframes, kHistThreads * kApplyVec);
+    if (!g.ok)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(kHistThreads), 0, stream, d_in, d_out, d_lut, (uint32_t)(w * h),
-                       tiles);
+    hipLaunchKernelGGL(apply_kernel, dim3(g.blocks), dim3(kHistThreads), 0, stream, d_in, d_out, d_lut, (uint32_t)(w * h),
+                       g.bpf);
     return hipGetLastError();
 }
 

@@ -13,7 +13,7 @@
 //   table scan   lane l of one wave holds bins 4 l .. 4 l + 3: an integer prefix sum across lanes (exact in any order),
 //                then one fp32 multiply and rint per bin (-ffp-contract=off: nothing fuses).
 #pragma once
-#include "common.hpp"
+#include "mask_common.hpp"
 
 namespace mi355 {
 
@@ -23,18 +23,6 @@ constexpr int kHistVec = 16;  // 16-byte vectors per thread of a counting block
 constexpr int kApplyVec = 8;  // per thread of an applying block
 constexpr uint32_t kHistBlockBytes = kHistThreads * kHistVec * 16;    // 64 KiB per block, 256 atomics per flush
 constexpr uint32_t kApplyBlockBytes = kHistThreads * kApplyVec * 16;  // 32 KiB per block
-
-// host: frames of w x h < 2^31 pixels (OpenCV counts pixels in an int), and a block count that fits a grid
-inline bool hist_frames_ok(int w, int h, int nframes)
-{
-    return w > 0 && h > 0 && nframes > 0 && (uint64_t)w * (uint64_t)h < (1ull << 31);
-}
-inline bool grid_fits(uint64_t blocks) { return blocks <= 0x7FFFFFFFull; }
-
-__device__ __forceinline__ void lds_add(uint32_t* hw, uint32_t bin, uint32_t n)
-{
-    __hip_atomic_fetch_add(hw + bin, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 __device__ __forceinline__ void count_dword(uint32_t* hw, uint32_t d)
 {
@@ -97,7 +85,7 @@ __device__ __forceinline__ void block_hists_flush(const uint32_t* sh, uint32_t* 
     for (int wv = 0; wv < kHistWaves; wv++)
         s += sh[wv * 256 + tid];
     if (s)
-        __hip_atomic_fetch_add(row + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(row + tid, s, MI355_RELAXED_AGENT);
 }
 
 // nbytes bytes: head bytes [0, head), nvec vectors that are 16-byte aligned at `aligned_side`, tail bytes from body_end
@@ -127,14 +115,7 @@ __device__ __forceinline__ void for_edge_byte(const ByteRange& r, uint32_t nbyte
 __device__ __forceinline__ uint32_t bins_below(const u32x4& hv, int lane)
 {
     const uint32_t lsum = hv.x + hv.y + hv.z + hv.w;
-    uint32_t inc = lsum;
-#pragma unroll
-    for (int d = 1; d < kWave; d *= 2) {
-        const uint32_t o = __shfl_up(inc, d);
-        if (lane >= d)
-            inc += o;
-    }
-    return inc - lsum;
+    return wave_scan_inclusive(lsum, lane) - lsum;
 }
 
 // a table entry from a cumulative count: (float)count * scale, cvRound, saturated to a byte

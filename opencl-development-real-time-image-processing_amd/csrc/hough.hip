@@ -25,12 +25,12 @@
 //                        bitonic sort of at most 4096 keys in LDS puts them in the contract's order (votes descending, cell
 //                        ascending = key descending), and the (rho, theta) rows, the votes and the zero fill are written.
 // Kernel boundaries are the only ordering between workgroups: no flag, no grid barrier, no retry; every loop is bounded by
-// a count fixed before it starts.
+// a count fixed before it starts.  Grids, prefix sums, compaction and chunk bytes: mask_common.hpp.
 #include <algorithm>
 
 #include "common.hpp"
-#include "hist_common.hpp"
 #include "kernels.hpp"
+#include "mask_common.hpp"
 #include "tile_common.hpp"
 
 namespace mi355 {
@@ -68,8 +68,6 @@ struct VoteArgs {
     float agg_step;
 };
 
-__device__ __forceinline__ uint32_t chunk_byte16(const u32x4& v, int j) { return (v[j >> 2] >> (8 * (j & 3))) & 0xFFu; }
-
 __global__ __launch_bounds__(kHoughPointThreads) void hough_points_kernel(const uint8_t* __restrict__ in,
                                                                           uint32_t* __restrict__ pts,
                                                                           uint32_t* __restrict__ npts, uint32_t w,
@@ -78,45 +76,25 @@ __global__ __launch_bounds__(kHoughPointThreads) void hough_points_kernel(const 
     __shared__ uint32_t wave_sum[kHoughPointThreads / kWave];
     __shared__ uint32_t block_base;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const uint32_t f = blockIdx.x / bpf, chunk = blockIdx.x - f * bpf;
+    const auto [f, blk, item] = frame_block(bpf, kHoughPointThreads);
     const uint8_t* fin = in + (size_t)f * npx;
-    const uint32_t p0 = chunk * kHoughPointBlock + (uint32_t)tid * kHoughPointBytes;  // npx < 2^31: no wrap
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (p0 + kHoughPointBytes <= npx) {
-        v = *reinterpret_cast<const u32x4_a1*>(fin + p0);
-    } else {
-        for (int j = 0; j < kHoughPointBytes; j++)  // bound: 16 bytes; nothing past the frame is read
-            if (p0 + (uint32_t)j < npx)
-                v[j >> 2] |= (uint32_t)fin[p0 + j] << (8 * (j & 3));
-    }
+    const uint32_t p0 = item * kHoughPointBytes;  // npx < 2^31: no wrap
+    const u32x4 v = p0 + kHoughPointBytes <= npx ? *reinterpret_cast<const u32x4_a1*>(fin + p0)
+                                                 : load_chunk_bytes(fin + p0, 0, p0 < npx ? (int)(npx - p0) : 0);
     uint32_t m = 0;
 #pragma unroll
     for (int j = 0; j < kHoughPointBytes; j++)
-        m |= (chunk_byte16(v, j) != 0u ? 1u : 0u) << j;
+        m |= (chunk_byte(v, j) != 0u ? 1u : 0u) << j;
     const uint32_t cnt = (uint32_t)__popc(m);
-    uint32_t inc = cnt;
-#pragma unroll
-    for (int d = 1; d < kWave; d *= 2) {
-        const uint32_t o = __shfl_up(inc, d);
-        if (lane >= d)
-            inc += o;
-    }
-    if (lane == kWave - 1)
-        wave_sum[wave] = inc;
-    __syncthreads();
-    uint32_t below = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < kHoughPointThreads / kWave; k++) {
-        below += k < wave ? wave_sum[k] : 0u;
-        total += wave_sum[k];
-    }
+    const uint32_t inc = wave_scan_inclusive(cnt, lane);
+    const BlockOffsets o = block_offsets<kHoughPointThreads / kWave>(inc, wave_sum, lane, wave);
     if (tid == 0)
-        block_base = total ? __hip_atomic_fetch_add(npts + f, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        block_base = o.total ? __hip_atomic_fetch_add(npts + f, o.total, MI355_RELAXED_AGENT) : 0u;
     __syncthreads();
     if (cnt == 0)
         return;
     // block_base + total <= the nonzero bytes of the frame <= npx: the list cannot overflow its npx entries
-    uint32_t* dst = pts + (size_t)f * npx + block_base + below + (inc - cnt);
+    uint32_t* dst = pts + (size_t)f * npx + block_base + o.before + (inc - cnt);
     uint32_t y = p0 / w, x = p0 - y * w;
 #pragma unroll
     for (int j = 0; j < kHoughPointBytes; j++) {
@@ -228,8 +206,7 @@ __global__ __launch_bounds__(kHoughPointThreads) void hough_peaks_kernel(const i
                                                                          uint32_t bpf)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t f = blockIdx.x / bpf, chunk = blockIdx.x - f * bpf;
-    const uint32_t i = chunk * kHoughPointThreads + threadIdx.x;  // interior cell number: numangle * numrho < 2^29
+    const auto [f, blk, i] = frame_block(bpf, kHoughPointThreads);  // i: interior cell number: numangle * numrho < 2^29
     const uint32_t ncell = (uint32_t)numangle * (uint32_t)numrho;
     const int S = numrho + 2;
     const int32_t* a = accum + (size_t)f * (size_t)(numangle + 2) * (size_t)S;
@@ -245,12 +222,7 @@ __global__ __launch_bounds__(kHoughPointThreads) void hough_peaks_kernel(const i
     const uint64_t m = __ballot(peak);
     if (m == 0)
         return;
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == leader)
-        base = __hip_atomic_fetch_add(count + f, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    const size_t slot = (size_t)base + (size_t)__popcll(m & ((1ull << lane) - 1ull));
+    const size_t slot = (size_t)wave_add_once(count + f, m, lane) + (size_t)lanes_below(m, lane);
     // two neighbours of a row cannot both be peaks (> to the left, >= to the right), so a frame has at most
     // numangle * ceil(numrho / 2) = cand_stride of them; the test below never fails and guards the store all the same
     if (peak && slot < cand_stride)
@@ -305,13 +277,7 @@ __global__ __launch_bounds__(kHoughThreads) void hough_select_kernel(const uint6
 #pragma unroll 4
                 for (int k = 0; k < kPer; k++)  // bound: 64 bins
                     own += hist[top - k];
-                uint32_t inc = own;
-#pragma unroll
-                for (int d = 1; d < kWave; d *= 2) {
-                    const uint32_t o = __shfl_up(inc, d);
-                    if (lane >= d)
-                        inc += o;
-                }
+                const uint32_t inc = wave_scan_inclusive(own, lane);
                 const uint64_t reached = __ballot(inc >= need);  // never empty: at least `need` keys share the prefix
                 if (reached && lane == __ffsll((unsigned long long)reached) - 1) {
                     uint32_t above = inc - own;
@@ -336,7 +302,7 @@ __global__ __launch_bounds__(kHoughThreads) void hough_select_kernel(const uint6
         for (uint32_t i = tid; i < n; i += kHoughThreads) {  // bound: as above
             const uint64_t key = list[i];
             if (key >= prefix) {
-                const uint32_t at = __hip_atomic_fetch_add(&sh_fill, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                const uint32_t at = __hip_atomic_fetch_add(&sh_fill, 1u, MI355_RELAXED_WG);
                 if (at < (uint32_t)kHoughMaxLines)
                     keys[at] = key;
             }
@@ -437,19 +403,18 @@ hipError_t launch_hough_accum(hipStream_t stream, const uint8_t* d_in, int32_t* 
         return hipErrorInvalidValue;
     const HoughPlan p = hough_plan(g.numangle, g.numrho);
     const uint32_t npx = (uint32_t)g.w * (uint32_t)g.h;
-    const uint32_t bpf = (npx + kHoughPointBlock - 1) / kHoughPointBlock;
     const int groups = (g.numangle + p.angles_per_block - 1) / p.angles_per_block;
-    const uint64_t pblocks = (uint64_t)g.nframes * bpf;
-    const uint64_t vblocks = (uint64_t)g.nframes * (uint64_t)groups * (uint64_t)p.rho_splits;
-    if (!grid_fits(pblocks) || !grid_fits(vblocks))
+    const FrameGrid pg = frame_grid(npx, kHoughPointBlock, g.nframes);
+    const FrameGrid vg = frame_grid((uint64_t)groups * (uint64_t)p.rho_splits, 1, g.nframes);
+    if (!pg.ok || !vg.ok)
         return hipErrorInvalidValue;
     uint32_t* npts = static_cast<uint32_t*>(d_scratch);
     uint32_t* pts = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_scratch) + counters_bytes(g));
     hipError_t e = hipMemsetAsync(npts, 0, (size_t)g.nframes * sizeof(uint32_t), stream);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(hough_points_kernel, dim3((uint32_t)pblocks), dim3(kHoughPointThreads), 0, stream, d_in, pts, npts,
-                       (uint32_t)g.w, npx, bpf);
+    hipLaunchKernelGGL(hough_points_kernel, dim3(pg.blocks), dim3(kHoughPointThreads), 0, stream, d_in, pts, npts,
+                       (uint32_t)g.w, npx, pg.bpf);
     VoteArgs a;
     a.pts = pts;
     a.npts = npts;
@@ -469,7 +434,7 @@ hipError_t launch_hough_accum(hipStream_t stream, const uint8_t* d_in, int32_t* 
     if (const char* env = tune_env("MI355_TUNE_HOUGH_UNROLL"))
         unroll = atoi(env) == 1 ? 1 : kHoughUnroll;
     const bool small = p.angles_per_block * p.span <= kHoughSmallCells;
-    const dim3 grid((uint32_t)vblocks), block(kHoughThreads);
+    const dim3 grid(vg.blocks), block(kHoughThreads);
     if (small && unroll == 1)
         hipLaunchKernelGGL((hough_vote_kernel<kHoughSmallCells, 1>), grid, block, 0, stream, a);
     else if (small)
@@ -487,17 +452,16 @@ hipError_t launch_hough_lines(hipStream_t stream, const int32_t* d_accum, float*
     if (!geom_ok(g) || threshold < 0 || max_lines < 1 || max_lines > kHoughMaxLines)
         return hipErrorInvalidValue;
     const uint32_t ncell = (uint32_t)g.numangle * (uint32_t)g.numrho;
-    const uint32_t bpf = (ncell + kHoughPointThreads - 1) / kHoughPointThreads;
-    const uint64_t blocks = (uint64_t)g.nframes * bpf;
-    if (!grid_fits(blocks))
+    const FrameGrid pg = frame_grid(ncell, kHoughPointThreads, g.nframes);
+    if (!pg.ok)
         return hipErrorInvalidValue;
     uint64_t* cand = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(d_scratch) + counters_bytes(g));
     uint32_t* count = reinterpret_cast<uint32_t*>(d_count);
     const hipError_t e = hipMemsetAsync(count, 0, (size_t)g.nframes * sizeof(uint32_t), stream);
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(hough_peaks_kernel, dim3((uint32_t)blocks), dim3(kHoughPointThreads), 0, stream, d_accum, cand, count,
-                       g.numangle, g.numrho, threshold, cand_stride_of(g), bpf);
+    hipLaunchKernelGGL(hough_peaks_kernel, dim3(pg.blocks), dim3(kHoughPointThreads), 0, stream, d_accum, cand, count,
+                       g.numangle, g.numrho, threshold, cand_stride_of(g), pg.bpf);
     hipLaunchKernelGGL(hough_select_kernel, dim3((uint32_t)g.nframes), dim3(kHoughThreads), 0, stream, cand, count, d_lines,
                        d_votes, cand_stride_of(g), g.numrho, max_lines, g.rho_f, g.theta_f, g.min_theta_f);
     return hipGetLastError();
