@@ -390,25 +390,68 @@ int check_filter(int filter, int w, int h, int nframes, int k, float sigma, cons
     return MI355_OK;
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
+// [a0, a0 + na) and [b0, b0 + nb) share a byte
+constexpr bool overlap(uintptr_t a0, size_t na, uintptr_t b0, size_t nb) { return a0 < b0 + nb && b0 < a0 + na; }
 
 size_t frame_bytes(int w, int h, int nframes, int bpp) { return (size_t)w * h * nframes * (size_t)bpp; }
 
-// What every device-resident call refuses of its frame pointers, each side counted with its own shape and bytes per
-// pixel.  RGBA pixels are accessed as dwords.  The stencil and geometric kernels read neighbouring rows / halo / source
-// pixels of what another wave may already have overwritten, and the (pointwise) grayscale kernels are compiled for
-// non-aliasing pointers (__restrict__, non-temporal accesses): in-place and overlapping calls are rejected, not run,
-// for every call (the reference never aliases them either: two clCreateBuffer objects per call,
-// RT/src/Controller.cpp:234-244)
-bool bad_dev_io(const void* d_in, size_t in_bytes, int in_bpp, const void* d_out, size_t out_bytes, int out_bpp)
+// One byte range of a device-resident call: where it starts (0: the caller passed no such pointer), its length, the
+// power-of-two alignment the kernels need of it, and whether the call writes it.
+struct Range {
+    uintptr_t at;
+    size_t len;
+    uintptr_t align;
+    bool written;
+};
+
+Range rd(const void* p, size_t len, int align) { return {reinterpret_cast<uintptr_t>(p), len, (uintptr_t)align, false}; }
+Range wr(const void* p, size_t len, int align) { return {reinterpret_cast<uintptr_t>(p), len, (uintptr_t)align, true}; }
+
+// What every device-resident call refuses of its pointers: a present pointer that misses its alignment (RGBA pixels and
+// every 4- or 8-byte output are accessed as such; frames of 1-byte pixels take any address, so a frame's alignment is its
+// bytes per pixel), and two present ranges that share a byte unless neither is written.  The stencil and geometric
+// kernels read neighbouring rows / halo / source pixels of what another wave may already have overwritten, and the
+// (pointwise) grayscale kernels are compiled for non-aliasing pointers (__restrict__, non-temporal accesses): in-place
+// and overlapping calls are rejected, not run, for every call (the reference never aliases them either: two
+// clCreateBuffer objects per call, RT/src/Controller.cpp:234-244)
+template <int N>
+constexpr bool bad_ranges(const Range (&r)[N])
 {
-    return (in_bpp == 4 && (reinterpret_cast<uintptr_t>(d_in) & 3u)) ||
-           (out_bpp == 4 && (reinterpret_cast<uintptr_t>(d_out) & 3u)) || overlap(d_in, in_bytes, d_out, out_bytes);
+    for (int i = 0; i < N; i++) {
+        if (!r[i].at)
+            continue;
+        if (r[i].at & (r[i].align - 1))
+            return true;
+        for (int j = 0; j < i; j++)
+            if (r[j].at && (r[i].written || r[j].written) && overlap(r[i].at, r[i].len, r[j].at, r[j].len))
+                return true;
+    }
+    return false;
+}
+
+static_assert(!bad_ranges({{64, 16, 4, false}, {80, 16, 4, true}}), "touching ranges pass");
+static_assert(bad_ranges({{64, 17, 4, false}, {80, 16, 4, true}}), "one shared byte fails ...");
+static_assert(bad_ranges({{80, 16, 4, true}, {64, 17, 1, false}}), "... whichever side is written");
+static_assert(!bad_ranges({{64, 32, 4, false}, {80, 32, 2, false}, {128, 8, 8, true}}), "read-only ranges may overlap");
+static_assert(!bad_ranges({{64, 32, 1, false}, {0, 1u << 20, 8, true}, {96, 8, 8, true}}), "a null entry is ignored");
+static_assert(bad_ranges({{64, 16, 1, false}, {82, 16, 4, true}}), "a misaligned entry fails");
+static_assert(!bad_ranges({{65, 15, 1, false}, {80, 16, 4, true}}), "a 1-byte range takes any address");
+
+// The front of a device-resident call with frames of `bpp` bytes per pixel in and out, each side with its own shape: the
+// null checks, what the call's value check answered (it is pure, so the caller has evaluated it), the pointer rules, and
+// the context's device made current.
+int frames_dev(mi355_ctx* ctx, const void* d_in, const void* d_out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+               int nframes, int values_rc)
+{
+    if (!ctx || !d_in || !d_out)
+        return MI355_ERR_BAD_ARG;
+    if (values_rc != MI355_OK)
+        return values_rc;
+    if (bad_ranges({rd(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp),
+                    wr(d_out, frame_bytes(dst_w, dst_h, nframes, bpp), bpp)}))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return MI355_OK;
 }
 
 // EQUALIZE_GRAY8 / OTSU_GRAY8 up to the tables in ctx->d_lut; Otsu's thresholds also to d_thresh if not null (below)
@@ -423,8 +466,8 @@ int dispatch_dev(mi355_ctx* ctx, int filter, const void* d_in, void* d_out, int 
     int rc = check_filter(filter, w, h, nframes, k, sigma, &f);
     if (rc != MI355_OK)
         return rc;
-    if (bad_dev_io(d_in, frame_bytes(w, h, nframes, f->in_bpp), f->in_bpp, d_out, frame_bytes(w, h, nframes, f->out_bpp),
-                   f->out_bpp))
+    if (bad_ranges({rd(d_in, frame_bytes(w, h, nframes, f->in_bpp), f->in_bpp),
+                    wr(d_out, frame_bytes(w, h, nframes, f->out_bpp), f->out_bpp)}))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const GaussCoef* coef = nullptr;
@@ -610,6 +653,83 @@ int timed_roundtrip(mi355_ctx* ctx, const HostIO& io, const uint8_t* in, uint8_t
                     Launch launch)
 {
     return timed_roundtrip(ctx, io, in, out, prof_ns, [] { return (int)MI355_OK; }, launch);
+}
+
+// The whole of a host-buffer call with frames of `bpp` bytes per pixel in and out, each side with its own shape: the null
+// checks, what the call's value check answered (it is pure, so the caller has evaluated it), the staging (BGR input
+// with 1-byte frames: unsupported), scratch() for what the family pools beside the frames, outside the timed window, and
+// the round trip around dev(), the family's device-resident call from ctx->d_in to ctx->d_out.
+template <class Scratch, class Dev>
+int frames_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h, int dst_w, int dst_h,
+                   int nframes, uint64_t prof_ns[6], int values_rc, Scratch scratch, Dev dev)
+{
+    if (!ctx || !in || !out)
+        return MI355_ERR_BAD_ARG;
+    if (values_rc != MI355_OK)
+        return values_rc;
+    HostIO io;
+    int rc = stage_host(ctx, (size_t)src_w * src_h * nframes, bpp, frame_bytes(dst_w, dst_h, nframes, bpp), &io);
+    if (rc == MI355_OK)
+        rc = scratch();
+    if (rc != MI355_OK)
+        return rc;
+    return timed_roundtrip(ctx, io, in, out, prof_ns, dev);
+}
+
+int no_scratch() { return MI355_OK; }  // ... of a family that pools nothing
+
+// One of the several outputs of a host-buffer call: where the caller takes it (null: not taken), its bytes and the
+// alignment of its place in the pooled output buffer.  An output the caller does not take has no place there, unless the
+// kernels write it regardless (`kept`).
+struct HostOut {
+    void* host;
+    size_t bytes, align;
+    bool kept;
+    size_t at;  // set by outputs_batched
+};
+
+// The place of an output on the device, once outputs_batched has staged the call; null for an output without one
+template <class T>
+T* out_dev(mi355_ctx* ctx, const HostOut& e)
+{
+    return e.host || e.kept ? reinterpret_cast<T*>(static_cast<uint8_t*>(ctx->d_out.p) + e.at) : nullptr;
+}
+
+// What follows the null and value checks of a host-buffer call with `in_bytes` of 1-byte frames in (BGR input:
+// unsupported) and several outputs.  They lie side by side in ctx->d_out in their order; scratch() is what the family
+// pools beside them, outside the timed window; dev() is its device-resident call from ctx->d_in to the out_dev()s.  The
+// first output the caller takes is what the round trip reads back behind the kernels (from 0: nothing `kept` stands in
+// front of it).  The others, a few rows or further planes, leave the device ahead of it: enqueued behind dev() and
+// before the kernel-end event, so they count as kernel time.
+template <int N, class Scratch, class Dev>
+int outputs_batched(mi355_ctx* ctx, const uint8_t* in, size_t in_bytes, HostOut (&o)[N], uint64_t prof_ns[6],
+                    Scratch scratch, Dev dev)
+{
+    size_t total = 0;
+    int first = N;  // the caller's null checks have seen to it that one is taken
+    for (int i = 0; i < N; i++)
+        if (o[i].host || o[i].kept) {
+            o[i].at = (total + o[i].align - 1) & ~(o[i].align - 1);
+            total = o[i].at + o[i].bytes;
+            first = o[i].host && i < first ? i : first;
+        }
+    HostIO io;
+    int rc = stage_host(ctx, in_bytes, 1, total, &io);
+    if (rc == MI355_OK)
+        rc = scratch();
+    if (rc != MI355_OK)
+        return rc;
+    io.out_bytes = o[first].bytes;
+    return timed_roundtrip(ctx, io, in, static_cast<uint8_t*>(o[first].host), prof_ns, [&] {
+        const int lrc = dev();
+        if (lrc != MI355_OK)
+            return lrc;
+        for (int i = first + 1; i < N; i++)
+            if (o[i].host)
+                HIP_TRY(ctx, hipMemcpyAsync(o[i].host, out_dev<void>(ctx, o[i]), o[i].bytes, hipMemcpyDeviceToHost,
+                                            ctx->stream));
+        return (int)MI355_OK;
+    });
 }
 
 // H2D, kernel, D2H through the context's pooled buffers
@@ -1188,15 +1308,10 @@ MI355_API int mi355_resize_check(int bpp, int src_w, int src_h, int dst_w, int d
 MI355_API int mi355_resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int bpp, int src_w, int src_h, int dst_w,
                                int dst_h, int nframes, int interp)
 {
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
-    const int rc = mi355_resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    const int rc = frames_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes,
+                              mi355_resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes, interp));
     if (rc != MI355_OK)
         return rc;
-    if (bad_dev_io(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp, d_out, frame_bytes(dst_w, dst_h, nframes, bpp),
-                   bpp))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_resize(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp, src_w,
                                src_h, dst_w, dst_h, nframes, interp));
     return MI355_OK;
@@ -1207,16 +1322,8 @@ MI355_API int mi355_resize_dev(mi355_ctx* ctx, const void* d_in, void* d_out, in
 MI355_API int mi355_resize_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int bpp, int src_w, int src_h,
                                    int dst_w, int dst_h, int nframes, int interp, uint64_t prof_ns[6])
 {
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = mi355_resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
-    if (rc != MI355_OK)
-        return rc;
-    HostIO io;
-    rc = stage_host(ctx, (size_t)src_w * src_h * nframes, bpp, frame_bytes(dst_w, dst_h, nframes, bpp), &io);
-    if (rc != MI355_OK)
-        return rc;
-    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+    const int vrc = mi355_resize_check(bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
+    return frames_batched(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, prof_ns, vrc, no_scratch, [&] {
         return mi355_resize_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, interp);
     });
 }
@@ -1255,16 +1362,11 @@ MI355_API int mi355_warp_affine_dev(mi355_ctx* ctx, const void* d_in, void* d_ou
                                     int dst_w, int dst_h, int nframes, const double m[6], int flags, int border_mode,
                                     uint32_t border_value)
 {
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
     double inv[6];
-    const int rc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv);
+    const int rc = frames_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes,
+                              check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv));
     if (rc != MI355_OK)
         return rc;
-    if (bad_dev_io(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp, d_out, frame_bytes(dst_w, dst_h, nframes, bpp),
-                   bpp))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_warp_affine(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp,
                                     src_w, src_h, dst_w, dst_h, nframes, inv, flags & ~MI355_WARP_INVERSE_MAP, border_mode,
                                     border_value));
@@ -1275,16 +1377,8 @@ MI355_API int mi355_warp_affine_batched(mi355_ctx* ctx, const uint8_t* in, uint8
                                         int dst_w, int dst_h, int nframes, const double m[6], int flags, int border_mode,
                                         uint32_t border_value, uint64_t prof_ns[6])
 {
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
-    if (rc != MI355_OK)
-        return rc;
-    HostIO io;
-    rc = stage_host(ctx, (size_t)src_w * src_h * nframes, bpp, frame_bytes(dst_w, dst_h, nframes, bpp), &io);
-    if (rc != MI355_OK)
-        return rc;
-    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+    const int vrc = check_warp(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
+    return frames_batched(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, prof_ns, vrc, no_scratch, [&] {
         return mi355_warp_affine_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags,
                                      border_mode, border_value);
     });
@@ -1310,13 +1404,11 @@ MI355_API int mi355_remap_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int
         return rc;
     if (!d_map2 && !(map_kind == MI355_MAP_FIXED && interp == MI355_INTERP_NEAREST))
         return MI355_ERR_BAD_ARG;
-    const size_t out_bytes = frame_bytes(dst_w, dst_h, nframes, bpp);
     size_t n1 = 0, n2 = 0;
     map_bytes(dst_w, dst_h, map_kind, &n1, &n2);
-    const uintptr_t align2 = map_kind == MI355_MAP_FIXED ? 1u : 3u;
-    if (bad_dev_io(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp, d_out, out_bytes, bpp) ||
-        (reinterpret_cast<uintptr_t>(d_map1) & 3u) || (reinterpret_cast<uintptr_t>(d_map2) & align2) ||
-        overlap(d_map1, n1, d_out, out_bytes) || (d_map2 && overlap(d_map2, n2, d_out, out_bytes)))
+    if (bad_ranges({rd(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp),
+                    wr(d_out, frame_bytes(dst_w, dst_h, nframes, bpp), bpp), rd(d_map1, n1, 4),
+                    rd(d_map2, n2, map_kind == MI355_MAP_FIXED ? 2 : 4)}))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_remap(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out), bpp, src_w,
@@ -1375,16 +1467,11 @@ MI355_API int mi355_warp_perspective_dev(mi355_ctx* ctx, const void* d_in, void*
                                          int dst_w, int dst_h, int nframes, const double m[9], int flags,
                                          int border_mode, uint32_t border_value)
 {
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
     double inv[9];
-    const int rc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv);
+    const int rc = frames_dev(ctx, d_in, d_out, bpp, src_w, src_h, dst_w, dst_h, nframes,
+                              check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, inv));
     if (rc != MI355_OK)
         return rc;
-    if (bad_dev_io(d_in, frame_bytes(src_w, src_h, nframes, bpp), bpp, d_out, frame_bytes(dst_w, dst_h, nframes, bpp),
-                   bpp))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_warp_perspective(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
                                          bpp, src_w, src_h, dst_w, dst_h, nframes, inv, flags & ~MI355_WARP_INVERSE_MAP,
                                          border_mode, border_value));
@@ -1395,16 +1482,8 @@ MI355_API int mi355_warp_perspective_batched(mi355_ctx* ctx, const uint8_t* in, 
                                              int src_h, int dst_w, int dst_h, int nframes, const double m[9], int flags,
                                              int border_mode, uint32_t border_value, uint64_t prof_ns[6])
 {
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
-    if (rc != MI355_OK)
-        return rc;
-    HostIO io;
-    rc = stage_host(ctx, (size_t)src_w * src_h * nframes, bpp, frame_bytes(dst_w, dst_h, nframes, bpp), &io);
-    if (rc != MI355_OK)
-        return rc;
-    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+    const int vrc = check_perspective(bpp, src_w, src_h, dst_w, dst_h, nframes, m, flags, border_mode, nullptr);
+    return frames_batched(ctx, in, out, bpp, src_w, src_h, dst_w, dst_h, nframes, prof_ns, vrc, no_scratch, [&] {
         return mi355_warp_perspective_dev(ctx, ctx->d_in.p, ctx->d_out.p, bpp, src_w, src_h, dst_w, dst_h, nframes, m,
                                           flags, border_mode, border_value);
     });
@@ -1422,14 +1501,10 @@ MI355_API int mi355_adaptive_threshold_check(int w, int h, int nframes, int max_
 MI355_API int mi355_adaptive_threshold_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h,
                                                  int nframes, int max_value, int type, int block, double delta)
 {
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
-    const int rc = mi355_adaptive_threshold_check(w, h, nframes, max_value, type, block, delta);
+    const int rc = frames_dev(ctx, d_in, d_out, 1, w, h, w, h, nframes,
+                              mi355_adaptive_threshold_check(w, h, nframes, max_value, type, block, delta));
     if (rc != MI355_OK)
         return rc;
-    if (bad_dev_io(d_in, frame_bytes(w, h, nframes, 1), 1, d_out, frame_bytes(w, h, nframes, 1), 1))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_adaptive_threshold(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
                                            w, h, nframes, block, max_value, type == MI355_ADAPTIVE_BINARY_INV,
                                            adaptive_idelta(type, delta)));
@@ -1440,16 +1515,8 @@ MI355_API int mi355_adaptive_threshold_gray8_batched(mi355_ctx* ctx, const uint8
                                                      int nframes, int max_value, int type, int block, double delta,
                                                      uint64_t prof_ns[6])
 {
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = mi355_adaptive_threshold_check(w, h, nframes, max_value, type, block, delta);
-    if (rc != MI355_OK)
-        return rc;
-    HostIO io;
-    rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
-    if (rc != MI355_OK)
-        return rc;
-    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+    const int vrc = mi355_adaptive_threshold_check(w, h, nframes, max_value, type, block, delta);
+    return frames_batched(ctx, in, out, 1, w, h, w, h, nframes, prof_ns, vrc, no_scratch, [&] {
         return mi355_adaptive_threshold_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, max_value, type, block,
                                                   delta);
     });
@@ -1493,7 +1560,7 @@ static int check_stats_call(mi355_ctx* ctx, const void* d_in, const void* d_out,
     const int rc = check_filter(MI355_FILTER_EQUALIZE_GRAY8, w, h, nframes, 0, 0.0f, nullptr);
     if (rc != MI355_OK)
         return rc;
-    if ((reinterpret_cast<uintptr_t>(d_out) & 3u) || overlap(d_in, (size_t)w * h * nframes, d_out, nout))
+    if (bad_ranges({rd(d_in, frame_bytes(w, h, nframes, 1), 1), wr(d_out, nout, 4)}))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return MI355_OK;
@@ -1546,10 +1613,19 @@ static int clahe_plan(int w, int h, int nframes, double clip_limit, int tiles_x,
     return MI355_OK;
 }
 
+// one histogram and one table per tile of every frame
+static size_t clahe_rows(const ClaheGeom& g, int nframes) { return (size_t)nframes * (size_t)(g.tiles_x * g.tiles_y); }
+
+// the pooled scratch of a CLAHE call, device-resident or (before its timed window) host-buffer
+static int clahe_scratch(mi355_ctx* ctx, const ClaheGeom& g, int nframes)
+{
+    return hist_scratch(ctx, clahe_rows(g, nframes));
+}
+
 // CLAHE up to the tables: the zeroed tile histograms, the histogram launch and the table launch into d_luts
 static int clahe_tables(mi355_ctx* ctx, const uint8_t* in, uint8_t* d_luts, const ClaheGeom& g, int nframes)
 {
-    const int rc = zeroed_hists(ctx, (size_t)nframes * (size_t)(g.tiles_x * g.tiles_y));
+    const int rc = zeroed_hists(ctx, clahe_rows(g, nframes));
     if (rc != MI355_OK)
         return rc;
     uint32_t* hist = static_cast<uint32_t*>(ctx->d_hist.p);
@@ -1568,11 +1644,10 @@ static int clahe_check_dev(mi355_ctx* ctx, const void* d_in, const void* d_out, 
     if (rc != MI355_OK)
         return rc;
     const size_t nin = frame_bytes(w, h, nframes, 1);
-    const size_t nout = luts ? (size_t)nframes * (size_t)(tiles_x * tiles_y) * 256 : nin;
-    if ((luts && (reinterpret_cast<uintptr_t>(d_out) & 3u)) || overlap(d_in, nin, d_out, nout))
+    if (bad_ranges({rd(d_in, nin, 1), luts ? wr(d_out, clahe_rows(*g, nframes) * 256, 4) : wr(d_out, nin, 1)}))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return hist_scratch(ctx, (size_t)nframes * (size_t)(tiles_x * tiles_y));
+    return clahe_scratch(ctx, *g, nframes);
 }
 
 MI355_API int mi355_clahe_check(int w, int h, int nframes, double clip_limit, int tiles_x, int tiles_y)
@@ -1605,19 +1680,10 @@ MI355_API int mi355_clahe_luts_gray8_dev(mi355_ctx* ctx, const void* d_in, uint8
 MI355_API int mi355_clahe_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
                                         double clip_limit, int tiles_x, int tiles_y, uint64_t prof_ns[6])
 {
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
     ClaheGeom g;
-    int rc = clahe_plan(w, h, nframes, clip_limit, tiles_x, tiles_y, &g);
-    if (rc != MI355_OK)
-        return rc;
-    HostIO io;
-    rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
-    if (rc == MI355_OK)
-        rc = hist_scratch(ctx, (size_t)nframes * (size_t)(tiles_x * tiles_y));  // outside the timed window
-    if (rc != MI355_OK)
-        return rc;
-    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+    const int vrc = clahe_plan(w, h, nframes, clip_limit, tiles_x, tiles_y, &g);
+    auto scratch = [&] { return clahe_scratch(ctx, g, nframes); };
+    return frames_batched(ctx, in, out, 1, w, h, w, h, nframes, prof_ns, vrc, scratch, [&] {
         return mi355_clahe_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, clip_limit, tiles_x, tiles_y);
     });
 }
@@ -1650,6 +1716,12 @@ MI355_API int mi355_ccl_check(int w, int h, int nframes, int connectivity, int s
     return ccl_values(w, h, nframes, connectivity, stats_rows, nullptr);
 }
 
+// the pooled scratch of a labelling call, device-resident or (before its timed window) host-buffer
+static int ccl_scratch(mi355_ctx* ctx, int w, int h, int nframes)
+{
+    return ensure(ctx, ctx->d_ccl, ccl_scratch_bytes(w, h, nframes));
+}
+
 MI355_API int mi355_ccl_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_labels, int32_t* d_count,
                                   int32_t* d_stats, uint64_t* d_sums, int w, int h, int nframes, int connectivity,
                                   int stats_rows)
@@ -1662,20 +1734,14 @@ MI355_API int mi355_ccl_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_l
         return rc;
     if (stats_rows > 0 && (!d_stats || !d_sums))
         return MI355_ERR_BAD_ARG;
-    // the ranges in play: the input and the outputs this call writes
-    const void* ptr[5] = {d_in, d_labels, d_count, d_stats, d_sums};
-    const size_t len[5] = {nb.in, nb.labels, nb.count, nb.stats, nb.sums};
-    const uintptr_t align[5] = {1, 4, 4, 4, 8};
-    const int n = stats_rows > 0 ? 5 : 3;
-    for (int i = 0; i < n; i++) {
-        if (reinterpret_cast<uintptr_t>(ptr[i]) & (align[i] - 1))
-            return MI355_ERR_BAD_ARG;
-        for (int j = 0; j < i; j++)
-            if (overlap(ptr[i], len[i], ptr[j], len[j]))
-                return MI355_ERR_BAD_ARG;
-    }
+    // the ranges in play: the input and the outputs this call writes (without statistics, whatever stands in their place
+    // is not looked at)
+    const bool with_stats = stats_rows > 0;
+    if (bad_ranges({rd(d_in, nb.in, 1), wr(d_labels, nb.labels, 4), wr(d_count, nb.count, 4),
+                    wr(with_stats ? d_stats : nullptr, nb.stats, 4), wr(with_stats ? d_sums : nullptr, nb.sums, 8)}))
+        return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int erc = ensure(ctx, ctx->d_ccl, ccl_scratch_bytes(w, h, nframes));
+    const int erc = ccl_scratch(ctx, w, h, nframes);
     if (erc != MI355_OK)
         return erc;
     HIP_TRY(ctx, launch_ccl(ctx->stream, static_cast<const uint8_t*>(d_in), d_labels, d_count, d_stats, d_sums,
@@ -1695,32 +1761,13 @@ MI355_API int mi355_ccl_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_t
         return rc;
     if (stats_rows > 0 && (!stats || !sums))
         return MI355_ERR_BAD_ARG;
-    // the four outputs side by side in the pooled output buffer, the sums on an 8-byte boundary
-    const size_t at_count = nb.labels, at_stats = at_count + nb.count;
-    const size_t at_sums = (at_stats + nb.stats + 7) & ~(size_t)7;
-    HostIO io;
-    rc = stage_host(ctx, nb.in, 1, at_sums + nb.sums, &io);  // BGR input: unsupported
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_ccl, ccl_scratch_bytes(w, h, nframes));  // outside the timed window
-    if (rc != MI355_OK)
-        return rc;
-    io.out_bytes = nb.labels;  // what the round trip reads back behind the kernels; the small outputs go ahead of it
-    uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out.p);
-    return timed_roundtrip(ctx, io, in, reinterpret_cast<uint8_t*>(labels), prof_ns, [&] {
-        const int lrc = mi355_ccl_gray8_dev(ctx, ctx->d_in.p, reinterpret_cast<int32_t*>(d_out),
-                                            reinterpret_cast<int32_t*>(d_out + at_count),
-                                            stats_rows ? reinterpret_cast<int32_t*>(d_out + at_stats) : nullptr,
-                                            stats_rows ? reinterpret_cast<uint64_t*>(d_out + at_sums) : nullptr, w, h,
-                                            nframes, connectivity, stats_rows);
-        if (lrc != MI355_OK)
-            return lrc;
-        // the few rows that leave the device beside the labels: enqueued here, so they count as kernel time
-        HIP_TRY(ctx, hipMemcpyAsync(count, d_out + at_count, nb.count, hipMemcpyDeviceToHost, ctx->stream));
-        if (stats_rows) {
-            HIP_TRY(ctx, hipMemcpyAsync(stats, d_out + at_stats, nb.stats, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(sums, d_out + at_sums, nb.sums, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        return (int)MI355_OK;
+    // the labels, then the few rows that leave the device beside them; the sums on an 8-byte boundary
+    HostOut o[4] = {{labels, nb.labels, 4}, {count, nb.count, 4}, {stats_rows ? stats : nullptr, nb.stats, 4},
+                    {stats_rows ? sums : nullptr, nb.sums, 8}};
+    return outputs_batched(ctx, in, nb.in, o, prof_ns, [&] { return ccl_scratch(ctx, w, h, nframes); }, [&] {
+        return mi355_ccl_gray8_dev(ctx, ctx->d_in.p, out_dev<int32_t>(ctx, o[0]), out_dev<int32_t>(ctx, o[1]),
+                                   out_dev<int32_t>(ctx, o[2]), out_dev<uint64_t>(ctx, o[3]), w, h, nframes, connectivity,
+                                   stats_rows);
     });
 }
 
@@ -1740,6 +1787,12 @@ MI355_API int mi355_dist_check(int w, int h, int nframes)
     return dist_values(w, h, nframes);
 }
 
+// the pooled scratch of a distance call, device-resident or (before its timed window) host-buffer
+static int dist_scratch(mi355_ctx* ctx, int w, int h, int nframes)
+{
+    return ensure(ctx, ctx->d_dist, dist_scratch_bytes(w, h, nframes));
+}
+
 MI355_API int mi355_dist_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_sq, float* d_dist, int32_t* d_nearest,
                                    int w, int h, int nframes)
 {
@@ -1749,20 +1802,12 @@ MI355_API int mi355_dist_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_
     if (rc != MI355_OK)
         return rc;
     // the ranges in play: the input and the outputs this call writes
-    const size_t px = (size_t)w * h * nframes;
-    const void* ptr[4] = {d_in, d_sq, d_dist, d_nearest};
-    const size_t len[4] = {px, px * sizeof(int32_t), px * sizeof(float), px * sizeof(int32_t)};
-    for (int i = 1; i < 4; i++) {
-        if (!ptr[i])
-            continue;
-        if (reinterpret_cast<uintptr_t>(ptr[i]) & 3u)
-            return MI355_ERR_BAD_ARG;
-        for (int j = 0; j < i; j++)
-            if (ptr[j] && overlap(ptr[i], len[i], ptr[j], len[j]))
-                return MI355_ERR_BAD_ARG;
-    }
+    const size_t plane = frame_bytes(w, h, nframes, 4);
+    if (bad_ranges({rd(d_in, frame_bytes(w, h, nframes, 1), 1), wr(d_sq, plane, 4), wr(d_dist, plane, 4),
+                    wr(d_nearest, plane, 4)}))
+        return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int erc = ensure(ctx, ctx->d_dist, dist_scratch_bytes(w, h, nframes));
+    const int erc = dist_scratch(ctx, w, h, nframes);
     if (erc != MI355_OK)
         return erc;
     HIP_TRY(ctx, launch_dist(ctx->stream, static_cast<const uint8_t*>(d_in), d_sq, d_dist, d_nearest,
@@ -1778,37 +1823,13 @@ MI355_API int mi355_dist_gray8_batched(mi355_ctx* ctx, const uint8_t* in, int32_
     int rc = dist_values(w, h, nframes);
     if (rc != MI355_OK)
         return rc;
-    // the outputs the caller takes side by side in the pooled output buffer, 4 bytes per pixel each; the round trip reads
-    // back the first of them, the others leave the device ahead of it and fall into the kernel interval
-    const size_t px = (size_t)w * h * nframes, plane = px * sizeof(int32_t);
-    void* host[3] = {sq, dist, nearest};
-    size_t at[3], total = 0;
-    int first = -1;
-    for (int i = 0; i < 3; i++) {
-        at[i] = total;
-        if (host[i]) {
-            total += plane;
-            first = first < 0 ? i : first;
-        }
-    }
-    HostIO io;
-    rc = stage_host(ctx, px, 1, total, &io);  // BGR input: unsupported
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_dist, dist_scratch_bytes(w, h, nframes));  // outside the timed window
-    if (rc != MI355_OK)
-        return rc;
-    io.out_bytes = plane;
-    uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out.p);
-    return timed_roundtrip(ctx, io, in, static_cast<uint8_t*>(host[first]), prof_ns, [&] {
-        const int lrc = mi355_dist_gray8_dev(ctx, ctx->d_in.p, sq ? reinterpret_cast<int32_t*>(d_out + at[0]) : nullptr,
-                                             dist ? reinterpret_cast<float*>(d_out + at[1]) : nullptr,
-                                             nearest ? reinterpret_cast<int32_t*>(d_out + at[2]) : nullptr, w, h, nframes);
-        if (lrc != MI355_OK)
-            return lrc;
-        for (int i = first + 1; i < 3; i++)
-            if (host[i])
-                HIP_TRY(ctx, hipMemcpyAsync(host[i], d_out + at[i], plane, hipMemcpyDeviceToHost, ctx->stream));
-        return (int)MI355_OK;
+    // the planes the caller takes, 4 bytes per pixel each
+    const size_t plane = frame_bytes(w, h, nframes, 4);
+    HostOut o[3] = {{sq, plane, 4}, {dist, plane, 4}, {nearest, plane, 4}};
+    auto scratch = [&] { return dist_scratch(ctx, w, h, nframes); };
+    return outputs_batched(ctx, in, frame_bytes(w, h, nframes, 1), o, prof_ns, scratch, [&] {
+        return mi355_dist_gray8_dev(ctx, ctx->d_in.p, out_dev<int32_t>(ctx, o[0]), out_dev<float>(ctx, o[1]),
+                                    out_dev<int32_t>(ctx, o[2]), w, h, nframes);
     });
 }
 
@@ -1847,14 +1868,10 @@ static int canny_values(int w, int h, int nframes, double threshold1, double thr
     return MI355_OK;
 }
 
-// the one pointer check of the device-resident hysteresis and Canny calls, and the pooled parent array
-static int edges_check_dev(mi355_ctx* ctx, const void* d_in, const void* d_out, int w, int h, int nframes)
+// the pooled parent array of a hysteresis or Canny call, device-resident or (before its timed window) host-buffer
+static int edges_scratch(mi355_ctx* ctx, int w, int h, int nframes)
 {
-    const size_t nbytes = frame_bytes(w, h, nframes, 1);
-    if (overlap(d_in, nbytes, d_out, nbytes))
-        return MI355_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ensure(ctx, ctx->d_parent, nbytes * sizeof(int32_t));
+    return ensure(ctx, ctx->d_parent, frame_bytes(w, h, nframes, sizeof(int32_t)));
 }
 
 MI355_API int mi355_hysteresis_check(int w, int h, int nframes, int low, int high, int connectivity)
@@ -1865,11 +1882,10 @@ MI355_API int mi355_hysteresis_check(int w, int h, int nframes, int low, int hig
 MI355_API int mi355_hysteresis_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes, int low,
                                          int high, int connectivity)
 {
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
-    int rc = hysteresis_values(w, h, nframes, low, high, connectivity);
+    int rc = frames_dev(ctx, d_in, d_out, 1, w, h, w, h, nframes,
+                        hysteresis_values(w, h, nframes, low, high, connectivity));
     if (rc == MI355_OK)
-        rc = edges_check_dev(ctx, d_in, d_out, w, h, nframes);
+        rc = edges_scratch(ctx, w, h, nframes);
     if (rc != MI355_OK)
         return rc;
     HIP_TRY(ctx, launch_hysteresis(ctx->stream, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
@@ -1880,18 +1896,9 @@ MI355_API int mi355_hysteresis_gray8_dev(mi355_ctx* ctx, const void* d_in, void*
 MI355_API int mi355_hysteresis_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
                                              int low, int high, int connectivity, uint64_t prof_ns[6])
 {
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = hysteresis_values(w, h, nframes, low, high, connectivity);
-    if (rc != MI355_OK)
-        return rc;
-    HostIO io;
-    rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_parent, frame_bytes(w, h, nframes, 4));  // outside the timed window
-    if (rc != MI355_OK)
-        return rc;
-    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+    const int vrc = hysteresis_values(w, h, nframes, low, high, connectivity);
+    auto scratch = [&] { return edges_scratch(ctx, w, h, nframes); };
+    return frames_batched(ctx, in, out, 1, w, h, w, h, nframes, prof_ns, vrc, scratch, [&] {
         return mi355_hysteresis_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, low, high, connectivity);
     });
 }
@@ -1904,12 +1911,11 @@ MI355_API int mi355_canny_check(int w, int h, int nframes, double threshold1, do
 MI355_API int mi355_canny_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_out, int w, int h, int nframes,
                                     double threshold1, double threshold2, int flags)
 {
-    if (!ctx || !d_in || !d_out)
-        return MI355_ERR_BAD_ARG;
     int low = 0, high = 0;
-    int rc = canny_values(w, h, nframes, threshold1, threshold2, flags, &low, &high);
+    int rc = frames_dev(ctx, d_in, d_out, 1, w, h, w, h, nframes,
+                        canny_values(w, h, nframes, threshold1, threshold2, flags, &low, &high));
     if (rc == MI355_OK)
-        rc = edges_check_dev(ctx, d_in, d_out, w, h, nframes);
+        rc = edges_scratch(ctx, w, h, nframes);
     if (rc != MI355_OK)
         return rc;
     uint8_t* out = static_cast<uint8_t*>(d_out);
@@ -1924,18 +1930,9 @@ MI355_API int mi355_canny_gray8_dev(mi355_ctx* ctx, const void* d_in, void* d_ou
 MI355_API int mi355_canny_gray8_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, int h, int nframes,
                                         double threshold1, double threshold2, int flags, uint64_t prof_ns[6])
 {
-    if (!ctx || !in || !out)
-        return MI355_ERR_BAD_ARG;
-    int rc = canny_values(w, h, nframes, threshold1, threshold2, flags, nullptr, nullptr);
-    if (rc != MI355_OK)
-        return rc;
-    HostIO io;
-    rc = stage_host(ctx, (size_t)w * h * nframes, 1, frame_bytes(w, h, nframes, 1), &io);  // BGR input: unsupported
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_parent, frame_bytes(w, h, nframes, 4));  // outside the timed window
-    if (rc != MI355_OK)
-        return rc;
-    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
+    const int vrc = canny_values(w, h, nframes, threshold1, threshold2, flags, nullptr, nullptr);
+    auto scratch = [&] { return edges_scratch(ctx, w, h, nframes); };
+    return frames_batched(ctx, in, out, 1, w, h, w, h, nframes, prof_ns, vrc, scratch, [&] {
         return mi355_canny_gray8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, threshold1, threshold2, flags);
     });
 }
@@ -2079,22 +2076,16 @@ MI355_API size_t mi355_hough_accum_bytes(int w, int h, int nframes, double rho, 
     return hough_values(w, h, nframes, rho, theta, min_theta, max_theta, false, 0, 0, &c) == MI355_OK ? c.accum : 0;
 }
 
-// the pointer rules of the device-resident Hough calls (n ranges: the input first; null entries are absent outputs), then
-// the device, the pooled scratch and the table
-static int hough_check_dev(mi355_ctx* ctx, const HoughCall& c, const void* const* ptr, const size_t* len, int n)
+// What a Hough call pools, device-resident or (before its timed window) host-buffer: the scratch, the table and, for a
+// caller that brings no accumulator, the pooled one
+static int hough_scratch(mi355_ctx* ctx, const HoughCall& c, bool pooled_accum)
 {
-    for (int i = 0; i < n; i++) {
-        if (!ptr[i])
-            continue;
-        if (i > 0 && (reinterpret_cast<uintptr_t>(ptr[i]) & 3u))
-            return MI355_ERR_BAD_ARG;
-        for (int j = 0; j < i; j++)
-            if (ptr[j] && overlap(ptr[i], len[i], ptr[j], len[j]))
-                return MI355_ERR_BAD_ARG;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int rc = ensure(ctx, ctx->d_hough, hough_scratch_bytes(c.g));
-    return rc == MI355_OK ? hough_table_dev(ctx, c) : rc;
+    int rc = ensure(ctx, ctx->d_hough, hough_scratch_bytes(c.g));
+    if (rc == MI355_OK)
+        rc = hough_table_dev(ctx, c);
+    if (rc == MI355_OK && pooled_accum)
+        rc = ensure(ctx, ctx->d_hough_acc, c.accum);
+    return rc;
 }
 
 MI355_API int mi355_hough_accum_gray8_dev(mi355_ctx* ctx, const void* d_in, int32_t* d_accum, int w, int h, int nframes,
@@ -2106,9 +2097,10 @@ MI355_API int mi355_hough_accum_gray8_dev(mi355_ctx* ctx, const void* d_in, int3
     int rc = hough_values(w, h, nframes, rho, theta, min_theta, max_theta, false, 0, 0, &c);
     if (rc != MI355_OK)
         return rc;
-    const void* ptr[2] = {d_in, d_accum};
-    const size_t len[2] = {c.in, c.accum};
-    rc = hough_check_dev(ctx, c, ptr, len, 2);
+    if (bad_ranges({rd(d_in, c.in, 1), wr(d_accum, c.accum, 4)}))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = hough_scratch(ctx, c, false);
     if (rc != MI355_OK)
         return rc;
     HIP_TRY(ctx, launch_hough_accum(ctx->stream, static_cast<const uint8_t*>(d_in), d_accum, ctx->d_hough_tab,
@@ -2126,15 +2118,15 @@ MI355_API int mi355_hough_lines_gray8_dev(mi355_ctx* ctx, const void* d_in, floa
     int rc = hough_values(w, h, nframes, rho, theta, min_theta, max_theta, true, threshold, max_lines, &c);
     if (rc != MI355_OK)
         return rc;
-    const void* ptr[5] = {d_in, d_lines, d_votes, d_count, d_accum};
-    const size_t len[5] = {c.in, c.lines, c.votes, c.count, c.accum};
-    rc = hough_check_dev(ctx, c, ptr, len, 5);
-    if (rc == MI355_OK && !d_accum) {
-        rc = ensure(ctx, ctx->d_hough_acc, c.accum);
-        d_accum = static_cast<int32_t*>(ctx->d_hough_acc.p);
-    }
+    if (bad_ranges({rd(d_in, c.in, 1), wr(d_lines, c.lines, 4), wr(d_votes, c.votes, 4), wr(d_count, c.count, 4),
+                    wr(d_accum, c.accum, 4)}))
+        return MI355_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = hough_scratch(ctx, c, !d_accum);
     if (rc != MI355_OK)
         return rc;
+    if (!d_accum)
+        d_accum = static_cast<int32_t*>(ctx->d_hough_acc.p);
     HIP_TRY(ctx, launch_hough_accum(ctx->stream, static_cast<const uint8_t*>(d_in), d_accum, ctx->d_hough_tab,
                                     ctx->d_hough.p, c.g));
     HIP_TRY(ctx, launch_hough_lines(ctx->stream, d_accum, d_lines, d_votes, d_count, ctx->d_hough.p, c.g, threshold,
@@ -2153,31 +2145,13 @@ MI355_API int mi355_hough_lines_gray8_batched(mi355_ctx* ctx, const uint8_t* in,
     int rc = hough_values(w, h, nframes, rho, theta, min_theta, max_theta, true, threshold, max_lines, &c);
     if (rc != MI355_OK)
         return rc;
-    // the three outputs side by side in the pooled output buffer; the accumulator is the pooled one
-    const size_t at_votes = c.lines, at_count = at_votes + c.votes;
-    HostIO io;
-    rc = stage_host(ctx, c.in, 1, at_count + c.count, &io);  // BGR input: unsupported
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_hough, hough_scratch_bytes(c.g));  // outside the timed window, like the table and ...
-    if (rc == MI355_OK)
-        rc = hough_table_dev(ctx, c);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_hough_acc, c.accum);  // ... the accumulator
-    if (rc != MI355_OK)
-        return rc;
-    io.out_bytes = c.lines;  // what the round trip reads back behind the kernels; the small outputs go ahead of it
-    uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out.p);
-    return timed_roundtrip(ctx, io, in, reinterpret_cast<uint8_t*>(lines), prof_ns, [&] {
-        const int lrc = mi355_hough_lines_gray8_dev(ctx, ctx->d_in.p, reinterpret_cast<float*>(d_out),
-                                                    reinterpret_cast<int32_t*>(d_out + at_votes),
-                                                    reinterpret_cast<int32_t*>(d_out + at_count), nullptr, w, h, nframes, rho,
-                                                    theta, threshold, max_lines, min_theta, max_theta);
-        if (lrc != MI355_OK)
-            return lrc;
-        HIP_TRY(ctx, hipMemcpyAsync(count, d_out + at_count, c.count, hipMemcpyDeviceToHost, ctx->stream));
-        if (votes)
-            HIP_TRY(ctx, hipMemcpyAsync(votes, d_out + at_votes, c.votes, hipMemcpyDeviceToHost, ctx->stream));
-        return (int)MI355_OK;
+    // the lines, then their votes (written on the device whether or not the caller takes them) and the counts; the
+    // accumulator is the pooled one
+    HostOut o[3] = {{lines, c.lines, 4}, {votes, c.votes, 4, true}, {count, c.count, 4}};
+    return outputs_batched(ctx, in, c.in, o, prof_ns, [&] { return hough_scratch(ctx, c, true); }, [&] {
+        return mi355_hough_lines_gray8_dev(ctx, ctx->d_in.p, out_dev<float>(ctx, o[0]), out_dev<int32_t>(ctx, o[1]),
+                                           out_dev<int32_t>(ctx, o[2]), nullptr, w, h, nframes, rho, theta, threshold,
+                                           max_lines, min_theta, max_theta);
     });
 }
 
@@ -2228,9 +2202,8 @@ static int yuv_check_dev(mi355_ctx* ctx, const void* d_yuv, const void* d_other,
     if (rc != MI355_OK)
         return rc;
     const size_t nyuv = yuv_frame_size(*s) * (size_t)nframes, nother = frame_bytes(w, h, nframes, other_bpp);
-    const bool bad = yuv_is_input ? bad_dev_io(d_yuv, nyuv, 1, d_other, nother, other_bpp)
-                                  : bad_dev_io(d_other, nother, other_bpp, d_yuv, nyuv, 1);
-    if (bad)
+    if (bad_ranges({yuv_is_input ? rd(d_yuv, nyuv, 1) : wr(d_yuv, nyuv, 1),
+                    yuv_is_input ? wr(d_other, nother, other_bpp) : rd(d_other, nother, other_bpp)}))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return MI355_OK;
@@ -2293,18 +2266,14 @@ static int yuv_batched(mi355_ctx* ctx, const uint8_t* in, uint8_t* out, int w, i
     int rc = yuv_plan(layout, standard, w, h, nframes, pitch, rows, encode ? 1 : 0, &s);
     if (rc != MI355_OK)
         return rc;
-    if (ctx->input_format == MI355_INPUT_BGR)
-        return MI355_ERR_UNSUPPORTED;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t nyuv = yuv_frame_size(s) * (size_t)nframes, nrgba = frame_bytes(w, h, nframes, 4);
-    const size_t in_bytes = encode ? nrgba : nyuv, out_bytes = encode ? nyuv : nrgba;
-    rc = ensure(ctx, ctx->d_in, in_bytes);
-    if (rc == MI355_OK)
-        rc = ensure(ctx, ctx->d_out, out_bytes);
+    const size_t out_bytes = encode ? nyuv : nrgba;
+    HostIO io;
+    rc = stage_host(ctx, encode ? nrgba : nyuv, 1, out_bytes, &io);  // either input counted in bytes: BGR is unsupported
     if (rc != MI355_OK)
         return rc;
     const bool padded = encode && (s.pitch != w || s.rows != h);
-    return timed_roundtrip(ctx, ctx->d_in.p, in, in_bytes, out, out_bytes, prof_ns, [&] {
+    return timed_roundtrip(ctx, io, in, out, prof_ns, [&] {
         if (!encode)
             return mi355_yuv_to_rgba8_dev(ctx, ctx->d_in.p, ctx->d_out.p, w, h, nframes, layout, standard, pitch, rows);
         if (padded)  // the kernel never writes padding; the host gets zeros there, not the pool's previous content
@@ -2385,7 +2354,7 @@ MI355_API int mi355_checksum_dev(mi355_ctx* ctx, const void* d_buf, size_t nbyte
 
 MI355_API int mi355_stream_copy_dev(mi355_ctx* ctx, void* d_dst, const void* d_src, size_t nbytes)
 {
-    if (!ctx || !d_dst || !d_src || overlap(d_src, nbytes, d_dst, nbytes))
+    if (!ctx || !d_dst || !d_src || bad_ranges({rd(d_src, nbytes, 1), wr(d_dst, nbytes, 1)}))
         return MI355_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_stream_copy(ctx->stream, static_cast<const uint8_t*>(d_src), static_cast<uint8_t*>(d_dst),

@@ -678,33 +678,28 @@ class Context:
         """cv::blur(Size(k, k), BORDER_REPLICATE) of (h, w) / (n, h, w) single-channel frames (MI355_FILTER_BOX_GRAY8)."""
         return self._host_gray8(FILTER_BOX_GRAY8, y, k)
 
-    def adaptive_threshold_gray8(self, y, max_value, type, block, delta, profile=False):
-        """cv::adaptiveThreshold(y, max_value, ADAPTIVE_THRESH_MEAN_C, type, block, delta) of (h, w) / (n, h, w)
-        single-channel frames (mi355_adaptive_threshold_gray8_batched); type is ADAPTIVE_BINARY or ADAPTIVE_BINARY_INV."""
-        frames, one = self._frames("adaptive_threshold_gray8", y, 1)
+    # -- single-output gray8 calls: (frames, out, w, h, n, <the call's own>, prof_ns) -----------------------
+    def _gray8_host(self, fn_name, y, profile, *tail):
+        frames, one = self._frames(fn_name[len("mi355_"):-len("_batched")], y, 1)
         n, h, w = frames.shape
         out = np.empty((n, h, w), np.uint8)
         prof = (ctypes.c_uint64 * 6)()
-        rc = self._lib.mi355_adaptive_threshold_gray8_batched(
-            self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, int(max_value), int(type),
-            int(block), float(delta), prof if profile else None)
-        _check("mi355_adaptive_threshold_gray8_batched", rc, self._h)
+        rc = getattr(self._lib, fn_name)(self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, *tail,
+                                         prof if profile else None)
+        _check(fn_name, rc, self._h)
         out = out[0] if one else out
         return (out, list(prof)) if profile else out
+
+    def adaptive_threshold_gray8(self, y, max_value, type, block, delta, profile=False):
+        """cv::adaptiveThreshold(y, max_value, ADAPTIVE_THRESH_MEAN_C, type, block, delta) of (h, w) / (n, h, w)
+        single-channel frames (mi355_adaptive_threshold_gray8_batched); type is ADAPTIVE_BINARY or ADAPTIVE_BINARY_INV."""
+        return self._gray8_host("mi355_adaptive_threshold_gray8_batched", y, profile, int(max_value), int(type),
+                                int(block), float(delta))
 
     def clahe_gray8(self, y, clip_limit=40.0, tiles_x=8, tiles_y=8, profile=False):
         """cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply() of (h, w) / (n, h, w) single-channel frames
         (mi355_clahe_gray8_batched); the defaults are OpenCV's."""
-        frames, one = self._frames("clahe_gray8", y, 1)
-        n, h, w = frames.shape
-        out = np.empty((n, h, w), np.uint8)
-        prof = (ctypes.c_uint64 * 6)()
-        rc = self._lib.mi355_clahe_gray8_batched(
-            self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, float(clip_limit), int(tiles_x),
-            int(tiles_y), prof if profile else None)
-        _check("mi355_clahe_gray8_batched", rc, self._h)
-        out = out[0] if one else out
-        return (out, list(prof)) if profile else out
+        return self._gray8_host("mi355_clahe_gray8_batched", y, profile, float(clip_limit), int(tiles_x), int(tiles_y))
 
     def ccl_gray8(self, mask, connectivity=8, stats_rows=0, profile=False):
         """cv::connectedComponentsWithStats of (h, w) / (n, h, w) single-channel masks (mi355_ccl_gray8_batched): int32
@@ -755,30 +750,13 @@ class Context:
     def hysteresis_gray8(self, y, low, high, connectivity=8, profile=False):
         """Hysteresis threshold of (h, w) / (n, h, w) single-channel response maps (mi355_hysteresis_gray8_batched): 255
         where the byte > low and the pixel's component of such pixels holds a byte > high, else 0."""
-        frames, one = self._frames("hysteresis_gray8", y, 1)
-        n, h, w = frames.shape
-        out = np.empty((n, h, w), np.uint8)
-        prof = (ctypes.c_uint64 * 6)()
-        rc = self._lib.mi355_hysteresis_gray8_batched(
-            self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, int(low), int(high),
-            int(connectivity), prof if profile else None)
-        _check("mi355_hysteresis_gray8_batched", rc, self._h)
-        out = out[0] if one else out
-        return (out, list(prof)) if profile else out
+        return self._gray8_host("mi355_hysteresis_gray8_batched", y, profile, int(low), int(high), int(connectivity))
 
     def canny_gray8(self, y, threshold1, threshold2, flags=0, profile=False):
         """cv::Canny(y, edges, threshold1, threshold2, 3, flags & CANNY_L2GRADIENT) of (h, w) / (n, h, w) single-channel
         frames (mi355_canny_gray8_batched): 255 on edges, else 0.  No blur of its own: chain gauss_gray8 in front."""
-        frames, one = self._frames("canny_gray8", y, 1)
-        n, h, w = frames.shape
-        out = np.empty((n, h, w), np.uint8)
-        prof = (ctypes.c_uint64 * 6)()
-        rc = self._lib.mi355_canny_gray8_batched(
-            self._h, frames.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), w, h, n, float(threshold1),
-            float(threshold2), int(flags), prof if profile else None)
-        _check("mi355_canny_gray8_batched", rc, self._h)
-        out = out[0] if one else out
-        return (out, list(prof)) if profile else out
+        return self._gray8_host("mi355_canny_gray8_batched", y, profile, float(threshold1), float(threshold2),
+                                int(flags))
 
     def hough_lines_gray8(self, edges, rho, theta, threshold, max_lines=256, min_theta=0.0, max_theta=np.pi,
                           profile=False):
